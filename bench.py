@@ -3,6 +3,7 @@
 (text states -> latent -> mel -> 16 kHz waveform; FLAN-T5 excluded) on N MI355X.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +13,12 @@ decode, HiFi-GAN vocoder, int16 conversion.  A "step" is one such batch.  Clips 
 independent, so N GPUs run N replicas of the batch (weak scaling, no data-path collective);
 the only collectives are the timing barrier / max-reduce over RCCL.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps of the replayed form the headline reports
+and prints the line; --dump-outputs DIR also writes what that form returned in its last timed step (rank 0's int16 waveforms,
+as float32) to DIR/pcm.npy.  Inputs and weights are seeded, so two runs with the same arguments see the same data.
+--full adds everything else, among it the extra objects below: the eager and single-graph rates, the stage split, the
+HBM-bound kernels, the PCIe-inclusive rate, the text encoder, single-clip latency, and the distillation / teacher /
+perceptual legs.  Extra objects:
   roofline     -- conv_gemm (the implicit-GEMM MFMA kernel family = >95 % of the step's FLOPs):
                   algorithmic FLOPs per step / summed launch time per step, measured live with
                   HIP events on the launch stream (ctta_prof_*), against the dense bf16 MFMA peak.
@@ -61,8 +67,37 @@ def parse():
                     help="micro-batch of the configs[4] `fused_micro_batch` leg (train.sh accumulates 15 x 3 samples per GPU)")
     ap.add_argument("--perceptual-batch", type=int, default=4,
                     help="per-GPU micro-batch of the perceptual-loss leg (configs[4] without CLAP)")
-    ap.add_argument("--profile-csv", default=None, help="append one line per MFMA launch (tuning aid)")
-    return ap.parse_args()
+    ap.add_argument("--profile-csv", default=None, help="append one line per MFMA launch (tuning aid; with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: eager and single-graph rates, stage split, roofline, HBM kernels, PCIe, text "
+                         "encoder, single-clip latency, CPU baseline and the distill / teacher / perceptual legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode not in ("both", "gen"):
+        ap.error("--dump-outputs writes the generation step's outputs: use it with --mode both or gen")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes each {name: array} as path/<name>.npy in float32 (float64 stays float64).  An array larger than its even share
+    of `limit` keeps its leading rows (whole clips), the same ones in every run."""
+    import numpy as np
+    share = limit // max(1, len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        row = max(1, a[:1].nbytes)
+        if a.nbytes > share:
+            a = a[:max(1, share // row)]
+        assert a.nbytes <= share, "%s: one row alone is larger than %d bytes" % (name, share)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def launcher_command(argv, n, port, script=None):
@@ -218,69 +253,99 @@ def main():
         N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
         return lat, mel, wav, pcm
 
+    def eager():
+        return step()[3]
+
     # The step as the product runs it for fixed shapes: ONE hipGraph replay of U-Net query -> VAE decoder -> HiFi-GAN -> int16
     # (ConsistencyTTA.capture_graph: handles never allocate or synchronise inside *_forward, so the ~370 launches of a
-    # batch-32 step replay as one submission; bit-identical to the eager launches, asserted here).  CTTA_BENCH_GRAPH=0, or a
-    # failed capture, times the eager launches instead; both rates are reported.
-    timed, launch_mode, genB = step, "eager launches", None
+    # batch-32 step replay as one submission; bit-identical to the eager launches, asserted under --full).  CTTA_BENCH_GRAPH=0,
+    # or a failed capture, times the eager launches instead.
+    # The throughput form of the same step: a 3-deep software pipeline over batches (U-Net of batch i, VAE decoder of batch
+    # i - 1, HiFi-GAN of batch i - 2 as three hipGraphs on three streams per step; ConsistencyTTA.capture_pipeline).  Every
+    # timed step runs every stage once on a full batch; a batch's waveforms leave two steps after its text states entered.
+    # --full captures both, checks each against the eager step, times eager launches, the single graph and the pipeline, and
+    # reports the faster replay.  A plain run captures and times only the pipeline (the faster form in every recorded --full
+    # run since it exists: 426 vs 416 clips/s in profiles/bench_r06.json), the single graph when the pipeline is off or its
+    # capture failed.
     # --no-latency (the PMC passes of tools/refresh_profiles.sh) times eager launches only: graph replays under
     # `rocprofv3 --pmc` hung on this pool in round 1, and counters should not mix replayed and eager steps
     # Rule for every leg below: a capture / parity check is LOCAL (no collective inside), then the ranks agree
     # (du.all_agree: one MAX all-reduce of an error flag) and all of them -- or none -- enter the timing collectives.
-    note = None
-    if os.environ.get("CTTA_BENCH_GRAPH", "1") != "0" and not args.no_latency:
+    use_graph = os.environ.get("CTTA_BENCH_GRAPH", "1") != "0" and not args.no_latency
+    use_pipeline = use_graph and os.environ.get("CTTA_BENCH_PIPELINE", "1") != "0"
+
+    def capture(make, fills, what):
+        """make() -> replay callable, or None with a note when it failed on any rank.  `fills` calls before the check: the
+        pipeline returns the batch fed two calls earlier, so its first two calls return warm-up data."""
+        g_, note_ = None, None
         try:
-            genB = pipe.capture_graph(B, L, cfg_scale_input=4.0)
-            pg = genB(enc, mask, noise)
-            torch.cuda.synchronize()
-            assert torch.equal(pg, step()[3]), "hipGraph replay differs from the eager step"
+            g_ = make()
+            for _ in range(fills):
+                out_ = g_(enc, mask, noise)
+            if args.full:
+                torch.cuda.synchronize()
+                assert torch.equal(out_, eager()), "the %s differs from the eager step" % what
         except Exception as exc:   # a failed capture must not cost the headline line
-            note, genB = "graph capture failed on rank %d: %s" % (rank, str(exc)[:120]), None
-        if du.all_agree(genB is not None, dev):
-            timed, launch_mode = (lambda: genB(enc, mask, noise)), "one hipGraph replay per step"
-        else:
-            launch_mode, genB = "eager launches (%s)" % (note or "graph capture failed on another rank"), None
+            g_, note_ = None, "%s capture failed on rank %d: %s" % (what, rank, str(exc)[:120])
+        if du.all_agree(g_ is not None, dev):
+            return g_, None
+        return None, note_ or "%s capture failed on another rank" % what
 
     def time_loop(fn):
+        """Seconds for the timed steps (max over ranks) and what fn returned in the last one, on the host when it is dumped."""
         for _ in range(args.warmup):
             fn()
         du.barrier(dev)
         t0_ = time.perf_counter()
         for _ in range(args.steps):
-            fn()
+            last = fn()
         du.barrier(dev)
-        return du.max_over_ranks(time.perf_counter() - t0_, dev)
+        dt_ = du.max_over_ranks(time.perf_counter() - t0_, dev)
+        return dt_, (last.float().cpu().numpy() if args.dump_outputs and rank == 0 else None), int(last.shape[1])
 
-    dt = dt_graph1 = time_loop(timed)
-    dt_eager = time_loop(step)      # always, on every rank
-    # The throughput form of the same step: a 3-deep software pipeline over batches (U-Net of batch i, VAE decoder of batch
-    # i - 1, HiFi-GAN of batch i - 2 as three hipGraphs on three streams per step; ConsistencyTTA.capture_pipeline).  Every
-    # timed step runs every stage once on a full batch; a batch's waveforms leave two steps after its text states entered.
+    PIPELINE_MODE = ("three hipGraph replays per step on three streams: U-Net(batch i) | VAE decoder(batch i-1) | "
+                     "HiFi-GAN + int16(batch i-2), handed over by device copies at the step boundary")
+    genB = genP = None
     placement_gen = None
-    if genB is not None and os.environ.get("CTTA_BENCH_PIPELINE", "1") != "0":      # same decision on every rank (agreed above)
-        genP, note = None, None
-        try:
-            genP = pipe.capture_pipeline(B, L, cfg_scale_input=4.0)
-            for _ in range(3):
-                pp = genP(enc, mask, noise)
-            torch.cuda.synchronize()
-            assert torch.equal(pp, step()[3]), "the pipelined replay differs from the eager step"
-        except Exception as exc:
-            note, genP = "pipelined capture failed on rank %d: %s" % (rank, str(exc)[:100]), None
-        if du.all_agree(genP is not None, dev):
-            dt_pipe = time_loop(lambda: genP(enc, mask, noise))
-            placement_gen = genP.placement_ms
-            if dt_pipe < dt:
-                dt = dt_pipe
-                launch_mode = ("three hipGraph replays per step on three streams: U-Net(batch i) | VAE decoder(batch i-1) | "
-                               "HiFi-GAN + int16(batch i-2), handed over by device copies at the step boundary")
-        else:
-            launch_mode += " (%s)" % (note or "pipelined capture failed on another rank")
-        del genP
-    del timed, genB
-    out = step()
-    lat, mel, wav, pcm = out
-    assert bool(torch.isfinite(wav).all()), "non-finite waveform"
+    if args.full:
+        timed, launch_mode, note = eager, "eager launches", None
+        if use_graph:
+            genB, note = capture(lambda: pipe.capture_graph(B, L, cfg_scale_input=4.0), 1, "hipGraph replay")
+            if genB is not None:
+                timed, launch_mode = (lambda: genB(enc, mask, noise)), "one hipGraph replay per step"
+            else:
+                launch_mode = "eager launches (%s)" % note
+        dt, pcm_out, n_samples = time_loop(timed)
+        dt_graph1 = dt
+        dt_eager = time_loop(eager)[0]      # always, on every rank
+        if genB is not None and use_pipeline:      # same decision on every rank (agreed above)
+            genP, note = capture(lambda: pipe.capture_pipeline(B, L, cfg_scale_input=4.0), 3, "pipelined replay")
+            if genP is not None:
+                dt_pipe, pp_out, _ = time_loop(lambda: genP(enc, mask, noise))
+                placement_gen = genP.placement_ms
+                if dt_pipe < dt:
+                    dt, pcm_out, launch_mode = dt_pipe, pp_out, PIPELINE_MODE
+            else:
+                launch_mode += " (%s)" % note
+        del timed
+    else:
+        timed, launch_mode, note = eager, "eager launches", None
+        if use_pipeline:
+            genP, note = capture(lambda: pipe.capture_pipeline(B, L, cfg_scale_input=4.0), 3, "pipelined replay")
+            if genP is not None:
+                timed, launch_mode, placement_gen = (lambda: genP(enc, mask, noise)), PIPELINE_MODE, genP.placement_ms
+        if genP is None and use_graph:
+            genB, note_b = capture(lambda: pipe.capture_graph(B, L, cfg_scale_input=4.0), 1, "hipGraph replay")
+            if genB is not None:
+                timed, launch_mode = (lambda: genB(enc, mask, noise)), "one hipGraph replay per step"
+            note = "; ".join(n_ for n_ in (note, note_b) if n_)
+        if note:
+            launch_mode += " (%s)" % note
+        dt, pcm_out, n_samples = time_loop(timed)
+        del timed
+    del genB, genP
+    if pcm_out is not None:
+        dump_outputs(args.dump_outputs, {"pcm": pcm_out})
     clips_per_s = world * B * args.steps / dt
 
     result = {
@@ -292,13 +357,21 @@ def main():
         "config": {"workload": "configs[1]: batch-32 single-step consistency inference, U-Net(light, 559M) + "
                                "AudioLDM VAE decoder + HiFi-GAN, 10 s clips, L=32 text tokens, w=4, T5 excluded",
                    "batch_per_gpu": B, "global_batch": B * world, "text_len": L, "latent": [8, 256, 16],
-                   "waveform_samples": int(wav.shape[1]), "weights": "random-init (no checkpoints offline)",
+                   "waveform_samples": n_samples, "weights": "random-init (no checkpoints offline)",
                    "parallelism": "replicas x%d (clips sharded, no data-path collective)" % world,
                    "launch": launch_mode},
-        "eager_clips_per_s": round(world * B * args.steps / dt_eager, 3),
-        "single_graph_clips_per_s": round(world * B * args.steps / dt_graph1, 3),
         "stage_stream_placement_ms": placement_gen,
     }
+    if not args.full:
+        emit(result if rank == 0 else None, rank, dev)
+        du.finish()
+        return
+
+    out = step()
+    lat, mel, wav, pcm = out
+    assert bool(torch.isfinite(wav).all()), "non-finite waveform"
+    result["eager_clips_per_s"] = round(world * B * args.steps / dt_eager, 3)
+    result["single_graph_clips_per_s"] = round(world * B * args.steps / dt_graph1, 3)
 
     minimal = os.environ.get("CTTA_BENCH_MINIMAL", "0") == "1"   # profiling aid: the timed loops only (a kernel table with a known step count)
     if rank == 0 and not minimal:

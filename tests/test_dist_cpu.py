@@ -3,6 +3,7 @@ MAX-reduce of elapsed time, clip sharding, global waveform extrema)."""
 import os
 import socket
 
+import pytest
 import torch
 import torch.multiprocessing as mp
 
@@ -102,10 +103,43 @@ def test_bench_builds_the_rank_launcher_command_line():
     assert not any("exec" in c for c in cmd)
 
 
+def test_bench_options_default_to_the_plain_headline_run(monkeypatch):
+    """A plain run is the headline only; --full and --dump-outputs are opt-in, --steps is the timed step count."""
+    import sys
+    bench, _ = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.mode) == (7, 2, False, None, "both")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--mode", "distill", "--dump-outputs", "out"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: int16 waveforms become float32 (exact), float64 stays float64, and an array over its share of the
+    size limit keeps its leading rows -- the same rows in every run."""
+    import numpy as np
+    bench, _ = _load_bench()
+    pcm = (np.arange(6 * 1000) % 65536 - 32768).astype(np.int16).reshape(6, 1000)
+    bench.dump_outputs(str(tmp_path / "a"), {"pcm": pcm, "x": np.linspace(0.0, 1.0, 5)})
+    got = np.load(tmp_path / "a" / "pcm.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pcm.astype(np.float32))
+    assert np.load(tmp_path / "a" / "x.npy").dtype == np.float64
+    bench.dump_outputs(str(tmp_path / "b"), {"pcm": pcm}, limit=4 * 1000 * 4 + 100)
+    got = np.load(tmp_path / "b" / "pcm.npy")
+    assert got.shape == (4, 1000) and np.array_equal(got, pcm[:4].astype(np.float32))
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+
+
 def test_bench_parent_launches_a_child_and_never_touches_the_gpu(tmp_path):
     """The parent of a self-launched run must not import torch (so it cannot initialise HIP), must start the ranks as a
-    CHILD process and hand back the child's exit code.  Dry run: the command line; real run on this GPU-less container:
-    both ranks refuse to run without a GPU and the parent returns their non-zero code instead of hanging."""
+    CHILD process and hand back the child's exit code.  Dry run: the command line; real run with every device hidden from
+    the ranks (so that it fails the same way on a machine with a GPU): both ranks refuse to run without a GPU and the parent
+    returns their non-zero code instead of hanging."""
     import json
     import subprocess
     import sys
@@ -121,6 +155,7 @@ def test_bench_parent_launches_a_child_and_never_touches_the_gpu(tmp_path):
     assert cmd[cmd.index("--nproc-per-node") + 1] == "2"
     env.pop("CTTA_BENCH_LAUNCH_DRYRUN")
     env["CTTA_BENCH_BACKEND"] = "gloo"
+    env["HIP_VISIBLE_DEVICES"] = "-1"                   # no device visible to the ranks, wherever the suite runs
     r = subprocess.run([sys.executable, "-c", probe], capture_output=True, text=True, env=env, timeout=600)
     assert "TORCH_IMPORTED False" in r.stdout, r.stdout + r.stderr
     assert "RC 0" not in r.stdout                       # the ranks' failure is the parent's exit code

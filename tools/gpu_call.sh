@@ -17,7 +17,7 @@ case $what in
     ( time python3 -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.txt 2>&1
     echo "smoke rc=$?" >> $O/smoke.txt
     cd /tmp; export TMPDIR=/tmp
-    ( time timeout 1200 python3 $R/bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt
+    ( time timeout 1200 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt
     echo "bench rc=$?" >> $O/bench.err
     tail -3 $O/tests.txt; tail -2 $O/smoke.txt; tail -c 600 $O/bench.json
     ;;
@@ -31,7 +31,7 @@ case $what in
     for v in "$@"; do
       env_line="$var=$v"
       export "$var=$v"
-      python3 $R/bench.py --mode $mode --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/ab.json
+      python3 $R/bench.py --full --mode $mode --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/ab.json
       python3 - "$env_line" $O/ab.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -7,20 +7,20 @@ R=$PWD
 O=$R/gpurun_out/refresh
 rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 # Kernel tables that belong to ONE launch form each, with the step count in the header (round 5):
 #   gen:     CTTA_BENCH_MINIMAL=1 CTTA_BENCH_GRAPH=0 -> 2 x (1 warm-up + 5 timed) + 1 = 13 eager batch-32 steps, nothing else
 #   distill: CTTA_BENCH_DISTILL_FORMS=eager          -> 1 + 5 eager optimizer steps at batch 9 (+ 2 loss-only forwards of the fixed draw)
-CTTA_BENCH_MINIMAL=1 CTTA_BENCH_GRAPH=0 rocprofv3 --kernel-trace --stats -d $O/prof_gen -o p -- python3 $R/bench.py --mode gen --steps 5 --warmup 1 --no-cpu-baseline > $O/prof_gen.log 2>&1
+CTTA_BENCH_MINIMAL=1 CTTA_BENCH_GRAPH=0 rocprofv3 --kernel-trace --stats -d $O/prof_gen -o p -- python3 $R/bench.py --full --mode gen --steps 5 --warmup 1 --no-cpu-baseline > $O/prof_gen.log 2>&1
 # (round 6: the distillation table is taken in the SINGLE-STREAM form -- no student side stream, no weight-gradient side stream --
 #  so that the kernel times of the table add up to a duration: CTTA_TWO_STREAM=0 is AudioLCM's switch, CTTA_OPT_WGRAD_STREAM=0 the
 #  library option "wgrad_stream" as _native applies it at load)
 CTTA_TWO_STREAM=0 CTTA_OPT_WGRAD_STREAM=0 CTTA_BENCH_DISTILL_FORMS=eager rocprofv3 --kernel-trace --stats -d $O/prof_distill -o p -- python3 $R/bench.py --mode distill --steps 5 --warmup 1 --no-cpu-baseline > $O/prof_distill.log 2>&1
 db=$(find $O/prof_gen -name '*.db' | head -1)
-[ -n "$db" ] && python3 $R/tools/rocpd_stats.py $db $O/rocprof_stats_gen.md "rocprofv3 --kernel-trace over: CTTA_BENCH_MINIMAL=1 CTTA_BENCH_GRAPH=0 bench.py --mode gen --steps 5 --warmup 1 = 13 eager batch-32 generation steps (2 x (1 + 5) timed-loop steps + 1), model set-up kernels (weight init / pack) included" > /dev/null
+[ -n "$db" ] && python3 $R/tools/rocpd_stats.py $db $O/rocprof_stats_gen.md "rocprofv3 --kernel-trace over: CTTA_BENCH_MINIMAL=1 CTTA_BENCH_GRAPH=0 bench.py --full --mode gen --steps 5 --warmup 1 = 13 eager batch-32 generation steps (2 x (1 + 5) timed-loop steps + 1), model set-up kernels (weight init / pack) included" > /dev/null
 db=$(find $O/prof_distill -name '*.db' | head -1)
 [ -n "$db" ] && python3 $R/tools/rocpd_stats.py $db $O/rocprof_stats_distill.md "rocprofv3 --kernel-trace over: CTTA_BENCH_DISTILL_FORMS=eager bench.py --mode distill --steps 5 --warmup 1 = 6 eager optimizer steps at batch 9, every launch on ONE stream (CTTA_TWO_STREAM=0, option wgrad_stream=0: kernel times add up) + 2 loss-only forward passes of the fixed draw + the single-stream profiled step of the roofline object = 7 step-equivalents of MFMA work, model set-up kernels included" > /dev/null
-python3 $R/bench.py --mode gen --steps 3 --warmup 1 --no-cpu-baseline --profile-csv $O/launch_gen.csv > /dev/null 2>&1
+python3 $R/bench.py --full --mode gen --steps 3 --warmup 1 --no-cpu-baseline --profile-csv $O/launch_gen.csv > /dev/null 2>&1
 python3 $R/tools/launch_table.py $O/launch_gen.csv 60 2 > $O/launch_table_gen.txt 2>&1
 CTTA_BENCH_DISTILL_FORMS=none python3 $R/bench.py --mode distill --steps 3 --warmup 1 --no-cpu-baseline --profile-csv $O/launch_distill.csv > /dev/null 2>&1
 python3 $R/tools/launch_table.py $O/launch_distill.csv.distill 60 1 > $O/launch_table_distill.txt 2>&1
@@ -42,8 +42,8 @@ pmc_pass() {   # <counter> <out dir name> <timeout> <bench args...>
   done
   return 1
 }
-pmc_pass FETCH_SIZE pmc_fetch 420 --mode gen --steps 2 --warmup 1 --no-cpu-baseline --no-latency
-pmc_pass WRITE_SIZE pmc_write 420 --mode gen --steps 2 --warmup 1 --no-cpu-baseline --no-latency
+pmc_pass FETCH_SIZE pmc_fetch 420 --full --mode gen --steps 2 --warmup 1 --no-cpu-baseline --no-latency
+pmc_pass WRITE_SIZE pmc_write 420 --full --mode gen --steps 2 --warmup 1 --no-cpu-baseline --no-latency
 python3 $R/tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write > $O/pmc_traffic.json 2> $O/pmc_traffic.err
 # Distillation leg: the PMC passes of that mode hung intermittently in round 1; one step, no warm-up, no latency legs
 # keeps each pass short, and a 300 s timeout bounds the loss when one hangs (tools/pmc_traffic.py ... distill <steps>;
@@ -51,7 +51,7 @@ python3 $R/tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write > $O/pmc_traffic.json 
 pmc_pass FETCH_SIZE pmc_fetch_d 300 --mode distill --steps 1 --warmup 1 --no-cpu-baseline --no-latency
 pmc_pass WRITE_SIZE pmc_write_d 300 --mode distill --steps 1 --warmup 1 --no-cpu-baseline --no-latency
 python3 $R/tools/pmc_traffic.py $O/pmc_fetch_d $O/pmc_write_d distill 18 > $O/pmc_traffic_distill.json 2> $O/pmc_traffic_distill.err
-pmc_pass SQ_VALU_MFMA_BUSY_CYCLES pmc_mfma 300 --mode gen --steps 2 --warmup 1 --no-cpu-baseline --no-latency
+pmc_pass SQ_VALU_MFMA_BUSY_CYCLES pmc_mfma 300 --full --mode gen --steps 2 --warmup 1 --no-cpu-baseline --no-latency
 python3 $R/tools/pmc_mfma_util.py $O/pmc_mfma > $O/pmc_mfma_util.json 2> $O/pmc_mfma_util.err
 # where a hipGraph-replayed distillation step spends its time: idle / one kernel / two kernels, dispatch counts, idle gaps by kernel
 # pair (three monolithic-graph steps between AdamW launches: eager 1+3, segmented 1+3, monolithic 1+3 -> AdamW launches 8..11)
