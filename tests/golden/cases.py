@@ -88,6 +88,26 @@ def prompt_states(cfg, B, L, tag):
     return dict(embeds_cf=torch.cat([uncond, cond]), mask_cf=torch.cat([umask, cmask]), embeds=cond, mask=cmask)
 
 
+def batch32_inputs():
+    """BASELINE.json configs[1] at its benchmarked size: 32 clips, L = 32 text states with ragged masks (6..32 valid
+    tokens) and unit-variance latent noise.  Shared by make_golden_batch32.py and the batch-32 GPU tests, so the
+    fixture and the tests cannot drift apart."""
+    B, L = 32, 32
+    gen = torch.Generator().manual_seed(3)
+    enc = torch.randn(B, L, 1024, generator=gen) * 0.25
+    lens = torch.randint(6, L + 1, (B,), generator=gen)
+    mask = torch.arange(L)[None, :] < lens[:, None]
+    noise = torch.randn(B, 8, 256, 16, generator=gen)
+    return dict(enc=enc, lens=lens, mask=mask, noise=noise)
+
+
+def batch32_clips(lens):
+    """The clips `pipeline_batch32.npz` stores in full: the first and the last row of the batch and the shortest mask
+    (a fourth clip would take the file past 1 MiB; every clip has its strided samples and norms)."""
+    lens = np.asarray(lens)
+    return sorted({0, len(lens) - 1, int(lens.argmin())})
+
+
 def sample_index(numel, n=512):
     """Deterministic strided sample positions inside a flattened tensor: what `distill_light.npz` keeps of every
     gradient tensor (the full gradient is 2.2 GB)."""
@@ -193,3 +213,18 @@ def eval_kl_names(n):
     names = ["clip_%03d.wav" % i for i in range(n)]
     perm = np.random.RandomState(5).permutation(n)
     return names, perm
+
+
+def distill_draws(B, seed):
+    """Random draws INJECTED into the reference's `AudioLCM.forward` by make_golden_distill_light.py --draw-seed (and
+    replayed by the GPU test): time indices in 0..16 (times 2 inside forward), unit noise for the latents, uniform
+    guidance draws (times 6).  Index 0 (the `last_mask` branch) and 16 (the largest) are always present, and so are
+    guidance draws near 0 and near 1 (scales near 0 and near 6)."""
+    assert B >= 4
+    gen = torch.Generator().manual_seed(seed)
+    time_inds = torch.randint(0, 17, (B,), generator=gen)
+    time_inds[0], time_inds[1] = 0, 16
+    noise = torch.randn(B, 8, 256, 16, generator=gen)
+    u = torch.rand(B, generator=gen)
+    u[2], u[3] = 0.003, 0.997
+    return time_inds, noise, u

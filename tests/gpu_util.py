@@ -72,3 +72,27 @@ def rel_l2(a, b):
 def det(name, shape, seed=0, scale=1.0):
     from consistencytta_amd import spec
     return torch.from_numpy(spec.det_uniform(name, shape, seed)) * scale
+
+
+def light_pipeline(scale_factor):
+    """BASELINE.json configs[1]'s pipeline (light U-Net, full-width VAE decoder and HiFi-GAN) with the seeded weights of
+    the parity fixtures (`pipeline_light.npz`, `pipeline_batch32.npz`)."""
+    import cases
+    from consistencytta_amd import modules, spec
+    from consistencytta_amd.models import ConsistencyTTA
+    vae = modules.AutoencoderKL(ddconfig=spec.VAE_DDCONFIG, embed_dim=8, scale_factor=scale_factor,
+                                hifigan_config=spec.HIFIGAN_16K_64)
+    sd = dict(cases.vae_weights(spec.VAE_DDCONFIG))
+    sd.update(cases.hifigan_weights(spec.HIFIGAN_16K_64))
+    vae.load_state_dict(sd)
+    pipe = ConsistencyTTA(unet_config=spec.LIGHT_UNET_CONFIG, vae=vae)
+    pipe.unet.load_state_dict(cases.unet_weights(spec.LIGHT_UNET_CONFIG, True))
+    return pipe.to(DEV).eval().requires_grad_(False)
+
+
+def run_light_pipeline(pipe, enc, mask, noise):
+    """One U-Net query (w = 4, no post-CFG) -> VAE decoder -> HiFi-GAN, eager: (latent, mel, float waveform)."""
+    lat = pipe.generate_latent(enc.to(DEV), mask.to(DEV), noise.to(DEV), cfg_scale_input=4.0, cfg_scale_post=1.0,
+                               num_steps=1)
+    mel = pipe.vae.decode_first_stage(lat)
+    return lat, mel, pipe.vae.vocode(mel)

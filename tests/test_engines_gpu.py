@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 import cases  # noqa: E402
 from consistencytta_amd import _native as N, modules, scheduler, spec  # noqa: E402
-from gpu_util import DEV, rel_err, rel_l2  # noqa: E402
+from gpu_util import DEV, light_pipeline, rel_err, rel_l2, run_light_pipeline  # noqa: E402
 from oracle import nets as onets  # noqa: E402
 
 REL_L2 = 2.5e-2
@@ -202,7 +202,7 @@ def test_pipeline_config1_end_to_end(golden):
     wav = v.vocode(mel)
     assert wav.shape[1] == 163872
     ref_head = torch.from_numpy(g["wav_head"])
-    _report("pipeline waveform head", wav[:, :ref_head.shape[1]], ref_head)
+    _check("pipeline waveform head", wav[:, :ref_head.shape[1]], ref_head)
     assert bool(torch.isfinite(wav).all()) and float(wav.abs().max()) <= 1.0
 
 
@@ -215,25 +215,12 @@ def test_pipeline_batch32_shards_into_single_clip_runs(golden):
     batch size -- tools/order_noise.py) moves the bf16 result by the same 9.2e-3 relative L2 in the latent (1.9e-2
     mel, 1.6e-2 waveform): the bf16 rounding-noise floor, below the 1.2e-2 / 1.9e-2 distance to the fp32 reference.
     The tolerances are that floor with 2x margin; a replay of the batch itself is bit-exact."""
-    from consistencytta_amd.models import ConsistencyTTA
-    g = golden("pipeline_light")
-    cfg = spec.LIGHT_UNET_CONFIG
-    v, _ = _vae(spec.VAE_DDCONFIG, spec.HIFIGAN_16K_64)
-    v.scale_factor = float(g["scale_factor"])
-    pipe = ConsistencyTTA(unet_config=cfg, vae=v)
-    _load(pipe.unet, cases.unet_weights(cfg, True))
-    B, L = 32, 32
-    gen = torch.Generator().manual_seed(3)
-    enc = torch.randn(B, L, 1024, generator=gen) * 0.25
-    lens = torch.randint(6, L + 1, (B,), generator=gen)
-    mask = torch.arange(L)[None, :] < lens[:, None]
-    noise = torch.randn(B, 8, 256, 16, generator=gen)
+    pipe = light_pipeline(float(golden("pipeline_light")["scale_factor"]))
+    X = cases.batch32_inputs()
+    B = X["noise"].shape[0]
 
     def run(sel):
-        lat = pipe.generate_latent(enc[sel].to(DEV), mask[sel].to(DEV), noise[sel].to(DEV), cfg_scale_input=4.0,
-                                   cfg_scale_post=1.0, num_steps=1)
-        mel = v.decode_first_stage(lat)
-        return lat, mel, v.vocode(mel)
+        return run_light_pipeline(pipe, X["enc"][sel], X["mask"][sel], X["noise"][sel])
     full = run(slice(0, B))
     again = run(slice(0, B))
     for a, b in zip(full, again):
@@ -246,6 +233,85 @@ def test_pipeline_batch32_shards_into_single_clip_runs(golden):
             err = rel_l2(a.float().cpu(), b.float().cpu())
             print("clip %d %s: batch-32 vs alone rel_l2 %.2e" % (i, tag, err))
             assert err < tol, (i, tag, err)
+
+
+# Per-clip outlier bound of the batch-32 test: on this random-init network the distance to the reference is the bf16
+# rounding noise, statistically the same for every clip, and a 512-entry sample estimates a clip's relative L2 to about
+# 5 % -- measured, the worst of the 32 clips is 1.10x the batch median in the latent and 1.11x in the mel.  A clip above
+# 1.3x its batch mates' median has an error of its own: one valid token masked out of clip 17's 14 makes 1.80x in the
+# latent and 1.49x in the mel, and no other clip moves.
+OUTLIER = 1.3
+
+
+def test_pipeline_batch32_against_reference_golden(golden):
+    """BASELINE.json configs[1] at the size bench.py times (batch 32, L = 32, ragged masks: the 256x256x64 conv tile,
+    the FFN GEGLU kernel, the eight-wave HiFi-GAN unit forms at 1024 mel frames) against the reference's own modules,
+    clip by clip (tests/golden/make_golden_batch32.py).  The clips stored in full (rows 0 and 31 and the shortest mask)
+    are checked at the REL_L2 / REL_MAX contract; every one of the 32 clips by the relative L2 of a
+    512-entry strided sample and by its full norm, and by how far that distance stands out from the other clips' (OUTLIER),
+    so an error confined to one row of the batch fails here; the int16
+    output of decode_to_waveform (batch-global centring) at the stored positions within the bound of
+    test_vae_and_hifigan_tiny."""
+    g = golden("pipeline_batch32")
+    X = cases.batch32_inputs()
+    assert np.array_equal(X["lens"].numpy(), g["lens"]), "inputs changed: mask lengths"
+    for k in ("enc", "noise"):
+        got = float(X[k].double().sum())
+        assert abs(got - float(g[k + "_sum"])) <= 1e-9 * float(X[k].double().abs().sum()), "inputs changed: " + k
+    clips = [int(c) for c in g["clips"]]
+    assert clips == cases.batch32_clips(g["lens"])
+    pipe = light_pipeline(float(g["scale_factor"]))
+    lat, mel, wav = run_light_pipeline(pipe, X["enc"], X["mask"], X["noise"])
+    B = lat.shape[0]
+    assert wav.shape == (B, 163872)
+    head, stride = int(g["wav_head_len"]), int(g["wav_stride"])
+    for j, b in enumerate(clips):
+        tag = "batch32 clip %d (%d tokens)" % (b, int(g["lens"][b]))
+        _check(tag + " latent", lat[b], torch.from_numpy(g["latent"][j].astype(np.float32)))
+        _check(tag + " mel", mel[b], torch.from_numpy(g["mel"][j].astype(np.float32)))
+        _check(tag + " waveform head", wav[b, :head], torch.from_numpy(g["wav_head"][j].astype(np.float32)))
+        _check(tag + " waveform 1-in-%d" % stride, wav[b, ::stride], torch.from_numpy(g["wav_strided"][j].astype(np.float32)))
+    worst, bad = {}, []
+    for key, got in (("latent", lat), ("mel", mel), ("wav", wav)):
+        l2s = []
+        flat = got.reshape(B, -1).float()
+        idx = torch.from_numpy(cases.sample_index(flat.shape[1])).to(DEV)
+        sampled = flat[:, idx].double().cpu().numpy()
+        ref = g[key + "_samples"].astype(np.float64)
+        norms = flat.double().norm(dim=1).cpu().numpy()
+        absmax = flat.abs().amax(dim=1).double().cpu().numpy()
+        for b in range(B):
+            l2 = float(np.linalg.norm(sampled[b] - ref[b]) / np.linalg.norm(ref[b]))
+            dn = abs(norms[b] - g[key + "_norm"][b]) / g[key + "_norm"][b]
+            dm = abs(absmax[b] - g[key + "_absmax"][b]) / g[key + "_absmax"][b]
+            l2s.append(l2)
+            if l2 > worst.get(key, (0, -1.0))[1]:
+                worst[key] = (b, l2)
+            if not (np.isfinite(l2) and l2 <= REL_L2 and dn <= REL_L2 and dm <= REL_MAX):
+                bad.append("clip %d %s: sampled rel_l2 %.3e, norm deviation %.3e, absmax deviation %.3e" % (b, key, l2, dn, dm))
+        med = float(np.median(l2s))
+        print("batch32 %-6s sampled rel_l2 over the clips: median %.3e, worst %.3e (clip %d, %.2fx the median)"
+              % (key, med, worst[key][1], worst[key][0], worst[key][1] / med))
+        if key != "wav":     # the waveform's distance is mostly bf16 order noise of its own (the vocoder's), alike for all
+            bad += ["clip %d %s: sampled rel_l2 %.3e is %.2fx the batch median %.3e" % (b, key, l2s[b], l2s[b] / med, med)
+                    for b in range(B) if l2s[b] > OUTLIER * med]
+    assert not bad, bad
+    # decode_to_waveform: vocoder_infer's int16 with the batch-global (max + min) / 2 centre of all 32 clips
+    pcm = pipe.vae.decode_to_waveform(mel)
+    assert pcm.dtype == np.int16 and pcm.shape == (B, 163872)
+    centre = np.float32(g["wav_centre"])
+
+    def ref_pcm(w):
+        return ((w.astype(np.float32) - centre) * np.float32(32768)).astype(np.int16).astype(np.int64)
+    n = pcm.shape[1]
+    pairs = [(pcm[:, cases.sample_index(n)], ref_pcm(g["wav_samples"]))]
+    for j, b in enumerate(clips):
+        pairs += [(pcm[b, :head], ref_pcm(g["wav_head"][j])), (pcm[b, ::stride], ref_pcm(g["wav_strided"][j]))]
+    for got, ref in pairs:
+        scale = float(np.abs(ref).max())
+        err = float(np.abs(got.astype(np.int64) - ref).max())
+        print("batch32 int16 waveform: max abs error %.0f of %.0f" % (err, scale))
+        assert err <= REL_MAX * scale + 2
 
 
 def test_vae_encoder_against_reference_golden_and_oracle_taps(golden):

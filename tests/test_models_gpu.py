@@ -326,6 +326,40 @@ def test_three_stage_batch_pipeline_equals_the_eager_pipeline_two_calls_later():
         assert np.array_equal(outs[j + 2], ref), j
 
 
+def test_batch32_graph_and_three_stage_pipeline_equal_eager_bit_for_bit(golden):
+    """The forms bench.py times for BASELINE.json configs[1] -- `capture_graph(32, 32, cfg_scale_input=4.0)` and
+    `capture_pipeline(32, 32, cfg_scale_input=4.0)`, the arguments of bench.py -- at the light widths, on the batch of
+    `cases.batch32_inputs()` that test_engines_gpu.py pins against the reference's own modules: their int16 output equals
+    the eager pipeline's bit for bit.  The pipeline gets three different batches (the fixture's batch, a row-permuted
+    copy of it, a fresh draw) and is drained; every output must be its own batch's, two calls later."""
+    from gpu_util import light_pipeline, run_light_pipeline
+    pipe = light_pipeline(float(golden("pipeline_batch32")["scale_factor"]))
+    X = cases.batch32_inputs()
+    B, L = X["enc"].shape[:2]
+    perm = torch.randperm(B, generator=torch.Generator().manual_seed(7))
+    gen = torch.Generator().manual_seed(4)
+    lens = torch.randint(6, L + 1, (B,), generator=gen)
+    batches = [(X["enc"], X["mask"], X["noise"]), (X["enc"][perm], X["mask"][perm], X["noise"][perm]),
+               (torch.randn(B, L, 1024, generator=gen) * 0.25, torch.arange(L)[None, :] < lens[:, None],
+                torch.randn(B, 8, 256, 16, generator=gen))]
+    batches = [tuple(t.to(DEV) for t in b) for b in batches]
+    refs = []
+    for b in batches:
+        lat, mel, _ = run_light_pipeline(pipe, *b)
+        refs.append(pipe.vae.decode_to_waveform(mel))
+    assert refs[0].shape == (B, 163872) and not np.array_equal(refs[0], refs[1])
+    graph = pipe.capture_graph(B, L, cfg_scale_input=4.0)
+    for b, ref in zip(batches, refs):
+        assert np.array_equal(graph(*b).cpu().numpy(), ref)
+    del graph
+    gen3 = pipe.capture_pipeline(B, L, cfg_scale_input=4.0)
+    outs = []
+    for b in batches + batches[-1:] * 2:                  # two extra calls drain the pipeline
+        outs.append(gen3(*b).cpu().numpy().copy())
+    for j, ref in enumerate(refs):
+        assert np.array_equal(outs[j + 2], ref), j
+
+
 class _FakeTokenizer:
     """Whitespace tokenizer with T5's calling convention (the sentencepiece model is not available offline)."""
     model_max_length = 512

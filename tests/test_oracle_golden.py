@@ -156,6 +156,39 @@ def test_vae_hifigan_full_width(golden):
         close(wav, g["wav"])
 
 
+@pytest.mark.slow
+def test_pipeline_batch32_shortest_mask_clip(golden):
+    """`pipeline_batch32.npz` (the reference's modules at BASELINE.json configs[1]'s size) against the independent
+    oracle on the clip with the shortest mask, run alone: U-Net query, VAE decoder, HiFi-GAN.  The full arrays are
+    float16 in the fixture, hence 2^-11 on top of the round-off tolerance; the fp32 samples and fp64 norms at round-off."""
+    g = golden("pipeline_batch32")
+    X = cases.batch32_inputs()
+    assert np.array_equal(X["lens"].numpy(), g["lens"]), "inputs changed: mask lengths"
+    b = int(np.argmin(g["lens"]))
+    j = [int(c) for c in g["clips"]].index(b)
+    cfg = spec.LIGHT_UNET_CONFIG
+    ts, sig = heun.set_timesteps(18)
+    sigma = torch.tensor([float(sig.max())])
+    with torch.no_grad():
+        z_in = heun.scale_model_input(X["noise"][b:b + 1] * sigma, sigma)
+        lat = nets.unet_forward(cfg, cases.unet_weights(cfg, True), z_in, float(ts[0]), 4.0, X["enc"][b:b + 1],
+                                X["mask"][b:b + 1])
+        sd = dict(cases.vae_weights(spec.VAE_DDCONFIG))
+        sd.update(cases.hifigan_weights(spec.HIFIGAN_16K_64))
+        mel = nets.vae_decode(spec.VAE_DDCONFIG, sd, lat, float(g["scale_factor"]))
+        wav, _, _ = nets.mel_to_waveform(spec.HIFIGAN_16K_64, sd, mel)
+    fp16 = 2e-4 + 2.0 ** -11
+    close(lat[0], g["latent"][j], fp16)
+    close(mel[0], g["mel"][j], fp16)
+    head, stride = int(g["wav_head_len"]), int(g["wav_stride"])
+    close(wav[0, :head], g["wav_head"][j], fp16)
+    close(wav[0, ::stride], g["wav_strided"][j], fp16)
+    for key, got in (("latent", lat), ("mel", mel), ("wav", wav)):
+        flat = got.reshape(-1).double().numpy()
+        close(flat[cases.sample_index(flat.size)], g[key + "_samples"][b])
+        assert abs(np.linalg.norm(flat) - g[key + "_norm"][b]) <= 2e-4 * g[key + "_norm"][b], key
+
+
 def _distill_setup():
     prompt_states = cases.prompt_states
     from oracle import distill

@@ -958,12 +958,49 @@ def _block_of(key):
     return head + "." + rest.split(".")[0] if head in ("down_blocks", "up_blocks") else head
 
 
+def _fixture_grad_samples(g):
+    """The strided gradient samples of a distill_light*.npz fixture, fp64 (stored as fp32, or as bfloat16 bit patterns)."""
+    if "grad_samples_bf16" in g.files:
+        return torch.from_numpy(g["grad_samples_bf16"]).view(torch.bfloat16).double().numpy()
+    return g["grad_samples"].astype(np.float64)
+
+
+def _check_student_grads(tag, m, g):
+    """The student's gradients against a distill_light*.npz fixture: per block (`_block_of`) the relative L2 over the
+    strided 512-entry samples <= GRAD_REL_L2_ALL, per tensor the deviation of the full norm <= GRAD_REL_L2."""
+    sample_index = cases.sample_index
+    names = [str(k) for k in g["grad_names"]]
+    params = dict(m.student_unet.named_parameters())
+    assert names == [k for k, p in params.items() if p.requires_grad]
+    off, samples, norms = g["grad_offsets"], _fixture_grad_samples(g), g["grad_norms"]
+    blocks, worst_norm = {}, ("", 0.0)
+    for i, k in enumerate(names):
+        gr = params[k].grad.detach().reshape(-1)
+        idx = torch.from_numpy(sample_index(gr.numel())).to(DEV)
+        got = gr[idx].double().cpu().numpy()
+        ref = samples[off[i]:off[i + 1]]
+        b = blocks.setdefault(_block_of(k), [0.0, 0.0])
+        b[0] += float(((got - ref) ** 2).sum())
+        b[1] += float((ref ** 2).sum())
+        nrel = abs(float(gr.double().norm()) - norms[i]) / max(norms[i], 1e-30)
+        if nrel > worst_norm[1]:
+            worst_norm = (k, nrel)
+    tot_e = sum(b[0] for b in blocks.values())
+    tot_n = sum(b[1] for b in blocks.values())
+    for name, (e, n) in blocks.items():
+        print("  %-28s sampled grad rel_l2 %.3e" % (name, (e / max(n, 1e-300)) ** 0.5))
+    print("%s, all blocks: sampled rel_l2 %.3e ; worst per-tensor norm deviation %s %.3e"
+          % (tag, (tot_e / tot_n) ** 0.5, worst_norm[0], worst_norm[1]))
+    for name, (e, n) in blocks.items():
+        assert (e / max(n, 1e-300)) ** 0.5 <= GRAD_REL_L2_ALL, (tag, name)
+    assert worst_norm[1] <= GRAD_REL_L2, (tag, worst_norm)
+
+
 def test_distillation_step_at_light_widths_matches_reference(golden):
     """`AudioLCM.forward` + backward at `tango_diffusion_light.json` widths (the code path the
     bench times: split-K deep-level GEMMs, wgrad scatter, 64x64 K/V tiles) vs the reference's loss and autograd
     gradients.  The fixture holds every tensor's gradient norm and a strided 512-entry sample of it; tolerances:
     loss 5e-2 relative, per-block sampled-gradient relative L2 4e-2, per-tensor norm 8e-2."""
-    sample_index = cases.sample_index
     g = golden("distill_light")
     m, P, z0 = _lcm_light(2, 16, "distill_light")
     m.train()
@@ -975,39 +1012,55 @@ def test_distillation_step_at_light_widths_matches_reference(golden):
     assert abs(float(loss) - ref_loss) <= 5e-2 * ref_loss
     loss.backward()
     torch.cuda.synchronize()
-    names = [str(k) for k in g["grad_names"]]
-    params = dict(m.student_unet.named_parameters())
-    assert names == [k for k, p in params.items() if p.requires_grad]
-    off, samples, norms = g["grad_offsets"], g["grad_samples"], g["grad_norms"]
-    blocks, worst_norm = {}, ("", 0.0)
-    for i, k in enumerate(names):
-        gr = params[k].grad.detach().reshape(-1)
-        idx = torch.from_numpy(sample_index(gr.numel())).to(DEV)
-        got = gr[idx].double().cpu().numpy()
-        ref = samples[off[i]:off[i + 1]].astype(np.float64)
-        b = blocks.setdefault(_block_of(k), [0.0, 0.0])
-        b[0] += float(((got - ref) ** 2).sum())
-        b[1] += float((ref ** 2).sum())
-        nrel = abs(float(gr.double().norm()) - norms[i]) / max(norms[i], 1e-30)
-        if nrel > worst_norm[1]:
-            worst_norm = (k, nrel)
-    tot_e = sum(b[0] for b in blocks.values())
-    tot_n = sum(b[1] for b in blocks.values())
-    for name, (e, n) in blocks.items():
-        print("  %-28s sampled grad rel_l2 %.3e" % (name, (e / max(n, 1e-300)) ** 0.5))
-    print("all blocks: sampled rel_l2 %.3e ; worst per-tensor norm deviation %s %.3e"
-          % ((tot_e / tot_n) ** 0.5, worst_norm[0], worst_norm[1]))
-    for name, (e, n) in blocks.items():
-        assert (e / max(n, 1e-300)) ** 0.5 <= GRAD_REL_L2_ALL, name
-    assert worst_norm[1] <= GRAD_REL_L2, worst_norm
+    _check_student_grads("B=2 light eager", m, g)
     for name in ("teacher_unet", "student_target_unet", "student_ema_unet"):
         assert all(p.grad is None for p in getattr(m, name).parameters())
+
+
+def test_distillation_step_b9_matches_reference_eager_and_pipelined_graph(golden):
+    """BASELINE configs[3] at its benchmarked size (per-GPU batch 9, L = 32: stream-K and two-pass split-K on the deep
+    levels, the ragged masks of a real batch) against the reference's own AudioLCM + autograd
+    (`distill_light_b9.npz`, make_golden_distill_light.py --draw-seed): the random draws were injected into the
+    reference and are rebuilt here from the seed (time indices 0 and 16 -- the `last_mask` branch and the largest index --
+    guidance scales near 0 and near 6).  The eager step, then the pipelined-teacher graph (the form bench.py's
+    distillation leg replays) on the same draws, at the bounds of the B = 2 test."""
+    g = golden("distill_light_b9")
+    B = 9
+    ti, noise, u = cases.distill_draws(B, int(g["draw_seed"]))
+    assert np.array_equal(ti.numpy(), g["time_inds"]), "injected draws changed: time indices"
+    assert np.array_equal((u * 6).numpy(), g["guidance"]), "injected draws changed: guidance"
+    assert abs(float(noise.double().sum()) - float(g["noise_sum"])) <= 1e-9 * float(noise.double().abs().sum()), \
+        "injected draws changed: noise"
+    assert 0 in ti and 16 in ti
+    m, P, z0 = _lcm_light(B, 32, "distill_full")
+    m.train()
+    kw = dict(time_inds=ti * 2, gaussian_noise=noise.to(DEV), guidance_scale=u * 6)
+    ref_loss = float(g["train_loss"])
+    loss = m(z0, None, P, **kw)
+    print("B=9 light distillation loss hip %.6f ref %.6f" % (float(loss), ref_loss))
+    assert abs(float(loss) - ref_loss) <= 5e-2 * ref_loss
+    loss.backward()
+    torch.cuda.synchronize()
+    _check_student_grads("B=9 light eager", m, g)
+    opt = m.prepare_training(lr=1e-5, weight_decay=1e-4, broadcast=False)
+    gs = m.capture_train_graph(opt, z0, P, segmented=False, pipeline_teacher=True, **kw)
+    assert float(opt.grad.abs().max()) == 0.0
+    gs.feed(z0, **kw)
+    assert gs.feed(z0, **kw) is True                 # the first feed becomes the current set
+    gs.replay()
+    torch.cuda.synchronize()
+    print("B=9 light distillation loss, pipelined-teacher graph %.6f ref %.6f" % (float(gs.loss.item()), ref_loss))
+    assert abs(float(gs.loss.item()) - ref_loss) <= 5e-2 * ref_loss
+    _check_student_grads("B=9 light pipelined-teacher graph", m, g)
+    opt.zero_grad()
+    del gs
 
 
 def test_distillation_step_full_batch_is_deterministic_and_blockwise_exact():
     """BASELINE configs[3] at its real size (per-GPU batch 9, L = 32): two identical steps give bit-identical losses
     and gradients outside the LayerNorm affine atomics, and the block-wise (overlappable) backward equals the
-    monolithic one -- size-independent properties where no CPU reference can run."""
+    monolithic one, and the captured forms equal the eager step -- properties of the engine itself; the same size
+    against the reference's own step is test_distillation_step_b9_matches_reference_eager_and_pipelined_graph."""
     m, P, z0 = _lcm_light(9, 32, "distill_full")
     m.train()
     gen = torch.Generator().manual_seed(5)
