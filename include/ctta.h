@@ -200,6 +200,32 @@ void ctta_mel_frontend_destroy(ctta_mel_frontend* h);
 ctta_status ctta_wav_to_fbank(ctta_mel_frontend* h, const float* wav, int batch, int n_samples,
                               int target_length, float* fbank, float* logmag, void* stream);
 
+/* Mix augmentation of the training batch (csrc/mix_augment.hip).  The handle owns the fp32 periodic-Hann, twiddle and
+ * A-weight tables (computed on the host in float64, uploaded once) and a workspace for max_clips clips of up to
+ * max_samples samples and max_pairs pairs.  fs is 16000 (n_fft 2048) or 44100 (n_fft 4096), anything else is
+ * CTTA_ERR_INVALID (tools/mix.py:19-24 raises); mode 0 = "A_weighting", 1 = "RMSE".  Calls on one handle must not overlap.
+ * ctta_mixer_frames: frames of a clip, (n_samples - n_fft) / (n_fft / 2) + 1 (0 when shorter than n_fft).
+ * ctta_mixer_gain_db replaces tools/mix.py:18-43 (compute_gain) for n_clips clips at once: wav [n_clips][ld] f32 ->
+ * gain_db [n_clips][frames] f32, 10 log10(max(E, 10^(min_db/10))) per frame (no padding, partial tail dropped).
+ * ctta_mixer_mix replaces tools/torch_tools.py:117-123 over tools/mix.py:46-51 (mix at ratio r): for pair p with clip indices
+ * pairs[2p], pairs[2p+1] (DEVICE int32, read by the kernel: a captured graph takes new pairs) the mixture
+ * (s1 t + s2 (1 - t)) / sqrt(t^2 + (1 - t)^2), t = 1 / (1 + 10^((g1 - g2)/20) (1 - r)/r) with g the clip's maximum frame
+ * gain, is written to dst row dst_row0 + p.  n_groups > 0 splits the pairs into that many equal consecutive groups and
+ * divides each group by its own max |.|, then by 2 (torch_tools.py:121, one collate per group; an all-silent group is
+ * 0/0 = NaN as in the reference); n_groups = 0 leaves the mixtures unnormalised (mix.py's mix).  t_out [n_pairs] and
+ * g_out [n_pairs][2] (f32, may be NULL) receive t and (g1, g2).  A pair index outside [0, n_clips) gives a NaN row.
+ * dst rows must not overlap the source rows.  Three launches, no host synchronisation, deterministic. */
+typedef struct ctta_mixer ctta_mixer;
+ctta_status ctta_mixer_create(int fs, int mode, float min_db, int max_clips, int max_samples, int max_pairs,
+                              ctta_mixer** out);
+void ctta_mixer_destroy(ctta_mixer* h);
+int ctta_mixer_frames(const ctta_mixer* h, int n_samples);
+ctta_status ctta_mixer_gain_db(ctta_mixer* h, const float* wav, int n_clips, int n_samples, int64_t ld, float* gain_db,
+                               void* stream);
+ctta_status ctta_mixer_mix(ctta_mixer* h, const float* wav, int n_clips, int n_samples, int64_t ld, const int32_t* pairs,
+                           int n_pairs, int n_groups, double r, float* dst, int64_t dst_ld, int dst_row0, float* t_out,
+                           float* g_out, void* stream);
+
 /* ------------------------------------------------------------------------------------ *
  * Text encoder.  Replaces `self.text_encoder(input_ids=, attention_mask=)[0]` of
  * models/audio_distilled_model.py:208-214 (transformers T5EncoderModel, FLAN-T5-large; weights in the
