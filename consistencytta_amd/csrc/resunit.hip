@@ -641,7 +641,7 @@ extern "C" ctta_status ctta_frag_pack(const void* packed, int n, int k_pad, int 
 }
 
 static size_t resunit_smem(int C, int WP, int T, int k, int dil) {
-  const int H1 = dil * (k - 1) / 2;
+  const long long H1 = (long long)dil * (k - 1) / 2;                   // 64-bit: the predicate is asked about any int dilation
   size_t smem = (size_t)(T + 16 * WP + 2 * H1) * (C + 8) * 2;      // WP * (T/16/WP + 1) blocks of 16 rows + the conv1 halo
   const size_t stage = (size_t)WP * 32 * (C * 4 + 16);
   return stage > smem ? stage : smem;
@@ -682,19 +682,43 @@ static int resunit_tile512(int k, int dil) {
   return 0;
 }
 
+// The launcher's geometry per width: positions per workgroup T (0 at C = 512 when no tile fits), wave parts WP, threads NT.
+// C = 256 / 512: eight waves, one workgroup per CU; every weight byte is streamed once per T positions, so T is as long as the
+// tile's rows fit the LDS.  Measured against the two conv_gemm launches (B = 32, ms per unit): C = 256: k = 3 (T = 192) 0.52 vs
+// 0.69, k = 7 (T = 224) 0.96 vs 1.17, k = 11 (T = 224) 1.42 vs 1.67 (T = 128: 0.53 / 1.01 / 1.52); C = 512: k = 3 (T = 96) 0.45 vs
+// 0.57, k = 7 (T = 96) 0.93 vs 1.05, k = 11 (T = 96; 80 at dilation 5) 1.42 (1.58) vs 1.57 -- at T = 64 k = 7 / 11 lost (1.08 / 1.66)
+struct ResUnitGeom { int T, WP, NT; };
+static ResUnitGeom resunit_geom(int channels, int k, int dil) {
+  if (channels == 512) return {resunit_tile512(k, dil), 1, 512};
+  if (channels == 256) return {k <= 3 ? 192 : 224, 1, 512};
+  if (channels == 128) return {128, 1, 256};
+  if (channels == 64) return {256, 2, 256};
+  return {512, 4, 256};
+}
+
 extern "C" int ctta_resunit_supported(int channels, int k, int dil) {
   if (!ctta_opt(CTTA_OPT_FUSED_RES)) return 0;
   if (k < 1 || k > 11 || (k & 1) == 0 || dil < 1) return 0;
-  // C = 256 / 512: eight waves, one workgroup per CU; every weight byte is streamed once per T positions, so T is as long as the
-  // tile's rows fit the LDS.  Measured against the two conv_gemm launches (B = 32, ms per unit): C = 256: k = 3 (T = 192) 0.52 vs
-  // 0.69, k = 7 (T = 224) 0.96 vs 1.17, k = 11 (T = 224) 1.42 vs 1.67 (T = 128: 0.53 / 1.01 / 1.52); C = 512: k = 3 (T = 96) 0.45 vs
-  // 0.57, k = 7 (T = 96) 0.93 vs 1.05, k = 11 (T = 96; 80 at dilation 5) 1.42 (1.58) vs 1.57 -- at T = 64 k = 7 / 11 lost (1.08 / 1.66)
-  if (channels == 256) return resunit_smem(256, 1, k <= 3 ? 192 : 224, k, dil) <= (size_t)160 * 1024 ? 1 : 0;
-  if (channels == 512) return resunit_tile512(k, dil) > 0 ? 1 : 0;
-  if (channels != 32 && channels != 64 && channels != 128) return 0;
-  const int T = channels == 128 ? 128 : channels == 64 ? 256 : 512;
-  const int WP = channels == 128 ? 1 : channels == 64 ? 2 : 4;
-  return resunit_smem(channels, WP, T, k, dil) <= (size_t)64 * 1024 ? 1 : 0;
+  if (channels != 32 && channels != 64 && channels != 128 && channels != 256 && channels != 512) return 0;
+  const ResUnitGeom g = resunit_geom(channels, k, dil);
+  if (g.T == 0) return 0;
+  const size_t lds = channels >= 256 ? (size_t)160 * 1024 : (size_t)64 * 1024;      // one workgroup per CU / three
+  return resunit_smem(channels, g.WP, g.T, k, dil) <= lds ? 1 : 0;
+}
+
+// The longest sequence resunit_kernel addresses with its 32-bit byte offsets.  The staging loop of the last tile (first position
+// l0) reads rows l0 - H1 - H2 + [0, (rows_in / BR + 1) * BR): rows_in = T + 16 * WP + 2 * H1 staged rows in batches of
+// BR = SU * RPS = 4 * NT / (C / 8) rows, the last batch loaded whole (only its LDS stores are guarded).  The epilogue's rows end
+// at l0 + T, before that.  Every offset it forms (voff + the row advance, signed int) and the descriptor's record count
+// (len * C * 2, unsigned) stay below 2^31 when those rows times C * 2 bytes are at most 2^31; the negative offsets of the left
+// halo then also land beyond the record count, which is what zero-fills them.
+static long long resunit_max_len(int channels, int k, int dil) {
+  const ResUnitGeom g = resunit_geom(channels, k, dil);
+  const int H1 = dil * (k - 1) / 2, H2 = (k - 1) / 2;
+  const int BR = 4 * g.NT / (channels / 8), rows_in = g.T + 16 * g.WP + 2 * H1;
+  const long long past_l0 = (long long)(rows_in / BR + 1) * BR - H1 - H2;         // rows addressed from l0 on
+  const long long rows = (1LL << 31) / (2 * channels);
+  return (rows - past_l0) / g.T * g.T + g.T;                                     // the last l0 with l0 + past_l0 <= rows, + T
 }
 
 extern "C" ctta_status ctta_resunit_conv1d(const void* x, int batch, int len, int channels, int k, int dil,
@@ -705,9 +729,13 @@ extern "C" ctta_status ctta_resunit_conv1d(const void* x, int batch, int len, in
   CTTA_REQUIRE(batch >= 1 && len >= 1 && (long long)batch * len < (1LL << 31), "resunit_conv1d: bad extent");
   CTTA_REQUIRE(out_slope >= 0.f && out_slope <= 1.f, "resunit_conv1d: out_slope=%g must lie in [0, 1]", (double)out_slope);
   CTTA_REQUIRE(slope >= 0.f && slope <= 1.f, "resunit_conv1d: slope=%g must lie in [0, 1]", (double)slope);
+  CTTA_REQUIRE(x != out, "resunit_conv1d: the output may not alias the input (neighbouring tiles read its halo)");
   CTTA_REQUIRE(ctta_resunit_supported(channels, k, dil),
                "resunit_conv1d: channels=%d k=%d dilation=%d is outside the fused kernel's range (C in {32,64,128,256}, odd k <= 11, "
                "tile <= 64 KB of LDS (C <= 128); C = 512: k in {3, 7, 11})", channels, k, dil);
+  CTTA_REQUIRE(len <= resunit_max_len(channels, k, dil),
+               "resunit_conv1d: len=%d is beyond the 32-bit per-sample offsets of the kernel (at most %lld positions for channels=%d "
+               "k=%d dilation=%d)", len, resunit_max_len(channels, k, dil), channels, k, dil);
   ResUnitParams p;
   memset(&p, 0, sizeof(p));
   p.x = (const bf16_t*)x; p.w1f = (const bf16_t*)w1_frag; p.w2f = (const bf16_t*)w2_frag; p.b1 = b1;
@@ -726,7 +754,7 @@ extern "C" ctta_status ctta_resunit_conv1d(const void* x, int batch, int len, in
   if (channels == 512) {
     const int t512 = resunit_tile512(k, dil);
     st = k == 3 ? (t512 == 96 ? launch_resunit_k<512, 8, 1, 96, 3>(p, batch, s) : launch_resunit_k<512, 8, 1, 64, 3>(p, batch, s))
-       : k == 7 ? launch_resunit_k<512, 8, 1, 96, 7>(p, batch, s)
+       : k == 7 ? (t512 == 96 ? launch_resunit_k<512, 8, 1, 96, 7>(p, batch, s) : launch_resunit_k<512, 8, 1, 80, 7>(p, batch, s))
        : t512 == 96 ? launch_resunit_k<512, 8, 1, 96, 11>(p, batch, s) : launch_resunit_k<512, 8, 1, 80, 11>(p, batch, s);
   }
   else if (channels == 256) st = k <= 3 ? launch_resunit<256, 8, 1, 192>(p, batch, s) : launch_resunit<256, 8, 1, 224>(p, batch, s);
@@ -750,6 +778,12 @@ static int reschain_halo(int k, const int* dils) {
 static size_t reschain_smem(int channels, int k, const int* dils) {
   const int T = reschain_tile(channels);
   return (size_t)(T + 2 * reschain_halo(k, dils) + 32) * (channels + 8) * 2 * 2;
+}
+// The longest sequence reschain_kernel addresses with its 32-bit byte offsets: it stages through 64-bit pointers, and its
+// epilogue (voff + the row advance, signed int; record count len * C * 2, unsigned) reaches row l0 + T of the last tile.
+static long long reschain_max_len(int channels) {
+  const int T = reschain_tile(channels);
+  return (1LL << 31) / (2 * channels) / T * T;
 }
 
 extern "C" int ctta_reschain_supported(int channels, int k, const int* dils) {
@@ -789,6 +823,9 @@ extern "C" ctta_status ctta_reschain_conv1d(const void* x, int batch, int len, i
   CTTA_REQUIRE(ctta_reschain_supported(channels, k, dils),
                "reschain_conv1d: channels=%d k=%d dilations=(%d,%d,%d) is outside the chained kernel's range (C in {32,64}, "
                "k in {3,5,7}, tile <= 72 KB of LDS)", channels, k, dils[0], dils[1], dils[2]);
+  CTTA_REQUIRE(len <= reschain_max_len(channels),
+               "reschain_conv1d: len=%d is beyond the 32-bit per-sample offsets of the kernel (at most %lld positions for "
+               "channels=%d)", len, reschain_max_len(channels), channels);
   ResChainParams p;
   memset(&p, 0, sizeof(p));
   p.x = (const bf16_t*)x;

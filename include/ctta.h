@@ -430,7 +430,10 @@ const char* ctta_conv_gemm_variant_name(int id);
  * conv1: k taps, dilation `dil`; conv2: k taps, dilation 1; "same" zero padding; x / out bf16 [batch][len][channels].
  * The intermediate never leaves LDS.  Weights are FRAGMENT-MAJOR copies ([n/16][k*channels/32][64][8] bf16) of the
  * packed [n][k_pad] operands, made by ctta_frag_pack (k_valid = k * channels).  out_slope > 0 applies a final
- * leaky_relu.  ctta_resunit_supported reports whether a (channels, k, dil) combination fits the kernel. */
+ * leaky_relu.  ctta_resunit_supported reports whether a (channels, k, dil) combination fits the kernel.  out must not alias x.
+ * One sample is addressed with signed 32-bit byte offsets: len is refused once the rows that the last tile stages (its
+ * positions, the conv1 / conv2 halo and the rest of its last load batch) would reach 2^31 bytes into the sample, i.e. a
+ * little under 2^30 / channels positions (C = 512, k = 3, dil = 1: at most 2 097 120; the exact rule is resunit_max_len in resunit.hip). */
 int ctta_resunit_supported(int channels, int k, int dil);
 ctta_status ctta_frag_pack(const void* packed, int n, int k_pad, int k_valid, void* dst, void* stream);
 ctta_status ctta_resunit_conv1d(const void* x, int batch, int len, int channels, int k, int dil,
@@ -439,7 +442,9 @@ ctta_status ctta_resunit_conv1d(const void* x, int batch, int len, int channels,
 /* The three units of one ResBlock chained in ONE launch (C = 32 / 64, k in {3, 5, 7}): x_{u+1} = x_u + unit_u(x_u) with the
  * residual stream kept in LDS between units (rounded to bf16 after every unit, as ctta_resunit_conv1d stores it), the last
  * unit finished by the same epilogue as ctta_resunit_conv1d.  Bit-identical to three ctta_resunit_conv1d calls.
- * dils / w1_frag / b1 / w2_frag / b2: HOST arrays of three entries (device pointers inside).  out must not alias x. */
+ * dils / w1_frag / b1 / w2_frag / b2: HOST arrays of three entries (device pointers inside).  out must not alias x.
+ * len is refused once ceil(len / T) * T * channels * 2 bytes (T = 256 / 128 positions per workgroup at 32 / 64 channels)
+ * would pass 2^31: at most 2^25 / 2^24 positions. */
 int ctta_reschain_supported(int channels, int k, const int* dils);
 ctta_status ctta_reschain_conv1d(const void* x, int batch, int len, int channels, int k, const int* dils,
                                  const void* const* w1_frag, const float* const* b1, const void* const* w2_frag,
