@@ -117,6 +117,64 @@ __global__ void lincomb2_kernel(const float4* __restrict__ x, const float4* __re
     out[i] = o;
   }
 }
+
+// One DDIM step (eta = 0) in one pass, scheduling_ddim.py:243-370 in the reference's batched-timestep form, with the CFG
+// combine of audio_distilled_model.py:313-319 folded in when the model output holds 2B rows [uncond | cond]:
+//   v    = CFG ? (1 - w) * u + w * c : model_output
+//   x0   = V ? sa * x - sb * v : (1 / sa) * x + (-sb / sa) * v        (clamped to +-clamp when clamp > 0)
+//   eps  = V ? sa * v + sb * x : v
+//   prev = sap * x0 + sbp * eps
+// Every element sees the fp32 operations of cfg_combine_kernel followed by three lincomb2_kernel launches, in their order
+// (this translation unit is built without fp contraction), so the result is bit-identical to that four-launch chain.
+template <bool CFG, bool V>
+__global__ void ddim_step_kernel(const float4* __restrict__ mo, const float* __restrict__ w, const float4* __restrict__ x,
+                                 const float* __restrict__ sa_, const float* __restrict__ sb_, const float* __restrict__ sap_,
+                                 const float* __restrict__ sbp_, float clamp, float4* __restrict__ prev,
+                                 float4* __restrict__ x0_out, long long nvec_per, long long total) {
+  VEC_LOOP(total) {
+    const int s = (int)(i / nvec_per);
+    const float sa = sa_[s], sb = sb_[s], sap = sap_[s], sbp = sbp_[s];
+    float4 v = mo[i];
+    if (CFG) {
+      const float ww = w[s];
+      const float a = 1.0f - ww;
+      const float4 cc = mo[total + i];
+      v = make_float4(a * v.x + ww * cc.x, a * v.y + ww * cc.y, a * v.z + ww * cc.z, a * v.w + ww * cc.w);
+    }
+    const float4 xx = x[i];
+    // the coefficient pair of the x0 lincomb, as DDIMScheduler.step hands it to lincomb2_kernel
+    const float ca = V ? sa : 1.0f / sa;
+    const float cb = V ? -sb : -sb / sa;
+    float4 x0 = make_float4(ca * xx.x + cb * v.x, ca * xx.y + cb * v.y, ca * xx.z + cb * v.z, ca * xx.w + cb * v.w);
+    if (clamp > 0.f) {
+      x0.x = fminf(fmaxf(x0.x, -clamp), clamp); x0.y = fminf(fmaxf(x0.y, -clamp), clamp);
+      x0.z = fminf(fmaxf(x0.z, -clamp), clamp); x0.w = fminf(fmaxf(x0.w, -clamp), clamp);
+    }
+    float4 e = v;
+    if (V) e = make_float4(sa * v.x + sb * xx.x, sa * v.y + sb * xx.y, sa * v.z + sb * xx.z, sa * v.w + sb * xx.w);
+    prev[i] = make_float4(sap * x0.x + sbp * e.x, sap * x0.y + sbp * e.y, sap * x0.z + sbp * e.z, sap * x0.w + sbp * e.w);
+    if (x0_out) x0_out[i] = x0;
+  }
+}
+
+// Noising of the distillation step with its last-step select (audio_consistency_model.py:312-319):
+//   out = last[b] != 0 ? noise * init_sigma : sa[b] * x0 + sb[b] * noise        (last NULL: no row is the last step)
+__global__ void ddim_noising_kernel(const float4* __restrict__ x0, const float4* __restrict__ nz, const float* __restrict__ sa_,
+                                    const float* __restrict__ sb_, const float* __restrict__ last, float init_sigma,
+                                    float4* __restrict__ out, long long nvec_per, long long total) {
+  VEC_LOOP(total) {
+    const int s = (int)(i / nvec_per);
+    const float4 n = nz[i];
+    if (last && last[s] != 0.f) {
+      out[i] = make_float4(n.x * init_sigma, n.y * init_sigma, n.z * init_sigma, n.w * init_sigma);
+    } else {
+      const float sa = sa_[s], sb = sb_[s];
+      const float4 a = x0[i];
+      out[i] = make_float4(sa * a.x + sb * n.x, sa * a.y + sb * n.y, sa * a.z + sb * n.z, sa * a.w + sb * n.w);
+    }
+  }
+}
+
 // loss = mean_b(w[b] * inst[b])  (w NULL = 1)
 __global__ void weighted_mean_kernel(const float* __restrict__ inst, const float* __restrict__ w, int B,
                                      float* __restrict__ loss) {
@@ -426,6 +484,42 @@ extern "C" ctta_status ctta_lincomb2_rows(const float* x, const float* y, const 
   const long long nv = n_per_sample / 4, total = nv * batch;
   hipLaunchKernelGGL(lincomb2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float4*)x,
                      (const float4*)y, a, b, (float4*)out, nv, total, clamp);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_ddim_step(const float* model_output, const float* cfg_w, const float* sample, const float* sqrt_a_t,
+                                      const float* sqrt_1m_a_t, const float* sqrt_a_prev, const float* sqrt_1m_a_prev,
+                                      int prediction_type, float clamp, float* prev_sample, float* pred_original_sample,
+                                      int batch, int64_t n_per_sample, void* stream) {
+  CTTA_REQUIRE(model_output && sample && sqrt_a_t && sqrt_1m_a_t && sqrt_a_prev && sqrt_1m_a_prev && prev_sample,
+               "ddim_step: null pointer");
+  CTTA_REQUIRE(prediction_type == CTTA_DDIM_V_PREDICTION || prediction_type == CTTA_DDIM_EPSILON,
+               "ddim_step: prediction_type=%d (0 = v_prediction, 1 = epsilon)", prediction_type);
+  CTTA_REQUIRE(batch >= 1 && n_per_sample >= 4, "ddim_step: empty batch");
+  REQ_VEC(n_per_sample);
+  const long long nv = n_per_sample / 4, total = nv * batch;
+  const bool v = prediction_type == CTTA_DDIM_V_PREDICTION;
+#define DDIM_LAUNCH(CFG, V)                                                                                                  \
+  hipLaunchKernelGGL((ddim_step_kernel<CFG, V>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,                   \
+                     (const float4*)model_output, cfg_w, (const float4*)sample, sqrt_a_t, sqrt_1m_a_t, sqrt_a_prev,          \
+                     sqrt_1m_a_prev, clamp, (float4*)prev_sample, (float4*)pred_original_sample, nv, total)
+  if (cfg_w) { if (v) DDIM_LAUNCH(true, true); else DDIM_LAUNCH(true, false); }
+  else       { if (v) DDIM_LAUNCH(false, true); else DDIM_LAUNCH(false, false); }
+#undef DDIM_LAUNCH
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_ddim_noising(const float* x0, const float* noise, const float* sqrt_a, const float* sqrt_1m_a,
+                                         const float* last, float init_sigma, float* out, int batch, int64_t n_per_sample,
+                                         void* stream) {
+  CTTA_REQUIRE(x0 && noise && sqrt_a && sqrt_1m_a && out, "ddim_noising: null pointer");
+  CTTA_REQUIRE(batch >= 1 && n_per_sample >= 4, "ddim_noising: empty batch");
+  REQ_VEC(n_per_sample);
+  const long long nv = n_per_sample / 4, total = nv * batch;
+  hipLaunchKernelGGL(ddim_noising_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float4*)x0,
+                     (const float4*)noise, sqrt_a, sqrt_1m_a, last, init_sigma, (float4*)out, nv, total);
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }

@@ -8,7 +8,8 @@ fused CFG / loss / EMA kernels).  The FLAN-T5 text encoder stays a PyTorch modul
 reference (it is frozen and outside the hot path); because neither box has
 network access it can be injected (`text_encoder=`, `tokenizer=`) instead of downloaded.
 
-Scope: `inference` (student, multi-step, teacher Heun loop), `_query_teacher`, `update_ema`,
+Scope: `inference` (student, multi-step, teacher Heun / DDIM loop), `_query_teacher`, `update_ema`, both solver
+modes of stage 2 (`use_edm=False`: DDIM, the reference's default; `use_edm=True`: Heun, optionally on Karras sigmas),
 `forward` (distillation loss; in training mode the returned loss carries a grad_fn whose backward
 runs the HIP engine's own backward pass and fills `student_unet` `.grad`s, so the reference loop
 `loss = model(...); loss.backward(); optimizer.step()` works unchanged on one GPU), and
@@ -27,7 +28,7 @@ from torch import nn
 from . import _native as N
 from . import dist_util
 from .modules import AutoencoderKL, UNet2DConditionGuidedModel, UNet2DConditionModel
-from .scheduler import DDPMScheduler, HeunDiscreteScheduler
+from .scheduler import DDIMScheduler, DDPMScheduler, HeunDiscreteScheduler
 
 
 def randn_tensor(shape, generator=None, device=None, dtype=None):
@@ -227,7 +228,9 @@ class AudioDistilledModel(nn.Module):
                 assert p.requires_grad is False, f"The {name} is not frozen."
 
     # audio_distilled_model.py:286-322
-    def _query_teacher(self, z_scaled, t, prompt_embeds, prompt_mask, guidance_scale=None, reuse_text=None):
+    def _query_teacher(self, z_scaled, t, prompt_embeds, prompt_mask, guidance_scale=None, reuse_text=None, raw=False):
+        """`raw=True` returns (the U-Net's output, the per-sample CFG scales or None) WITHOUT the combine: the DDIM path
+        folds it into its one-pass solver step (ctta_ddim_step)."""
         if not torch.is_tensor(t):
             t = torch.tensor(t)
         if len(t.reshape(-1)) != 1 and self.use_teacher_cf_guidance:
@@ -246,13 +249,15 @@ class AudioDistilledModel(nn.Module):
             else:
                 w = torch.full((B,), float(self.teacher_guidance_scale), dtype=torch.float32, device=pred.device)
             w = w.contiguous()
+            if raw:
+                return pred, w
             out = torch.empty_like(pred[:B])
             N.check(N.lib().ctta_cfg_combine(N.ptr(pred[:B]), N.ptr(pred[B:]), N.ptr(w), N.ptr(out), B,
                                              out[0].numel(), N.stream_ptr()))
             pred = out
         # the reference asserts `not noise_pred.isnan().any()` here (a device->host sync per query);
         # enable with CTTA_NAN_CHECKS=1
-        return pred
+        return (pred, None) if raw else pred
 
 
 class AudioLCM(AudioDistilledModel):
@@ -264,17 +269,19 @@ class AudioLCM(AudioDistilledModel):
                          unet_model_name=unet_model_name, unet_model_config_path=unet_model_config_path,
                          snr_gamma=snr_gamma, freeze_text_encoder=freeze_text_encoder, use_lora=use_lora,
                          ema_decay=ema_decay, teacher_guidance_scale=teacher_guidance_scale, **kwargs)
-        assert use_edm, "only the Heun/EDM path (use_edm, train.sh:33) is built; DDIM is §8f rank 3"
-        assert not use_karras, "Karras sigmas are unused by the shipped scripts and not built"
         assert loss_type in ("mse", "mel", "stft", "clap"), "unknown loss_type %r" % (loss_type,)
         self.uncondition = uncondition
-        self.use_edm = use_edm
+        self.use_edm = use_edm            # False (the reference's default): DDIM, one teacher query per step; True: Heun
+        self.use_karras = use_karras      # Karras sigmas for the Heun tables; no effect with DDIM (:77-82)
         self.target_ema_decay = target_ema_decay
         self.num_diffusion_steps = num_diffusion_steps
         self.lightweight = "light" in (unet_model_config_path or "light")
         self.student_target_unet = deepcopy(self.student_unet)
         self.student_target_unet.eval().requires_grad_(False)
-        self.noise_scheduler = HeunDiscreteScheduler.from_pretrained(self.scheduler_name, subfolder="scheduler")
+        sched_class = HeunDiscreteScheduler if self.use_edm else DDIMScheduler      # audio_consistency_model.py:72-84
+        self.noise_scheduler = sched_class.from_pretrained(self.scheduler_name, subfolder="scheduler")
+        if self.use_karras and self.use_edm:
+            self.noise_scheduler.use_karras_sigmas = True
         self.noise_scheduler.set_timesteps(self.num_diffusion_steps)
         self.vae = vae
         self.loss_type = loss_type
@@ -318,7 +325,17 @@ class AudioLCM(AudioDistilledModel):
         return self.train(False)
 
     def compute_snr(self, timesteps, t_indices):
-        return self.noise_scheduler.sigmas[t_indices] ** (-2)
+        """:215-219: sigma^-2 of the Heun tables; with DDIM alphas_cumprod[t] / (1 - alphas_cumprod[t])
+        (audio_distilled_model.py:165-192)."""
+        if self.use_edm:
+            return self.noise_scheduler.sigmas[t_indices] ** (-2)
+        ac = self.noise_scheduler.alphas_cumprod
+        t = torch.as_tensor(timesteps).to("cpu", torch.int64)
+        return ((ac ** 0.5)[t].float() / ((1.0 - ac) ** 0.5)[t].float()) ** 2
+
+    def _snr_sigma(self, t):
+        """DDIM: the loss kernels weigh by min(sigma^-2, snr_gamma); the sigma whose -2nd power is compute_snr(t)."""
+        return (1.0 / self.compute_snr(t, None).to(torch.float64)).sqrt().to(torch.float32)
 
     def update_ema(self):
         assert self.training, "EMA update should only be called during training"
@@ -503,8 +520,9 @@ class AudioLCM(AudioDistilledModel):
         dev = z_0.device
         B = z_0.shape[0]
         embeds_cf, mask_cf, embeds, mask = self.get_prompt_embeds(prompt, self.use_teacher_cf_guidance, 1)
-        avail = sch._timesteps_host
-        order = 2
+        heun = self.use_edm       # else DDIM: first order, int64 timesteps, ONE teacher query (:273,343)
+        avail = sch._timesteps_host if heun else sch.timesteps.numpy()
+        order = 2 if heun else 1
         if validation_mode != 0:
             ti = len(avail) - 1 - int(validation_mode * order)
             assert ti >= 0
@@ -516,12 +534,16 @@ class AudioLCM(AudioDistilledModel):
         t_np1 = torch.from_numpy(avail[inds.numpy()])
         t_n = torch.from_numpy(avail[(inds + order).numpy()])
         noise = gaussian_noise if gaussian_noise is not None else torch.randn_like(z_0)
-        z_noisy = sch.add_noise(z_0, noise, t_np1)
-        z_gauss = noise * sch.init_noise_sigma.to(dev)
-        last_mask = (t_np1 == float(avail.max())).reshape(-1, 1, 1, 1).to(dev)
-        z_np1 = torch.where(last_mask, z_gauss, z_noisy)
-        z_np1_scaled = sch.scale_model_input(z_np1, t_np1)
-        assert sch.state_in_first_order
+        if heun:
+            z_noisy = sch.add_noise(z_0, noise, t_np1)
+            z_gauss = noise * sch.init_noise_sigma.to(dev)
+            last_mask = (t_np1 == float(avail.max())).reshape(-1, 1, 1, 1).to(dev)
+            z_np1 = torch.where(last_mask, z_gauss, z_noisy)
+            z_np1_scaled = sch.scale_model_input(z_np1, t_np1)
+            assert sch.state_in_first_order
+        else:       # noising + last-step select in one pass (ctta_ddim_noising); scale_model_input is the identity
+            last = (t_np1 == int(avail.max())).to(device=dev, dtype=torch.float32)
+            z_np1 = z_np1_scaled = sch.add_noise_last(z_0, noise, t_np1, last)
         if self.teacher_guidance_scale == -1:
             if guidance_scale is None:
                 guidance_scale = torch.rand(B) * self.max_rand_guidance_scale
@@ -545,17 +567,21 @@ class AudioLCM(AudioDistilledModel):
             with torch.cuda.stream(side):
                 side_pred = self.student_unet.forward_train(z_np1_scaled, t_np1, w_stu, embeds, mask)
             side_pred.record_stream(cur)
-        v1 = self._query_teacher(z_np1_scaled, t_np1, embeds_cf, mask_cf, guidance_scale)
-        zhat_n = sch.step(v1, t_np1, z_np1).prev_sample
-        zhat_n_scaled = sch.scale_model_input(zhat_n, t_n)
-        v2 = self._query_teacher(zhat_n_scaled, t_n, embeds_cf, mask_cf, guidance_scale)
-        zhat_n = sch.step(v2, t_n, zhat_n).prev_sample
-        zhat_n_scaled = sch.scale_model_input(zhat_n, t_n)
-        assert sch.state_in_first_order
+        if heun:
+            v1 = self._query_teacher(z_np1_scaled, t_np1, embeds_cf, mask_cf, guidance_scale)
+            zhat_n = sch.step(v1, t_np1, z_np1).prev_sample
+            zhat_n_scaled = sch.scale_model_input(zhat_n, t_n)
+            v2 = self._query_teacher(zhat_n_scaled, t_n, embeds_cf, mask_cf, guidance_scale)
+            zhat_n = sch.step(v2, t_n, zhat_n).prev_sample
+            zhat_n_scaled = sch.scale_model_input(zhat_n, t_n)
+            assert sch.state_in_first_order
+        else:       # CFG combine + DDIM step in one pass (ctta_ddim_step)
+            raw, w_cfg = self._query_teacher(z_np1_scaled, t_np1, embeds_cf, mask_cf, guidance_scale, raw=True)
+            zhat_n = zhat_n_scaled = sch.step_fused(raw, t_np1, z_np1, cfg_w=w_cfg)
         w = guidance_scale if guidance_scale is not None else float(self.teacher_guidance_scale)
         target = self.student_target_unet(zhat_n_scaled, t_n, guidance=w, encoder_hidden_states=embeds,
                                           encoder_attention_mask=mask).sample
-        sig = torch.from_numpy(sch._sigmas_host[inds.numpy()]).to(dev)
+        sig = torch.from_numpy(sch._sigmas_host[inds.numpy()]).to(dev) if heun else self._snr_sigma(t_np1).to(dev)
 
         def mse(a, b, sigma=None, gamma=0.0):
             if self.loss is not None and sigma is not None:   # the consistency loss proper (get_loss); plain MSEs stay MSE
@@ -570,13 +596,18 @@ class AudioLCM(AudioDistilledModel):
         if validation_mode != 0:   # :354-405
             from_np1 = self.student_target_unet(z_np1_scaled, t_np1, guidance=w, encoder_hidden_states=embeds,
                                                 encoder_attention_mask=mask).sample
-            if run_teacher:        # the teacher continues from t_n down to 0 with the full Heun schedule
+            if run_teacher and heun:   # the teacher continues from t_n down to 0 with the full Heun schedule
                 for j in range(int(inds[0]) + order, len(avail)):
                     t = float(avail[j])
                     z_in = sch.scale_model_input(zhat_n, t)
                     pred = self._query_teacher(z_in, t, embeds_cf, mask_cf, guidance_scale)
                     zhat_n = sch.step(pred, t, zhat_n).prev_sample
                 sch.prev_derivative = sch.dt = sch.sample = None
+            elif run_teacher:          # ... or with plain DDIM steps: no solver state to reset
+                for j in range(int(inds[0]) + order, len(avail)):
+                    t = int(avail[j])
+                    raw, w_cfg = self._query_teacher(zhat_n, t, embeds_cf, mask_cf, guidance_scale, raw=True)
+                    zhat_n = sch.step_fused(raw, t, zhat_n, cfg_w=w_cfg)
             loss_w_gt = mse(from_np1, z_0)
             loss_w_teacher = mse(from_np1, zhat_n)
             loss_consis = mse(from_np1, target, sig, self.snr_gamma or 0.0)
@@ -605,10 +636,16 @@ class AudioLCM(AudioDistilledModel):
     def inference(self, prompt, inference_scheduler, guidance_scale_input=3, guidance_scale_post=1, num_steps=20,
                   use_edm=False, num_samples=1, use_ema=True, query_teacher=False, num_teacher_steps=18,
                   return_all=False, noise=None, graph_teacher=False):
-        """`graph_teacher=True` runs the Heun teacher loop as replays of ONE captured hipGraph (a full 2nd-order
-        step = 2 CFG teacher queries); results are identical to the eager loop."""
+        """`graph_teacher=True` runs the teacher loop as replays of ONE captured hipGraph (Heun: a full 2nd-order
+        step = 2 CFG teacher queries; DDIM: one query + step); results are identical to the eager loop.
+        `inference_scheduler` is a HeunDiscreteScheduler or a DDIMScheduler, chosen by the CALLER (inference.py:160,
+        demo.py:94) whatever `self.use_edm` is; the re-noising stride still follows `self.use_edm` (:497-499)."""
         self.check_eval_mode()
         sch = inference_scheduler
+        heun = hasattr(sch, "_timesteps_host")
+
+        def host_timesteps():      # Python numbers: float64 for Heun, int for DDIM (no device -> host sync)
+            return [float(t) for t in sch._timesteps_host] if heun else [int(t) for t in sch.timesteps]
         use_cf = guidance_scale_post > 1.
         t0 = time()
         embeds_cf, mask_cf, embeds, mask = self.get_prompt_embeds(prompt, True, num_samples)
@@ -635,25 +672,33 @@ class AudioLCM(AudioDistilledModel):
         t1 = time()
         sch.set_timesteps(18, device=dev)
         z_N = noise * sch.init_noise_sigma
-        zhat_0 = calc_zhat_0(z_N, float(sch._timesteps_host[0]))
+        zhat_0 = calc_zhat_0(z_N, host_timesteps()[0])
         sch.set_timesteps(num_steps, device=dev)
-        for t in sch._timesteps_host[1::2]:
-            zhat_n = sch.add_noise(zhat_0, torch.randn_like(zhat_0), float(t))
-            zhat_0 = calc_zhat_0(zhat_n, float(t))
+        order = 2 if self.use_edm else 1
+        for t in host_timesteps()[1::order]:
+            zhat_n = sch.add_noise(zhat_0, torch.randn_like(zhat_0), t)
+            zhat_0 = calc_zhat_0(zhat_n, t)
         time_stu = time() - t1
         zhat_tea, time_tea = None, None
         if query_teacher:
             t2 = time()
             sch.set_timesteps(num_teacher_steps, device=dev)
             zhat_tea = noise * sch.init_noise_sigma
-            if graph_teacher:
+            if graph_teacher and heun:
                 zhat_tea = self._teacher_loop_graphed(sch, zhat_tea, enc_tea, mask_tea, guidance_scale_input)
-            else:
-                for t in sch._timesteps_host:
-                    z_in = sch.scale_model_input(zhat_tea, float(t))
-                    pred = self._query_teacher(z_in, float(t), enc_tea, mask_tea, guidance_scale_input)
-                    zhat_tea = sch.step(pred, float(t), zhat_tea).prev_sample
-            sch.prev_derivative = sch.dt = sch.sample = None
+            elif graph_teacher:
+                zhat_tea = self._teacher_loop_graphed_ddim(sch, zhat_tea, enc_tea, mask_tea, guidance_scale_input)
+            elif heun:
+                for t in host_timesteps():
+                    z_in = sch.scale_model_input(zhat_tea, t)
+                    pred = self._query_teacher(z_in, t, enc_tea, mask_tea, guidance_scale_input)
+                    zhat_tea = sch.step(pred, t, zhat_tea).prev_sample
+            else:       # DDIM: CFG combine + step in one pass (ctta_ddim_step)
+                for t in host_timesteps():
+                    raw, w_cfg = self._query_teacher(zhat_tea, t, enc_tea, mask_tea, guidance_scale_input, raw=True)
+                    zhat_tea = sch.step_fused(raw, t, zhat_tea, cfg_w=w_cfg)
+            if heun:    # reset the solver
+                sch.prev_derivative = sch.dt = sch.sample = None
             time_tea = time() - t2 + time_embed
         if return_all:
             return zhat_0, zhat_tea, time_stu + time_embed, time_tea
@@ -924,6 +969,59 @@ def _teacher_loop_graphed(self, sch, z, enc, mask, guidance_scale):
 AudioLCM._teacher_loop_graphed = _teacher_loop_graphed
 
 
+def _teacher_loop_graphed_ddim(self, sch, z, enc, mask, guidance_scale):
+    """The DDIM teacher loop of `inference` with its launch sequence captured once: timesteps and the four step
+    coefficients live in device tables indexed by a device-side counter, so one graph = one step (teacher query, CFG
+    combine + DDIM step in one pass) and the loop is N replays.  Same kernels and arguments as the eager loop."""
+    dev = z.device
+    B = z.shape[0]
+    ts = [int(t) for t in sch.timesteps]
+    nt = len(ts)
+    ts_dev = torch.tensor(ts, dtype=torch.float32, device=dev)
+    coef_dev = sch.step_coeffs(torch.tensor(ts), nt).to(dev)          # (4, nt)
+    cfg = self.use_teacher_cf_guidance
+    w = None
+    if cfg:
+        w_val = guidance_scale if self.teacher_guidance_scale == -1 else self.teacher_guidance_scale
+        w = torch.full((B,), float(w_val), dtype=torch.float32, device=dev)
+    x = z.clone().contiguous()
+    xnew = torch.empty_like(x)
+    idx = torch.zeros(1, dtype=torch.int64, device=dev)
+    first = [True]
+
+    def one():
+        t_b = ts_dev.index_select(0, idx).expand(B).contiguous()
+        c = coef_dev.index_select(1, idx).expand(4, B).contiguous()
+        # the text states are the same tensors for the whole loop: only the very first query projects their K / V
+        out = self.teacher_unet(torch.cat([x] * 2) if cfg else x, torch.cat([t_b] * 2) if cfg else t_b, enc,
+                                encoder_attention_mask=mask, reuse_text=not first[0]).sample
+        first[0] = False
+        sch.step_fused(out, None, x, cfg_w=w, coeffs=c, out=xnew)
+        x.copy_(xnew)
+        idx.add_(1)
+
+    # one eager step on a side stream first (handles, kernel attributes, allocator pool), then rewind and capture
+    x0 = x.clone()
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        one()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    x.copy_(x0)
+    idx.zero_()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        one()
+    x.copy_(x0)
+    idx.zero_()
+    for _ in range(nt):
+        graph.replay()
+    return x.clone()
+
+
+AudioLCM._teacher_loop_graphed_ddim = _teacher_loop_graphed_ddim
+
+
 class _DistillStepGraph:
     """The distillation micro-step of `AudioLCM.train_step` (tools/train_utils.py:150-183) with its launch sequence
     captured ONCE into a hipGraph: noising, the two CFG teacher queries + Heun, the target network, the student's training
@@ -934,7 +1032,9 @@ class _DistillStepGraph:
     What makes the sequence replayable: every per-step quantity lives in a STATIC device tensor that the host refreshes
     before the replay -- the latents, the noise, the guidance scales, the two timestep vectors and the eight per-sample
     sigma vectors the Heun scheduler's methods look up (computed by the scheduler's own host logic, `_sigma_plan`, in the
-    order `_forward_impl` calls them) -- and the networks whose weights change every step (student after AdamW, target after
+    order `_forward_impl` calls them; Karras sigmas only change the host tables it reads.  With use_edm=False the teacher
+    phase is ONE query and the same slots carry the DDIM step's per-row vectors instead: four coefficients, the last-step
+    flags and the loss weight's sigma, `_ddim_plan`) -- and the networks whose weights change every step (student after AdamW, target after
     the EMA) have their bf16 re-pack captured at the head of their forward.
     Results are bit-identical to the eager `train_step` (same kernels, same arguments; asserted by
     tests/test_train_gpu.py and by bench.py before it times the replays).
@@ -1050,6 +1150,18 @@ class _DistillStepGraph:
         plan = [sig[i1], sig[i1 + 1], sig[i2], sig[i2 - 1], sig[i2], sig[i3], sig[inds]]
         return t_np1, t_n, plan
 
+    def _ddim_plan(self, inds):
+        """use_edm=False: the per-row vectors of the DDIM step in the slots of the sigma plan -- the four step coefficients
+        (the first two are also those of the noising), the last-step flags, an unused row, and the sigma whose -2nd
+        power is the row's SNR (the loss weight)."""
+        m = self.m
+        sch = m.noise_scheduler
+        avail = sch.timesteps.numpy()
+        t_np1, t_n = avail[inds], avail[inds + 1]
+        c = sch.step_coeffs(torch.from_numpy(t_np1), self.B).numpy()
+        last = (t_np1 == avail.max()).astype(np.float32)
+        return t_np1, t_n, [c[0], c[1], c[2], c[3], last, np.zeros(self.B, np.float32), m._snr_sigma(t_np1).numpy()]
+
     def _refresh(self, z_0, time_inds, gaussian_noise, guidance_scale, S=None, prompt=None, gt_wav=None):
         """Fills an input set (default: the one the teacher phase reads) on the CURRENT stream.  `prompt`: the batch's
         pre-computed text states (dict); None keeps the set's (a fixed prompt batch)."""
@@ -1090,8 +1202,8 @@ class _DistillStepGraph:
         """The host-side half: timesteps, sigma vectors and guidance scales, computed by the scheduler's own host logic and
         copied from the pinned staging buffer on the current stream."""
         m, B = self.m, self.B
-        avail = m.noise_scheduler._timesteps_host
-        order = 2
+        avail = m.noise_scheduler._timesteps_host if m.use_edm else m.noise_scheduler.timesteps.numpy()
+        order = 2 if m.use_edm else 1
         if time_inds is not None:
             inds = time_inds.to("cpu", torch.int64)
         else:
@@ -1102,7 +1214,7 @@ class _DistillStepGraph:
             guidance_scale = torch.full((B,), float(m.teacher_guidance_scale))
         elif guidance_scale is None:
             guidance_scale = torch.rand(B) * m.max_rand_guidance_scale
-        t_np1, t_n, plan = self._sigma_plan(inds.numpy())
+        t_np1, t_n, plan = self._sigma_plan(inds.numpy()) if m.use_edm else self._ddim_plan(inds.numpy())
         if self.pipelined:
             self._ev_h2d.synchronize()       # the previous batch's host -> device copies have left the pinned buffer
         host = self._pinned
@@ -1134,6 +1246,17 @@ class _DistillStepGraph:
         n = z0[0].numel()
         s_add, s_next1, s_scale2, s_prev2, s_cur2, s_scale3 = S["sig"][:6]
         embeds_cf, mask_cf = S["P"]["embeds_cf"], S["P"]["mask_cf"]
+        w_t = S["w"] if m.teacher_guidance_scale == -1 else None      # None: `_query_teacher` takes the model's fixed scale
+        if not m.use_edm:
+            # DDIM (:313-340 with one query): noising + last-step select, the CFG query, CFG combine + step; the student's
+            # input needs no scaling, and neither does the target network's
+            coeffs, last = S["small"][3:7], S["sig"][4]
+            sch.add_noise_last(z0, noise, None, last, coeffs=coeffs, out=S["z_in"])
+            if self._fork_student is not None:
+                self._fork_student()
+            raw, w_cfg = m._query_teacher(S["z_in"], S["t_np1"], embeds_cf, mask_cf, w_t, reuse_text=False, raw=True)
+            sch.step_fused(raw, None, S["z_in"], cfg_w=w_cfg, coeffs=coeffs, out=S["tgt_in"])
+            return
 
         def scale(x, sg, out=None):
             out = torch.empty_like(x) if out is None else out
@@ -1142,12 +1265,11 @@ class _DistillStepGraph:
         z_noisy = torch.empty_like(z0)
         N.check(L_.ctta_heun_add_noise(N.ptr(z0), N.ptr(noise), N.ptr(s_add), N.ptr(z_noisy), B, n, N.stream_ptr()))
         z_gauss = noise * float(sch.init_noise_sigma)
-        t_max = float(sch._timesteps_host.max())
+        t_max = float(np.float32(sch._timesteps_host.max()))      # S["t_np1"] holds float32 (Karras: 998.9999997 -> 999)
         z_np1 = torch.where((S["t_np1"] == t_max).reshape(-1, 1, 1, 1), z_gauss, z_noisy)
         z_np1_scaled = scale(z_np1, s_add, S["z_in"])
         if self._fork_student is not None:
             self._fork_student()      # unpipelined: the student's forward starts here, beside the teacher queries
-        w_t = S["w"] if m.teacher_guidance_scale == -1 else None      # None: `_query_teacher` takes the model's fixed scale
         v1 = m._query_teacher(z_np1_scaled, S["t_np1"], embeds_cf, mask_cf, w_t, reuse_text=False)
         zhat = torch.empty_like(z0)
         deriv = torch.empty_like(z0)

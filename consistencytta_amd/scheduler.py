@@ -69,8 +69,13 @@ class HeunDiscreteScheduler:
         timesteps = np.linspace(0, num_train_timesteps - 1, num_inference_steps, dtype=float)[::-1].copy()
         sigmas = np.array((((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).tolist(), dtype=np.float32)
         sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
+        # read here, not in __init__: the reference switches the flag on by assigning the attribute after construction
+        # (audio_consistency_model.py:80, inference.py:167)
         if self.use_karras_sigmas:
-            raise NotImplementedError("use_karras_sigmas is not built (unused by train.sh / inference.sh)")
+            log_sigmas = np.log(np.array((((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).tolist(),
+                                         dtype=np.float32))
+            sigmas = self._convert_to_karras(sigmas, num_inference_steps)
+            timesteps = np.array([self._sigma_to_t(s, log_sigmas) for s in sigmas], dtype=np.float64)
         sigmas = np.concatenate([sigmas, [0.0]]).astype(np.float32)
         sig = np.concatenate([sigmas[:1], np.repeat(sigmas[1:-1], 2), sigmas[-1:]])
         ts = np.concatenate([timesteps[:1], np.repeat(timesteps[1:], 2)])
@@ -84,6 +89,30 @@ class HeunDiscreteScheduler:
         self.prev_derivative = None
         self.dt = None
         self.sample = None
+
+    @staticmethod
+    def _convert_to_karras(in_sigmas, num_inference_steps):
+        """The noise schedule of Karras et al. (2022), rho = 7, between the ends of the interpolated uniform table
+        (:253-266)."""
+        sigma_min, sigma_max = float(in_sigmas[-1]), float(in_sigmas[0])
+        rho = 7.0
+        ramp = np.linspace(0, 1, num_inference_steps)
+        min_inv_rho = sigma_min ** (1 / rho)
+        max_inv_rho = sigma_max ** (1 / rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
+
+    @staticmethod
+    def _sigma_to_t(sigma, log_sigmas):
+        """Fractional training timestep of a sigma (:228-251): linear interpolation in log(sigma) against the float32
+        table of the 1000 training sigmas, arithmetic in float64."""
+        log_sigmas = np.asarray(log_sigmas, dtype=np.float64)
+        log_sigma = np.log(np.float64(sigma))
+        dists = log_sigma - log_sigmas
+        low_idx = int(min(np.cumsum(dists >= 0).argmax(), log_sigmas.shape[0] - 2))
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = np.clip((low - log_sigma) / (low - high), 0, 1)
+        return float((1 - w) * low_idx + w * high_idx)
 
     @property
     def state_in_first_order(self):
@@ -168,7 +197,9 @@ class HeunDiscreteScheduler:
 # ------------------------------------------------------------------------------------------------------------------
 # Stage-1 guided distillation: the reference's batched-timestep DDPM / DDIM schedulers
 # (diffusers/schedulers/scheduling_ddpm.py, scheduling_ddim.py).  Coefficient tables live on the host; the per-sample
-# linear combinations run on the HIP elementwise kernel ctta_lincomb2_rows.
+# linear combinations run on the HIP elementwise kernel ctta_lincomb2_rows.  Stage 2 with use_edm=False (the reference's
+# default, audio_consistency_model.py:72-75) distils with DDIMScheduler too, through its one-pass forms
+# (`step_fused` / `add_noise_last`: ctta_ddim_step / ctta_ddim_noising).
 SD21_DDIM_EXTRA = dict(clip_sample=False, set_alpha_to_one=False)
 
 
@@ -372,3 +403,62 @@ class DDIMScheduler(_LinCombMixin):
         if not return_dict:
             return (prev_sample,)
         return SimpleNamespace(prev_sample=prev_sample, pred_original_sample=x0)
+
+    # ---- the one-pass forms stage 2 runs (AudioLCM with use_edm=False): ctta_ddim_step / ctta_ddim_noising.  Same host
+    # tables and the same fp32 operations per element as `step` / `add_noise` above, which stage 1 keeps.
+    def step_coeffs(self, timestep, B):
+        """(4, B) float32 host table of `step`: sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        t = self._t_index(timestep, B)
+        prev = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_prev = torch.where(prev >= 0, self.alphas_cumprod[prev.clamp(min=0)], self.final_alpha_cumprod)
+        return torch.stack([a_t ** 0.5, (1 - a_t) ** 0.5, a_prev ** 0.5, (1 - a_prev) ** 0.5]).to(torch.float32)
+
+    def noise_coeffs(self, timesteps, B):
+        """(2, B) float32 host table of `add_noise`: sqrt(a_t), sqrt(1 - a_t)."""
+        ac = self.alphas_cumprod[self._t_index(timesteps, B)]
+        return torch.stack([ac ** 0.5, (1 - ac) ** 0.5]).to(torch.float32)
+
+    def step_fused(self, model_output, timestep, sample, cfg_w=None, coeffs=None, out=None, want_x0=False):
+        """`step(...).prev_sample` in one launch.  With `cfg_w` ((B,) device float32) `model_output` holds 2B rows
+        [uncond | cond] and the classifier-free combine (audio_distilled_model.py:313-319) is part of the pass.
+        `coeffs`: the (4, B) table already on the device (a captured step keeps it in a static input)."""
+        if not sample.is_cuda:
+            raise N.CttaError("scheduler inputs are on %s: the HIP kernels have no CPU path" % sample.device)
+        x = sample.detach().to(torch.float32).contiguous()
+        v = model_output.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        B = x.shape[0]
+        assert v.shape[0] == (2 * B if cfg_w is not None else B), (tuple(v.shape), B)
+        if coeffs is None:
+            coeffs = self.step_coeffs(timestep, B).to(x.device)
+        assert coeffs.shape == (4, B) and coeffs.dtype == torch.float32 and coeffs.is_contiguous()
+        prev = torch.empty_like(x) if out is None else out
+        x0 = torch.empty_like(x) if want_x0 else None
+        clamp = float(self.config.clip_sample_range) if self.config.clip_sample else 0.0
+        with torch.cuda.device(x.device):
+            N.check(N.lib().ctta_ddim_step(
+                N.ptr(v), N.ptr(cfg_w) if cfg_w is not None else N.c_void_p(0), N.ptr(x), N.ptr(coeffs[0]),
+                N.ptr(coeffs[1]), N.ptr(coeffs[2]), N.ptr(coeffs[3]),
+                0 if self.config.prediction_type == "v_prediction" else 1, clamp, N.ptr(prev),
+                N.ptr(x0) if want_x0 else N.c_void_p(0), B, x[0].numel(), N.stream_ptr()))
+        return (prev, x0) if want_x0 else prev
+
+    def add_noise_last(self, original_samples, noise, timesteps, last=None, init_sigma=None, coeffs=None, out=None):
+        """`add_noise` with the last-step select of the distillation step (audio_consistency_model.py:312-319) in one
+        launch: rows with `last` ((B,) device float32, nonzero) become noise * init_noise_sigma."""
+        if not original_samples.is_cuda:
+            raise N.CttaError("scheduler inputs are on %s: the HIP kernels have no CPU path" % original_samples.device)
+        x = original_samples.detach().to(torch.float32).contiguous()
+        nz = noise.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        B = x.shape[0]
+        if coeffs is None:
+            coeffs = self.noise_coeffs(timesteps, B).to(x.device)
+        res = torch.empty_like(x) if out is None else out
+        sig0 = float(self.init_noise_sigma if init_sigma is None else init_sigma)
+        with torch.cuda.device(x.device):
+            N.check(N.lib().ctta_ddim_noising(N.ptr(x), N.ptr(nz), N.ptr(coeffs[0]), N.ptr(coeffs[1]),
+                                              N.ptr(last) if last is not None else N.c_void_p(0), sig0, N.ptr(res), B,
+                                              x[0].numel(), N.stream_ptr()))
+        return res

@@ -327,6 +327,28 @@ ctta_status ctta_snr_mse_loss(const float* pred, const float* target, const floa
  * of AudioGDM.forward's get_loss (models/audio_guided_model.py:92-117). */
 ctta_status ctta_lincomb2_rows(const float* x, const float* y, const float* a, const float* b, float* out,
                                int batch, int64_t n_per_sample, float clamp, void* stream);
+/* The DDIM solver of stage-2 consistency distillation (AudioLCM with use_edm=False, models/audio_consistency_model.py:
+ * 72-75,313-340) as one-pass primitives with PER-SAMPLE coefficients ((B) f32 on device: sqrt(alphas_cumprod[t]),
+ * sqrt(1 - alphas_cumprod[t]) and the same two at the previous timestep).
+ * ctta_ddim_step: DDIMScheduler.step with eta = 0 (diffusers/schedulers/scheduling_ddim.py:243-370, batched timesteps):
+ *   x0 = sqrt_a_t * sample - sqrt_1m_a_t * v            (v_prediction, :310-314)
+ *   x0 = (sample - sqrt_1m_a_t * v) / sqrt_a_t          (epsilon, :305-306; as (1/sqrt_a_t) * sample + (-sqrt_1m_a_t/sqrt_a_t) * v)
+ *   x0 clamped to [-clamp, clamp] when clamp > 0 (:321-324); eps = sqrt_a_t * v + sqrt_1m_a_t * sample (v_prediction) or v;
+ *   prev_sample = sqrt_a_prev * x0 + sqrt_1m_a_prev * eps (:345-349).
+ * model_output is (B, n_per_sample) when cfg_w is NULL; otherwise (2B, n_per_sample) = [uncond | cond] and
+ * v = (1 - cfg_w[b]) * uncond + cfg_w[b] * cond first (models/audio_distilled_model.py:313-319).  pred_original_sample may be
+ * NULL.  Bit-identical to ctta_cfg_combine followed by three ctta_lincomb2_rows (the chain DDIMScheduler.step launches).
+ * ctta_ddim_noising: DDIMScheduler.add_noise (:372-393) with the last-step select of the distillation step
+ * (models/audio_consistency_model.py:312-319): out = last[b] != 0 ? noise * init_sigma : sqrt_a * x0 + sqrt_1m_a * noise;
+ * last (B) f32 may be NULL (plain add_noise). */
+enum { CTTA_DDIM_V_PREDICTION = 0, CTTA_DDIM_EPSILON = 1 };
+ctta_status ctta_ddim_step(const float* model_output, const float* cfg_w, const float* sample, const float* sqrt_a_t,
+                           const float* sqrt_1m_a_t, const float* sqrt_a_prev, const float* sqrt_1m_a_prev,
+                           int prediction_type, float clamp, float* prev_sample, float* pred_original_sample,
+                           int batch, int64_t n_per_sample, void* stream);
+ctta_status ctta_ddim_noising(const float* x0, const float* noise, const float* sqrt_a, const float* sqrt_1m_a,
+                              const float* last, float init_sigma, float* out, int batch, int64_t n_per_sample,
+                              void* stream);
 ctta_status ctta_weighted_mse_loss(const float* pred, const float* target, const float* weights,
                                    float* per_instance, float* loss, int batch, int64_t n_per_sample,
                                    void* stream);
