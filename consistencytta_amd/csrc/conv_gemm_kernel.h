@@ -32,6 +32,9 @@
 #ifndef CTTA_XBAR_MIN
 #define CTTA_XBAR_MIN 32
 #endif
+#ifndef CTTA_XBAR_STAGGER
+#define CTTA_XBAR_STAGGER 1
+#endif
 
 // MODE 0: register-staged tiles (supports in_act).  MODE 1: direct-to-LDS, generic gather (per-lane
 // global pointers, zero page).  MODE 2: direct-to-LDS through BUFFER descriptors with the address
@@ -623,14 +626,68 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, unsigned char* sm
     // LDS-DMA has 1.5 steps to land with the same two buffers: parity-green, 256 registers, 2.4 % SLOWER.  Like the deeper
     // rings at BK = 32, it says the step is not waiting for the LDS-DMA's latency.  And a hand-pinned two-phase schedule --
     // sched_group_barrier: per position fragment four MFMAs, then the read that takes over its registers, so that no read
-    // is waited for behind the barrier at all (in the loop below the compiler sinks the first-half reads under the held
-    // MFMAs) -- runs at exactly the same speed with 14 more registers: profiles/ab_r05_xbar3_streaming_schedule.txt.)
+    // is waited for behind the barrier at all (in the lockstep loop below the compiler issues ONE of the ten first-half reads
+    // under the held MFMAs and waits for the other nine behind them: held half + first half + the DMA's per-lane state do not
+    // fit 256 registers at once) -- runs at exactly the same speed with 14 more registers:
+    // profiles/ab_r05_xbar3_streaming_schedule.txt.)
     constexpr bool XBAR = FAST && BK == 64 && FM * FN >= CTTA_XBAR_MIN && CTTA_XBAR;
+    // STAGGER (CTTA_XBAR_STAGGER, -DCTTA_XBAR_STAGGER=0 compiles the lockstep loop below): the eight-wave XBAR tiles (256x256x64, its
+    // stream-K form, 512x128x64) put two waves on every SIMD, and in lockstep both reach the two MFMA-free stretches of a K step --
+    // the LDS-DMA issue for tile kt + 1 (8 loads + ~45 address instructions) and the wait for the first fragments of tile kt --
+    // together, so the SIMD's matrix pipe idles through both.  Here waves 0-3 keep the order [DMA issue, 32 held MFMAs, reads,
+    // 32 MFMAs] and waves 4-7 run [32 held MFMAs, DMA issue, reads, 32 MFMAs]: split by wave number, not parity, so every SIMD
+    // holds one wave of each half and one wave's address work lies beside its partner's MFMAs.  The DMA of the late half writes the
+    // slot nobody reads in this step and is covered by the same vmcnt(0) in front of the barrier; it has about three quarters of a
+    // step to land (the step does not wait for DMA latency, see above).  Registers 216 / 230 / 249 as before (parent 216 / 230 /
+    // 250), no spills, same MFMA order per accumulator: bit-identical outputs (bench.py --dump-outputs: pcm.npy array_equal).
+    // Same-box A/B against the parent, three alternating rounds (profiles/ab_stagger_tiles.txt, ab_stagger_gen.txt), TFLOP/s:
+    // 131072x512x4608 1232 -> 1308, 524288x256x2304 1171 -> 1256, 2097152x256x2304 1197 -> 1241, 655488x256x5632 1243 -> 1303,
+    // 163872x512x11264 1188 -> 1252 (main loop per workgroup -12 %), 512x128x64 on 1310976x128x2816 1090 -> 1152, stream-K 766 ->
+    // 790 and 839 -> 854; generation 418.2 -> 424.4 clips/s (76.52 -> 75.40 ms per step).
+    // Measured beside it and not kept (same file): the first-half reads issued AHEAD of the late half's DMA, so that the address
+    // work hides their latency -- 48 more registers live at that point: 5 / 48 / 70 spilled, equal on the 256-row tile where the
+    // spills stay outside the loop, 0.6x where they do not; half or a quarter of the pixel fragments read ahead with column-major
+    // MFMAs (248 / 240 registers on the big tile): equal; the pinned streaming schedule of round 5 under the stagger: 50-105
+    // spilled, not run; `s_setprio 1` for waves 4-7 alone or on top: within the spread.  A half-step LAG (the late half entering
+    // the barrier with 16-32 more MFMAs pending) needs 32-40 registers beyond the held half's 48 and was not built.
+    constexpr bool STAGGER = XBAR && WM * WN == 8 && CTTA_XBAR_STAGGER;
     if constexpr (XBAR) {
       bf16x8_t ha[FN], hb[FM];
       const bf16_t* xs0 = Xs + (wm * TM + frow) * LDK;
       const bf16_t* ws0 = Ws + (wn * TN + frow) * LDK;
       const int koff0 = ((fchunk ^ fswz) & SWZ_MASK) * 8, koff1 = (((4 + fchunk) ^ fswz) & SWZ_MASK) * 8;
+      if constexpr (STAGGER) {
+        const bool late = wave_u >= 4;     // wave-uniform: scalar branches
+        for (int kt = 0; kt < nk; ++kt) {
+          const int buf = kt & 1;
+          if (!late && kt + 1 < nk) issue_fast(kt_begin + kt + 1, buf ^ 1);
+          if (wave_live && kt > 0) {
+#pragma unroll
+            for (int i = 0; i < FN; ++i)
+#pragma unroll
+              for (int j = 0; j < FM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ha[i], hb[j], acc[i][j], 0, 0, 0);
+          }
+          if (late && kt + 1 < nk) issue_fast(kt_begin + kt + 1, buf ^ 1);
+          if (wave_live) {
+            const bf16_t* xs = xs0 + buf * BM * LDK;
+            const bf16_t* ws = ws0 + buf * BN * LDK;
+            bf16x8_t fa[FN], fb[FM];
+#pragma unroll
+            for (int i = 0; i < FN; ++i) fa[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ws + i * 16 * LDK + koff0));
+#pragma unroll
+            for (int j = 0; j < FM; ++j) fb[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xs + j * 16 * LDK + koff0));
+#pragma unroll
+            for (int i = 0; i < FN; ++i) ha[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ws + i * 16 * LDK + koff1));
+#pragma unroll
+            for (int j = 0; j < FM; ++j) hb[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xs + j * 16 * LDK + koff1));
+#pragma unroll
+            for (int i = 0; i < FN; ++i)
+#pragma unroll
+              for (int j = 0; j < FM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+          }
+          __syncthreads();
+        }
+      } else
       for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) issue_fast(kt_begin + kt + 1, buf ^ 1);

@@ -126,23 +126,30 @@ SHAPES = [
     ("d9 lin M4608 1024>1024", 18, 256, 1, 1024, 1024, 1, 1, 1),
     ("d9 lin M36864 256>2048", 9, 4096, 1, 256, 2048, 1, 1, 1),
     ("d9 lin M9216 2048>512", 9, 1024, 1, 2048, 512, 1, 1, 1),
+    # round 6: the big-tile rows of profiles/launch_table_r06.txt that the list lacked (the HiFi-GAN upsamplers as the GEMMs
+    # they run as: M x N x K = 655488 x 256 x 5632, 163872 x 512 x 11264, 1310976 x 128 x 2816): SWEEP_FILTER=r06
+    ("r06 hifi L20484 512>256 k11", 32, 1, 20484, 512, 256, 1, 11, 1),
+    ("r06 hifi L5121 1024>512 k11", 32, 1, 5121, 1024, 512, 1, 11, 1),
+    ("r06 hifi L40968 256>128 k11", 32, 1, 40968, 256, 128, 1, 11, 1),
 ]
 
 
 def main():
-    # SWEEP_FILTER=substring restricts the shapes; SWEEP_VARIANTS=17,18,... the variants; SWEEP_EPI=1 adds the
-    # HiFi-GAN ResBlock epilogue (residual read + second, LeakyReLU'd output) to every launch
+    # SWEEP_FILTER=substring[,substring...] restricts the shapes; SWEEP_VARIANTS=17,18,... the variants; SWEEP_EPI=1 adds the
+    # HiFi-GAN ResBlock epilogue (residual read + second, LeakyReLU'd output) to every launch; SWEEP_REPS=n times n launches
+    # per variant instead of 5 (a window of a few milliseconds measures the clock ramp as much as the kernel)
     L = N.lib()
     nvar = L.ctta_conv_gemm_num_variants()
     names = [L.ctta_conv_gemm_variant_name(i + 1).decode() for i in range(nvar)]
-    flt = os.environ.get("SWEEP_FILTER", "")
+    flt = [f for f in os.environ.get("SWEEP_FILTER", "").split(",") if f]
+    nreps = int(os.environ.get("SWEEP_REPS", "5"))
     only = [int(v) for v in os.environ.get("SWEEP_VARIANTS", "").split(",") if v]
     epi = os.environ.get("SWEEP_EPI", "0") == "1"
     geglu = os.environ.get("SWEEP_GEGLU", "0") == "1"
     print("variants:", names if not only else [names[v - 1] for v in only])
     results = []
     for (tag, B, H, W, Cin, Cout, kh, kw, dil) in SHAPES:
-        if flt and flt not in tag:
+        if flt and not any(f in tag for f in flt):
             continue
         x = (torch.randn(B, H, W, Cin, device=DEV) * 0.5).to(torch.bfloat16)
         K = kh * kw * Cin
@@ -194,7 +201,7 @@ def main():
             N.check(L.ctta_conv_gemm(ctypes.byref(d), st))
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            reps = 5 if ncopy == 1 else 2 * ncopy
+            reps = nreps if ncopy == 1 else 2 * ncopy
             e0.record()
             for r_ in range(reps):
                 d.w = ws[r_ % ncopy].data_ptr()
