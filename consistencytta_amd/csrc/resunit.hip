@@ -15,6 +15,17 @@
 //      C-channel rows leave as 64..256-byte segments.
 // HBM sees x once and the output once.
 //
+// Schedule (CTTA_RESUNIT_OVERLAP, default 1; 0 compiles the round-6 schedule; same arithmetic in the same order either way, so
+// the outputs are bit-identical):
+//   * K loops (every width, KT = 3 / 7 / 11): a wave reads its position fragments two blocks ahead of the MFMAs that consume
+//     them, the order [one ds_read_b128, NCB MFMAs] pinned -- a wave covers its own LDS latency instead of leaning on the
+//     wave it shares the SIMD with.  This is where the gain is: 2-5 % per unit, 0.7 ms of the 73.8 ms generation step.
+//   * memory phases (C = 32 / 64 / 256): conv1's first weight fragments and bias are requested in front of the staging loads,
+//     ALL staging loads of the tile are in flight before the first conversion, conv2's first weight fragments travel under
+//     the intermediate write, the epilogue's bias and first residual / old-output rows under conv2's K loop.  Worth 0-6 %
+//     per unit at these widths; at C = 128 / 512 it measured level or slower and is not compiled in.
+// What the phase stamps showed, and why the tile walk with next-tile staging under the epilogue was not built: LABNOTES R8.
+//
 // MFMA mapping (v_mfma_f32_16x16x32_bf16, weights = A operand, positions = B operand, as in conv_gemm): the
 // workgroup's 4 waves are split WC x WP; wave (wc, wp) owns a slice of C / WC output channels (NCB = 2 blocks of 16)
 // for the positions of part wp.  WEIGHT-STATIONARY: a wave streams its own rows of the weight matrix straight from
@@ -42,12 +53,26 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 // workgroup barrier that orders LDS traffic only (leaves global loads / stores in flight)
 #define LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
+// the schedule switch of resunit_kernel (header comment); -DCTTA_RESUNIT_OVERLAP=0 goes through CTTA_EXTRA_FLAGS of build.sh, so
+// both libraries of an A/B build from one tree
+#ifndef CTTA_RESUNIT_OVERLAP
+#define CTTA_RESUNIT_OVERLAP 1
+#endif
+
 // KT: the tap count when it is one of the vocoder's (3 / 7 / 11: both K loops fully unrolled, so the weight prefetch keeps
 // its distance without a back edge), 0 = read it from the parameters.
 template <int C, int WC, int WP, int T, int KT>
 __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_kernel(const ResUnitParams p) {
   static_assert(WC * WP == 4 || WC * WP == 8, "four waves per workgroup (C <= 128) or eight (C = 256: one workgroup per CU)");
   constexpr int NT = WC * WP * 64;           // threads per workgroup
+  // the memory-phase overlap where it measured faster per unit than round 6's phases (profiles/ab_resunit_overlap_units.txt:
+  // C = 32 / 64 / 256; at C = 128 it lost 1 %, at C = 512 0.1-0.4 %, so those widths keep the round-6 phases)
+  constexpr bool OVL = CTTA_RESUNIT_OVERLAP != 0 && C != 128 && C != 512;
+  // Position fragments are read LA = 2 ahead of the MFMAs that consume them (the K loops unrolled for KT = 3 / 7 / 11 only), and
+  // the order [one ds_read_b128, NCB MFMAs] is pinned per position block.  The compiler's own order issued two reads and waited
+  // for the first at once: a wave covered no LDS latency by itself and leaned on its SIMD partner, which the stamps show running
+  // far behind it (LABNOTES R8).  Same MFMA order per accumulator; +0 to +4 registers, occupancy unchanged.
+  constexpr int LA = CTTA_RESUNIT_OVERLAP != 0 && KT != 0 ? 2 : 0;
   // Round 6: without the scheduling barrier behind each weight prefetch the compiler sinks the loads to the MFMAs that consume
   // them (s_waitcnt vmcnt(0) per K step, the same thing ffn_fused.hip's first version showed): pinned, C = 128 k = 11 / 7 / 3
   // 0.885 / 0.603 / 0.328 -> 0.749 / 0.518 / 0.304 ms per unit at B = 32 (1 262 / 1 162 / 849 TFLOP/s), C = 64 k = 11 0.503 -> 0.428
@@ -87,8 +112,51 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
   const unsigned sample_bytes = (unsigned)L * C * 2;
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, sample_bytes, 0x00020000);
 
+  // conv1's first two weight fragments and its bias: with the overlap schedule they are requested HERE, in front of the
+  // staging loads (their L2 / HBM latency hides under the tile's), otherwise in front of the first MFMA as in round 6
+  const int cb0 = wc * NCB;
+  const int nsteps = k * NCH;
+  bf16x8_t wa0[NCB], wa1[NCB];
+  float4 bias1[NCB];
+  if constexpr (OVL) {
+    const uint4* wf = reinterpret_cast<const uint4*>(p.w1f) + (size_t)cb0 * nsteps * 64 + lane;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      wa0[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps) * 64]);
+      wa1[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps + (nsteps > 1 ? 1 : 0)) * 64]);
+      bias1[cb] = *reinterpret_cast<const float4*>(p.b1 + (cb0 + cb) * 16 + lg * 4);
+    }
+    __builtin_amdgcn_sched_barrier(0);       // pinned: the compiler would sink them to the first MFMA again
+  }
+
   // ---- 1. leaky_relu(x) tile -> LDS (zero outside the sequence: F.conv1d pads the ACTIVATED signal with zeros; the
-  //         descriptor's bounds check returns those zeros, so the loop is branch-free and SU loads are in flight per thread)
+  //         descriptor's bounds check returns those zeros, so the loads are branch-free)
+  if constexpr (OVL) {
+    // Every load of the tile is in flight before the first conversion: ONE HBM round trip per tile instead of one per
+    // SU = 4 loads.  ML = the loads per thread of the longest tile the LDS budget admits (13-20; the registers are free
+    // here).  A load whose row lies past rows_in gets an offset beyond any record count (2^31 >= L * C * 2), so the rows
+    // addressed are exactly [l0 - H1 - H2, l0 - H1 - H2 + rows_in): fewer than resunit_max_len allows for.  Only the
+    // LDS stores are guarded -- a guard around a LOAD compiles into a branch and a full vmcnt(0) in front of every store.
+    constexpr int CV = C / 8, RPS = NT / CV;                   // uint4 per row, rows per sweep of the workgroup
+    constexpr int ML = ((NT == 512 ? 160 : 64) * 1024 / (RS * 2) + RPS - 1) / RPS;
+    const int cc = tid % CV, rr = tid / CV;
+    const int voff = ((l0 - H1 - H2 + rr) * C + cc * 8) * 2;   // (see below: the whole byte offset in the VGPR)
+    bf16_t* trow = tile + rr * RS + cc * 8;
+    u32x4_t v[ML];
+#pragma unroll
+    for (int u = 0; u < ML; ++u)
+      v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsx, u * RPS + rr < rows_in ? voff + u * RPS * C * 2 : (int)0x80000000, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < ML; ++u)
+      if (u * RPS + rr < rows_in) {
+        float f[8];
+        unpack8(make_uint4(v[u][0], v[u][1], v[u][2], v[u][3]), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], f[e] * slope);     // leaky_relu for 0 <= slope <= 1 (checked by the host)
+        *reinterpret_cast<uint4*>(trow + u * RPS * RS) = pack8(f);
+      }
+  } else
   {
     constexpr int SU = 4, CV = C / 8, RPS = NT / CV;           // uint4 per row, rows per sweep of the workgroup
     const int cc = tid % CV, rr = tid / CV;
@@ -125,27 +193,39 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
   if (stamp && tid == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); stamp[2] = __builtin_amdgcn_s_memtime(); }
 
   // ---- 2. conv1: rows [mb0*16, (mb0 + MBW)*16) of the intermediate, couts [cout0, cout0 + 16*NCB)
-  const int cb0 = wc * NCB;
   const int mb0 = wp * MBW;
   f32x4_t acc[NCB][MBW];
 #pragma unroll
   for (int i = 0; i < NCB; ++i)
 #pragma unroll
     for (int j = 0; j < MBW; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  float4 bias1[NCB];
+  if constexpr (!OVL) {
 #pragma unroll
-  for (int cb = 0; cb < NCB; ++cb) bias1[cb] = *reinterpret_cast<const float4*>(p.b1 + (cb0 + cb) * 16 + lg * 4);
-  const int nsteps = k * NCH;
+    for (int cb = 0; cb < NCB; ++cb) bias1[cb] = *reinterpret_cast<const float4*>(p.b1 + (cb0 + cb) * 16 + lg * 4);
+  }
   {
     const uint4* wf = reinterpret_cast<const uint4*>(p.w1f) + (size_t)cb0 * nsteps * 64 + lane;
     bf16x8_t a0[NCB], a1[NCB], a2[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-      a0[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps) * 64]);
-      a1[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps + (nsteps > 1 ? 1 : 0)) * 64]);
+      if constexpr (OVL) { a0[cb] = wa0[cb]; a1[cb] = wa1[cb]; }
+      else {
+        a0[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps) * 64]);
+        a1[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps + (nsteps > 1 ? 1 : 0)) * 64]);
+      }
     }
     __syncthreads();
     const bf16_t* xw = tile + (mb0 * 16 + lq) * RS + lg * 8;
+    // position fragment i = st * MBW + pb of the whole K loop (LA > 0: the loop is unrolled, i is a constant)
+    auto frag = [&](int i) {
+      const int s_ = i / MBW, pb_ = i % MBW;
+      return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xw + (s_ / NCH) * dil * RS + (s_ % NCH) * 32 + pb_ * 16 * RS));
+    };
+    bf16x8_t ring[LA + 1];
+    if constexpr (LA > 0) {
+#pragma unroll
+      for (int i = 0; i < LA; ++i) ring[i] = frag(i);
+    }
     int st = 0;
 #pragma unroll
     for (int tap = 0; tap < k; ++tap) {
@@ -158,10 +238,23 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
         if (RU_PIN) __builtin_amdgcn_sched_barrier(0);     // the prefetch stays two steps ahead of its use (see ffn_fused.hip)
 #pragma unroll
         for (int pb = 0; pb < MBW; ++pb) {
-          const bf16x8_t bf = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xt + ch * 32 + pb * 16 * RS));
+          bf16x8_t bf;
+          if constexpr (LA > 0) {
+            const int i = st * MBW + pb;
+            if (i + LA < nsteps * MBW) ring[(i + LA) % (LA + 1)] = frag(i + LA);
+            bf = ring[i % (LA + 1)];
+          } else
+            bf = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xt + ch * 32 + pb * 16 * RS));
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb)
             acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[cb], bf, acc[cb][pb], 0, 0, 0);
+        }
+        if constexpr (LA > 0) {
+#pragma unroll
+          for (int pb = 0; pb < MBW; ++pb) {
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, NCB, 0);
+          }
         }
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) { a0[cb] = a1[cb]; a1[cb] = a2[cb]; }
@@ -170,6 +263,15 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
   }
   if (stamp && tid == 0) stamp[3] = __builtin_amdgcn_s_memtime();
   __syncthreads();   // every wave is done with the input tile: the intermediate takes its place
+  if constexpr (OVL) {   // conv2's first two weight fragments travel while the intermediate is written
+    const uint4* wf = reinterpret_cast<const uint4*>(p.w2f) + (size_t)cb0 * nsteps * 64 + lane;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      wa0[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps) * 64]);
+      wa1[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps + (nsteps > 1 ? 1 : 0)) * 64]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
   {
 #pragma unroll
     for (int pb = 0; pb < MBW; ++pb) {
@@ -199,6 +301,43 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
   if (stamp && tid == 0) stamp[4] = __builtin_amdgcn_s_memtime();
 
   // ---- 3. conv2 over the T output positions: rows [ob0*16, (ob0 + OB)*16), taps = consecutive intermediate rows
+  // (the epilogue's geometry: described at the epilogue below)
+  constexpr int RSF = C * 4 + 16;            // staging row stride (bytes)
+  constexpr int CH_ROWS = 32;                // rows per part and pass
+  constexpr int LPR = C / 4;                 // lanes per output row
+  constexpr int RPP = NT / LPR;              // rows finished per sweep of the workgroup
+  constexpr int NSW = WP * CH_ROWS / RPP;    // sweeps per pass
+  constexpr int NP = (OB + 1) / 2;           // passes (an odd OB -- the 80-position tile of C = 512 -- leaves half a pass)
+  const int col4 = tid % LPR, prow = tid / LPR;
+  const ConvParams& e = p.epi;
+  float4 bias4;
+  const float oslope = e.out_act == 3 ? e.out_slope : 1.0f, alpha = e.alpha;
+  const bool acc_old = e.accumulate != 0;
+  const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(reinterpret_cast<bf16_t*>(e.out) + (size_t)b * L * C), 0, sample_bytes, 0x00020000);
+  const int voff = ((l0 + prow) * C + col4 * 4) * 2;
+  // sequence position of (pass, sweep) relative to l0 + prow: part = sweep * RPP / 32 rows of 32, OB blocks per part
+  auto rel = [](int pass, int sw) { return (((sw * RPP) / CH_ROWS) * OB + pass * 2) * 16 + (sw * RPP) % CH_ROWS; };
+  // the second 16-row block of the last pass does not exist when OB is odd: its sweeps are skipped (compile-time, the loops
+  // are unrolled) -- their positions belong to the NEXT tile
+  auto live = [](int pass, int sw) { return !((OB & 1) && pass == NP - 1 && (sw * RPP) % CH_ROWS >= 16); };
+  u32x2_t rx[NSW], ro[NSW];
+  // the epilogue's bias and the residual -- and, when accumulating, the old output -- of its first pass: requested behind
+  // conv2's K loop (round 6) or, with the overlap schedule, in front of it
+  auto epi_request = [&]() {
+    bias4 = e.bias ? *reinterpret_cast<const float4*>(e.bias + col4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int sw = 0; sw < NSW; ++sw) {
+      rx[sw] = (u32x2_t){0u, 0u};
+      if (live(0, sw)) rx[sw] = __builtin_amdgcn_raw_buffer_load_b64(rsx, voff, rel(0, sw) * C * 2, 0);
+      ro[sw] = (u32x2_t){0u, 0u};
+    }
+    if (acc_old) {
+#pragma unroll
+      for (int sw = 0; sw < NSW; ++sw)
+        if (live(0, sw)) ro[sw] = __builtin_amdgcn_raw_buffer_load_b64(rso, voff, rel(0, sw) * C * 2, 0);
+    }
+  };
   const int ob0 = wp * OB;
   f32x4_t acc2[NCB][OB];
 #pragma unroll
@@ -210,11 +349,28 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
     bf16x8_t a0[NCB], a1[NCB], a2[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-      a0[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps) * 64]);
-      a1[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps + (nsteps > 1 ? 1 : 0)) * 64]);
+      if constexpr (OVL) { a0[cb] = wa0[cb]; a1[cb] = wa1[cb]; }
+      else {
+        a0[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps) * 64]);
+        a1[cb] = __builtin_bit_cast(bf16x8_t, wf[(size_t)(cb * nsteps + (nsteps > 1 ? 1 : 0)) * 64]);
+      }
     }
-    __syncthreads();
+    if constexpr (OVL) {
+      LDS_BARRIER();     // the intermediate is complete; the weight fragments stay in flight (no vmcnt(0) as in __syncthreads())
+      epi_request();     // served by L2 (x was staged by this CU) / HBM while the K loop runs
+      __builtin_amdgcn_sched_barrier(0);
+    } else
+      __syncthreads();
     const bf16_t* xw = tile + (ob0 * 16 + lq) * RS + lg * 8;
+    auto frag = [&](int i) {
+      const int s_ = i / OB, pb_ = i % OB;
+      return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xw + (s_ / NCH) * RS + (s_ % NCH) * 32 + pb_ * 16 * RS));
+    };
+    bf16x8_t ring[LA + 1];
+    if constexpr (LA > 0) {
+#pragma unroll
+      for (int i = 0; i < LA; ++i) ring[i] = frag(i);
+    }
     int st = 0;
 #pragma unroll
     for (int tap = 0; tap < k; ++tap) {
@@ -227,10 +383,23 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
         if (RU_PIN) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int pb = 0; pb < OB; ++pb) {
-          const bf16x8_t bf = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xt + ch * 32 + pb * 16 * RS));
+          bf16x8_t bf;
+          if constexpr (LA > 0) {
+            const int i = st * OB + pb;
+            if (i + LA < nsteps * OB) ring[(i + LA) % (LA + 1)] = frag(i + LA);
+            bf = ring[i % (LA + 1)];
+          } else
+            bf = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xt + ch * 32 + pb * 16 * RS));
 #pragma unroll
           for (int cb = 0; cb < NCB; ++cb)
             acc2[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[cb], bf, acc2[cb][pb], 0, 0, 0);
+        }
+        if constexpr (LA > 0) {
+#pragma unroll
+          for (int pb = 0; pb < OB; ++pb) {
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, NCB, 0);
+          }
         }
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) { a0[cb] = a1[cb]; a1[cb] = a2[cb]; }
@@ -253,37 +422,7 @@ __global__ __launch_bounds__(WC * WP * 64, WC * WP == 4 ? 3 : 2) void resunit_ke
   // the residual -- and, when accumulating, the old output -- of pass p + 1 is requested while pass p is finished.
   // A rolled loop over epilogue_wide4 made every sweep wait for its own residual load and for all but one of the
   // stores issued before it (the compiler's wait counts are conservative across a back edge).
-  constexpr int RSF = C * 4 + 16;            // staging row stride (bytes)
-  constexpr int CH_ROWS = 32;                // rows per part and pass
-  constexpr int LPR = C / 4;                 // lanes per output row
-  constexpr int RPP = NT / LPR;              // rows finished per sweep of the workgroup
-  constexpr int NSW = WP * CH_ROWS / RPP;    // sweeps per pass
-  constexpr int NP = (OB + 1) / 2;           // passes (an odd OB -- the 80-position tile of C = 512 -- leaves half a pass)
-  const int col4 = tid % LPR, prow = tid / LPR;
-  const ConvParams& e = p.epi;
-  const float4 bias4 = e.bias ? *reinterpret_cast<const float4*>(e.bias + col4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float oslope = e.out_act == 3 ? e.out_slope : 1.0f, alpha = e.alpha;
-  const bool acc_old = e.accumulate != 0;
-  const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(reinterpret_cast<bf16_t*>(e.out) + (size_t)b * L * C), 0, sample_bytes, 0x00020000);
-  const int voff = ((l0 + prow) * C + col4 * 4) * 2;
-  // sequence position of (pass, sweep) relative to l0 + prow: part = sweep * RPP / 32 rows of 32, OB blocks per part
-  auto rel = [](int pass, int sw) { return (((sw * RPP) / CH_ROWS) * OB + pass * 2) * 16 + (sw * RPP) % CH_ROWS; };
-  // the second 16-row block of the last pass does not exist when OB is odd: its sweeps are skipped (compile-time, the loops
-  // are unrolled) -- their positions belong to the NEXT tile
-  auto live = [](int pass, int sw) { return !((OB & 1) && pass == NP - 1 && (sw * RPP) % CH_ROWS >= 16); };
-  u32x2_t rx[NSW], ro[NSW];
-#pragma unroll
-  for (int sw = 0; sw < NSW; ++sw) {
-    rx[sw] = (u32x2_t){0u, 0u};
-    if (live(0, sw)) rx[sw] = __builtin_amdgcn_raw_buffer_load_b64(rsx, voff, rel(0, sw) * C * 2, 0);
-    ro[sw] = (u32x2_t){0u, 0u};
-  }
-  if (acc_old) {
-#pragma unroll
-    for (int sw = 0; sw < NSW; ++sw)
-      if (live(0, sw)) ro[sw] = __builtin_amdgcn_raw_buffer_load_b64(rso, voff, rel(0, sw) * C * 2, 0);
-  }
+  if constexpr (!OVL) epi_request();
 #pragma unroll
   for (int pass = 0; pass < NP; ++pass) {
     LDS_BARRIER();     // the intermediate (first pass) / the previous pass's staging rows are dead
