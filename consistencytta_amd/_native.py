@@ -251,6 +251,9 @@ SIGNATURES = {
     "ctta_logmel_to_image": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ctta_avgpool2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ctta_cnn14_head": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ctta_vggish_frontend_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "ctta_wav_to_vggish_logmel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ctta_maxpool2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ctta_reschain_supported": (c_int, [c_int, c_int, c_void_p]),
     "ctta_reschain_conv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_float, c_void_p, c_int, c_float, c_float, c_void_p]),

@@ -10,13 +10,24 @@ arithmetic on its features.
   * `calculate_fid` / `calculate_isc` / `calculate_kid` / `calculate_kl` -- audioldm_eval/metrics/{fid,isc,kid,kl}.py: same
     names, arguments, dictionary keys and random streams (np.random.RandomState(rng_seed)); host arithmetic on (N, 2048) /
     (N, 527) feature matrices, as in the reference (numpy / scipy there too).
+  * `VGGish` -- the embedding model of the Frechet Audio Distance (metrics/fad.py:39-79).  The reference takes it from
+    `torch.hub` (harritaylor/torchvggish, fad.py:53), so its sources are not in the reference tree; it is built here from the
+    published definition (TensorFlow models' vggish_input.py / mel_features.py / vggish_params.py and torchvggish's `VGG`):
+    16 kHz waveform -> 400-sample Hann frames at hop 160 -> |rfft_512| -> 64 HTK mel bands -> ln(x + 0.01) -> patches of
+    96 frames -> six 3x3 convolutions with ReLU and four 2x2 max-poolings -> three Linear layers -> 128 numbers per 0.96 s.
+    The front end runs on ctta_wav_to_vggish_logmel, the convolutions and the two wide Linear layers on ctta_conv_gemm, the
+    pooling on ctta_maxpool2, the last Linear in fp32 on ctta_linear_f32; state-dict keys are torchvggish's, so the released
+    `vggish-10086976.pth` loads as it is.
+  * `calculate_fid` / `calculate_isc` / `calculate_kid` / `calculate_kl` / `calculate_fad` -- audioldm_eval/metrics/{fid,isc,
+    kid,kl,fad}.py: same names, dictionary keys and random streams; `load_audio_task` is fad.py's own file loader.
   * `EvaluationHelper` -- audioldm_eval/eval.py:58-349: `get_featuresdict`, `calculate_metrics` on two directories of .wav
-    files (or two lists of waveforms), the CLAP scores through `consistencytta_amd.clap.CLAP_Module`.
+    files (or two lists of waveforms), the CLAP scores through `consistencytta_amd.clap.CLAP_Module`, the Frechet Audio
+    Distance through a `VGGish` passed as `vggish_model`.
 
-Not rebuilt, and reported as NaN exactly like a key the reference leaves out (eval.py:297-299 `out.get(key, nan)`):
-frechet_audio_distance (VGGish through `torch.hub`, metrics/fad.py:53 -- its sources are not in the reference tree), lsd / ssim_stft
-(`ssr_eval`, a pip dependency) and psnr / ssim (`skimage`).  Resampling of files whose rate is not an integer multiple of the
-target (`resampy`, load_mel.py:25-28) is refused loudly.
+Not rebuilt, and reported as NaN exactly like a key the reference leaves out (eval.py:297-299 `out.get(key, nan)`): lsd /
+ssim_stft (`ssr_eval`, a pip dependency) and psnr / ssim (`skimage`); frechet_audio_distance is NaN too when no `vggish_model`
+is given.  Resampling of files whose rate is not an integer multiple of the target (`resampy`, load_mel.py:25-28,
+fad.py:33-34) is refused loudly.
 """
 import os
 from collections import OrderedDict
@@ -30,12 +41,40 @@ from . import spec
 from .clap import PackedLinear, _check_cuda, _conv, _desc
 from .modules import _ParamTree
 
-__all__ = ["Cnn14", "EvaluationHelper", "calculate_fid", "calculate_isc", "calculate_kid", "calculate_kl",
-           "read_centered_wav", "pad_short_audio"]
+__all__ = ["Cnn14", "VGGish", "EvaluationHelper", "calculate_fid", "calculate_isc", "calculate_kid", "calculate_kl",
+           "calculate_fad", "read_centered_wav", "pad_short_audio", "load_audio_task"]
 
 
 # ------------------------------------------------------------------------------------------------ classifier
-class Cnn14(_ParamTree):
+class _FrontendHandle:
+    """The ctta_mel_frontend handle of a model: created on first use by the model's `_create_frontend(max_batch,
+    max_samples, handle)`, re-created when a larger batch or a longer clip arrives, destroyed with the model."""
+
+    _fe = _fe_key = None
+
+    def __del__(self):
+        try:
+            self._release_frontend()
+        except Exception:
+            pass
+
+    def _release_frontend(self):
+        if self._fe is not None:
+            N.lib().ctta_mel_frontend_destroy(self._fe)
+            self._fe = self._fe_key = None
+
+    def _frontend(self, B, L):
+        key = self._fe_key
+        if self._fe is None or B > key[0] or L > key[1]:
+            Bm, Lm = (max(B, key[0]), max(L, key[1])) if key else (B, L)
+            self._release_frontend()
+            h = N.c_void_p()
+            N.check(self._create_frontend(Bm, Lm, h))
+            self._fe, self._fe_key = h, (Bm, Lm)
+        return self._fe
+
+
+class Cnn14(_FrontendHandle, _ParamTree):
     """`Cnn14(features_list, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num)` of the reference,
     eval mode (no SpecAugment, mixup or dropout: eval.py:83 calls `.eval()`), without the checkpoint download of its
     constructor (models.py:236-253): load the released state dict with `load_state_dict(torch.load(...)["model"])`."""
@@ -71,28 +110,10 @@ class Cnn14(_ParamTree):
                     p.copy_(torch.from_numpy(spec.cnn14_det_weight(prefix + k, tuple(p.shape), seed)).to(p.device))
         return self
 
-    def __del__(self):
-        try:
-            self._release_frontend()
-        except Exception:
-            pass
-
-    def _release_frontend(self):
-        if self._fe is not None:
-            N.lib().ctta_mel_frontend_destroy(self._fe)
-            self._fe = self._fe_key = None
-
-    def _frontend(self, B, L):
-        key = self._fe_key
-        if self._fe is None or B > key[0] or L > key[1]:
-            Bm, Lm = (max(B, key[0]), max(L, key[1])) if key else (B, L)
-            self._release_frontend()
-            c = self.cfg
-            h = N.c_void_p()
-            N.check(N.lib().ctta_mel_frontend_create(c["n_fft"], c["hop"], c["n_fft"], c["mel_bins"], c["sample_rate"],
-                                                     float(c["fmin"]), float(c["fmax"]), Bm, Lm, h))
-            self._fe, self._fe_key = h, (Bm, Lm)
-        return self._fe
+    def _create_frontend(self, max_batch, max_samples, h):
+        c = self.cfg
+        return N.lib().ctta_mel_frontend_create(c["n_fft"], c["hop"], c["n_fft"], c["mel_bins"], c["sample_rate"],
+                                                float(c["fmin"]), float(c["fmax"]), max_batch, max_samples, h)
 
     def _pack(self):
         ver = self._weights_version()
@@ -174,14 +195,161 @@ class Cnn14(_ParamTree):
         return {"logits": logits, "2048": emb, "clipwise_output": torch.sigmoid(logits)}
 
 
+class VGGish(_FrontendHandle, _ParamTree):
+    """torchvggish's `VGG` as metrics/fad.py:46-60 configures it (`use_pca=False, use_activation=False`: no PCA / quantisation
+    post-processor, the ReLU behind the last Linear removed), eval mode, without the hub download: load the released state
+    dict with `load_state_dict(torch.load("vggish-10086976.pth"))`."""
+
+    def __init__(self, use_pca=False, use_activation=False):
+        super().__init__()
+        if use_pca:
+            raise N.CttaError("VGGish(use_pca=True): the PCA / quantisation post-processor is not built (fad.py:54-55 "
+                              "switches it off)")
+        self.use_activation = bool(use_activation)
+        self.cfg = dict(spec.VGGISH_CONFIG)
+        self._register(spec.vggish_param_spec())
+        self.requires_grad_(False)
+        self._packed = self._packed_ver = None
+        self._fe = self._fe_key = None
+
+    @property
+    def device(self):
+        return self.get_parameter("embeddings.4.weight").device
+
+    def load_state_dict(self, state_dict, strict=True):
+        """torchvggish keys; the `pproc.*` PCA tables of a hub-built model are accepted and ignored."""
+        keep = OrderedDict((k, v) for k, v in state_dict.items() if not k.startswith("pproc."))
+        return super().load_state_dict(keep, strict=strict)
+
+    def init_deterministic(self, seed=0, prefix="vggish."):
+        with torch.no_grad():
+            for k, p in self.named_parameters():
+                p.copy_(torch.from_numpy(spec.vggish_det_weight(prefix + k, tuple(p.shape), seed)).to(p.device))
+        return self
+
+    def n_examples(self, n_samples):
+        """96-frame examples of a clip of `n_samples` samples (vggish_input.waveform_to_examples: frames of 400 at hop 160
+        without padding, examples at hop 96, the incomplete tail dropped)."""
+        c = self.cfg
+        if n_samples < c["window"]:
+            return 0
+        return (1 + (n_samples - c["window"]) // c["hop"]) // c["example_frames"]
+
+    def _create_frontend(self, max_batch, max_samples, h):
+        return N.lib().ctta_vggish_frontend_create(max_batch, max_samples, h)
+
+    def _pack(self):
+        ver = self._weights_version()
+        if self._packed is not None and self._packed_ver == ver:
+            return self._packed
+        sd = {k: p.detach() for k, p in self.named_parameters()}
+        for k, p in sd.items():
+            _check_cuda(p, "parameter '%s'" % k)
+        P = {}
+        for i, ci, co in self.cfg["convs"]:
+            cp = max(8, ci)                                  # NHWC channel count of the layer's input (1 -> 8)
+            colmap = [-1] * (9 * cp)
+            for t in range(9):
+                for ch in range(ci):
+                    colmap[t * cp + ch] = ch * 9 + t         # (cout, cin, kh, kw) rows -> (kh, kw, c) columns
+            w = sd["features.%d.weight" % i].float().reshape(co, ci * 9)
+            P["features.%d" % i] = PackedLinear(w, sd["features.%d.bias" % i], list(range(co)), colmap, need_grad=False)
+        for i, ci, co in self.cfg["linears"][:2]:
+            # torchvggish flattens (N, 512, 6, 4) in (frame, mel, channel) order: the NHWC activation as it lies in memory
+            P["embeddings.%d" % i] = PackedLinear(sd["embeddings.%d.weight" % i].float(), sd["embeddings.%d.bias" % i],
+                                                  list(range(co)), list(range(ci)), need_grad=False)
+        P["unit"] = (torch.ones(self.cfg["mel_bins"], dtype=torch.float32, device=self.device),
+                     torch.zeros(self.cfg["mel_bins"], dtype=torch.float32, device=self.device))
+        self._packed, self._packed_ver = P, ver
+        return P
+
+    def logmel_examples(self, wav):
+        """(B, L) fp32 at 16 kHz on the GPU -> (B * n_examples, 96, 64) fp32 log-mel patches, clip-major."""
+        wav = wav.contiguous().float()
+        _check_cuda(wav, "waveform")
+        if wav.dim() != 2:
+            raise ValueError("VGGish takes a (batch, samples) waveform, got %s" % (tuple(wav.shape),))
+        B, L = wav.shape
+        c = self.cfg
+        ne = self.n_examples(L)
+        if ne < 1:
+            raise ValueError("%d samples hold no %d-frame example: 15600 samples at least" % (L, c["example_frames"]))
+        lm = torch.empty(B, ne * c["example_frames"], c["mel_bins"], dtype=torch.float32, device=wav.device)
+        clips = max(1, self.MAX_EXAMPLES // ne)
+        for b0 in range(0, B, clips):
+            b1 = min(B, b0 + clips)
+            N.check(N.lib().ctta_wav_to_vggish_logmel(self._frontend(b1 - b0, L), N.ptr(wav[b0:b1]), b1 - b0, L,
+                                                      N.ptr(lm[b0:b1]), N.stream_ptr()))
+        return lm.view(B * ne, c["example_frames"], c["mel_bins"])
+
+    MAX_EXAMPLES = 512      # examples per pass of the network: bounds the activations (0.4 GB behind the first convolution)
+
+    def _features(self, lm, P):
+        """lm (n, 96, 64) fp32 -> the `features` stack: bf16 (n, 6 * 4 * 512), NHWC, which is torchvggish's flatten order
+        (`transpose(1, 3)`, `transpose(1, 2)`, `view`: frame, mel, channel)."""
+        c = self.cfg
+        L_ = N.lib()
+        s = N.stream_ptr()
+        dev = lm.device
+        n, H, W = lm.shape
+        x = torch.empty(n, H, W, 8, dtype=torch.bfloat16, device=dev)
+        N.check(L_.ctta_logmel_to_image(N.ptr(lm), n, H, W, N.ptr(P["unit"][0]), N.ptr(P["unit"][1]), N.ptr(x), s))
+        cp = 8
+        for i, ci, co in c["convs"]:
+            W_ = P["features.%d" % i]
+            y = torch.empty(n, H, W, co, dtype=torch.bfloat16, device=dev)
+            _conv(_desc(x0=x, c0=cp, batch=n, hi=H, wi=W, ho=H, wo=W, kh=3, kw=3, pad_h=1, pad_w=1, w=W_.w, k_pad=W_.k_pad,
+                        n=W_.n, bias=W_.bias, out=y, ldc=co, out_act=3, out_slope=0.0))                            # ReLU
+            x, cp = y, co
+            if i in c["pool_after"]:
+                y = torch.empty(n, H // 2, W // 2, co, dtype=torch.bfloat16, device=dev)
+                N.check(L_.ctta_maxpool2(N.ptr(x), N.ptr(y), n, H, W, co, s))
+                x, H, W = y, H // 2, W // 2
+        return x.view(n, H * W * cp)
+
+    def _embeddings(self, x, out, P):
+        """bf16 (n, 12288) -> the `embeddings` stack without its last ReLU: out (n, 128) fp32.  The two wide layers are 1x1
+        launches of the convolution family with ReLU; the last one runs in fp32, so the embedding is not rounded to bf16."""
+        c = self.cfg
+        L_ = N.lib()
+        s = N.stream_ptr()
+        n = x.shape[0]
+        for i, ci, co in c["linears"][:2]:
+            W_ = P["embeddings.%d" % i]
+            assert x.shape[1] == W_.k_pad, (tuple(x.shape), W_.k_pad)
+            y = torch.empty(n, co, dtype=torch.bfloat16, device=x.device)
+            _conv(_desc(x0=x, c0=W_.k_pad, batch=1, hi=n, wi=1, ho=n, wo=1, w=W_.w, k_pad=W_.k_pad, n=W_.n, bias=W_.bias, out=y,
+                        ldc=co, out_act=3, out_slope=0.0))
+            x = y
+        i, ci, co = c["linears"][2]
+        x32 = x.float()
+        w, b = self.get_parameter("embeddings.%d.weight" % i), self.get_parameter("embeddings.%d.bias" % i)
+        for r0 in range(0, n, 1024):                         # ctta_linear_f32 takes <= 1024 rows
+            r1 = min(n, r0 + 1024)
+            N.check(L_.ctta_linear_f32(N.ptr(x32[r0:r1]), N.ptr(w), N.ptr(b), N.ptr(out[r0:r1]), r1 - r0, co, ci, 0, 0, s))
+
+    def forward(self, wav):
+        """wav: (B, L) fp32 waveform at 16 kHz on the GPU -> (B * n_examples(L), 128) fp32 embeddings, clip-major rows
+        (what `model.forward(audio, sr)` of fad.py:76 returns per file, stacked)."""
+        if self.training:
+            raise N.CttaError("VGGish is built for evaluation only (fad.py:60 calls .eval())")
+        P = self._pack()
+        lm = self.logmel_examples(wav)
+        total = lm.shape[0]
+        out = torch.empty(total, self.cfg["embedding"], dtype=torch.float32, device=lm.device)
+        for e0 in range(0, total, self.MAX_EXAMPLES):
+            e1 = min(total, e0 + self.MAX_EXAMPLES)
+            self._embeddings(self._features(lm[e0:e1], P), out[e0:e1], P)
+        if self.use_activation:
+            out.clamp_(min=0)
+        return out
+
+
 # ------------------------------------------------------------------------------------------------ metrics
-def calculate_fid(featuresdict_1, featuresdict_2, feat_layer_name):
-    """metrics/fid.py:7-67: Frechet distance between the Gaussians fitted to two (N, D) feature sets."""
+def _frechet_distance(f1, f2, what, imag_error):
+    """Frechet distance between the Gaussians fitted to two (N, D) numpy feature sets: the stable form shared by
+    metrics/fid.py:20-65 and metrics/fad.py:81-144 (they differ in the exception an imaginary square root raises)."""
     eps = 1e-6
-    features_1, features_2 = featuresdict_1[feat_layer_name], featuresdict_2[feat_layer_name]
-    assert torch.is_tensor(features_1) and features_1.dim() == 2
-    assert torch.is_tensor(features_2) and features_2.dim() == 2
-    f1, f2 = features_1.cpu().numpy(), features_2.cpu().numpy()
     mu1, sigma1 = np.atleast_1d(np.mean(f1, axis=0)), np.atleast_2d(np.cov(f1, rowvar=False))
     mu2, sigma2 = np.atleast_1d(np.mean(f2, axis=0)), np.atleast_2d(np.cov(f2, rowvar=False))
     assert mu1.shape == mu2.shape, "Training and test mean vectors have different lengths"
@@ -189,15 +357,36 @@ def calculate_fid(featuresdict_1, featuresdict_2, feat_layer_name):
     diff = mu1 - mu2
     covmean, _ = scipy.linalg.sqrtm(sigma1.dot(sigma2), disp=False)        # the product might be almost singular
     if not np.isfinite(covmean).all():
-        print("WARNING: fid calculation produces singular product; adding %g to the covariance diagonal" % eps)
+        print("WARNING: %s calculation produces singular product; adding %g to the covariance diagonal" % (what, eps))
         offset = np.eye(sigma1.shape[0]) * eps
         covmean = scipy.linalg.sqrtm((sigma1 + offset).dot(sigma2 + offset))
     if np.iscomplexobj(covmean):                                           # numerical error: slight imaginary component
         if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
-            raise AssertionError("Imaginary component {}".format(np.max(np.abs(covmean.imag))))
+            raise imag_error("Imaginary component {}".format(np.max(np.abs(covmean.imag))))
         covmean = covmean.real
-    fid = diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
-    return {"frechet_distance": float(fid)}
+    return float(diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean))
+
+
+def calculate_fid(featuresdict_1, featuresdict_2, feat_layer_name):
+    """metrics/fid.py:7-67: Frechet distance between the Gaussians fitted to two (N, D) feature sets."""
+    features_1, features_2 = featuresdict_1[feat_layer_name], featuresdict_2[feat_layer_name]
+    assert torch.is_tensor(features_1) and features_1.dim() == 2
+    assert torch.is_tensor(features_2) and features_2.dim() == 2
+    return {"frechet_distance": _frechet_distance(features_1.cpu().numpy(), features_2.cpu().numpy(), "fid", AssertionError)}
+
+
+def calculate_fad(embds_gen, embds_gt):
+    """metrics/fad.py:146-168 behind the embeddings: (N, 128) VGGish embeddings of the generated and the ground-truth set
+    (tensors or arrays) -> {"frechet_audio_distance"}; -1 when a side is empty, like the reference."""
+    g = embds_gen.detach().cpu().numpy() if torch.is_tensor(embds_gen) else np.asarray(embds_gen)
+    t = embds_gt.detach().cpu().numpy() if torch.is_tensor(embds_gt) else np.asarray(embds_gt)
+    if len(g) == 0:
+        print("[Frechet Audio Distance] generated dir is empty, exitting...")
+        return -1
+    if len(t) == 0:
+        print("[Frechet Audio Distance] ground truth dir is empty, exitting...")
+        return -1
+    return {"frechet_audio_distance": _frechet_distance(g, t, "fad", ValueError)}
 
 
 def calculate_isc(featuresdict, feat_layer_name, rng_seed, samples_shuffle, splits):
@@ -321,6 +510,26 @@ def read_centered_wav(audio_file, target_sr):
     return audio - audio.mean()
 
 
+def load_audio_task(fname, target_sr=16000, target_length=1000):
+    """metrics/fad.py:22-36, the Frechet Audio Distance's own loader, with scipy.io.wavfile in place of soundfile: samples as
+    int16 / 32768, MEAN over the channels, integer-ratio decimation by plain striding, cut to `target_length` centiseconds;
+    the mean is NOT removed (unlike `read_centered_wav`: the two loaders differ in the reference too).  float64 array."""
+    from scipy.io import wavfile
+    orig_sr, audio = wavfile.read(fname)
+    if audio.dtype != np.int16:
+        raise N.CttaError("%s holds %s samples: only 16-bit PCM is read (the reference converts other widths with soundfile's "
+                          "dtype='int16' read, which is not rebuilt)" % (fname, audio.dtype))
+    audio = audio / 32768.0
+    if audio.ndim > 1:
+        audio = np.mean(audio, axis=1)
+    if orig_sr % target_sr == 0:
+        audio = audio[::(orig_sr // target_sr)]
+    else:
+        raise N.CttaError("%s: %d Hz is not an integer multiple of %d Hz; the reference resamples such files with resampy "
+                          "(kaiser_best), which is not rebuilt -- resample the directory first" % (fname, orig_sr, target_sr))
+    return audio[:int(target_length * target_sr / 100)]
+
+
 class WaveDataset:
     """datasets/load_mel.py:123-151: sorted .wav files of a directory -> (waveform (1, n) fp32, base name)."""
 
@@ -346,14 +555,16 @@ class WaveDataset:
 # ------------------------------------------------------------------------------------------------ driver
 class EvaluationHelper:
     """eval.py:58-349 for the metrics this build computes.  `clap_model`: a `consistencytta_amd.clap.CLAP_Module` (or None
-    to skip the three CLAP scores); the reference constructs one from `ckpt/music_audioset_epoch_15_esc_90.14.pt`."""
+    to skip the three CLAP scores); the reference constructs one from `ckpt/music_audioset_epoch_15_esc_90.14.pt`.
+    `vggish_model`: a `VGGish` holding the released torchvggish weights (or None to leave `frechet_audio_distance` NaN); the
+    reference downloads one through `torch.hub` (eval.py:65, metrics/fad.py:53)."""
 
     KEYS = ["frechet_distance", "frechet_audio_distance", "lsd", "psnr", "kullback_leibler_divergence_sigmoid",
             "kullback_leibler_divergence_softmax", "ssim", "ssim_stft", "inception_score_mean", "inception_score_std",
             "kernel_inception_distance_mean", "kernel_inception_distance_std", "gt_text_clap_score", "gen_text_clap_score",
             "gen_gt_clap_score"]
 
-    def __init__(self, sampling_rate, device, backbone="cnn14", mel_model=None, clap_model=None):
+    def __init__(self, sampling_rate, device, backbone="cnn14", mel_model=None, clap_model=None, vggish_model=None):
         self.device, self.backbone, self.sampling_rate = device, backbone, sampling_rate
         if sampling_rate not in (16000, 32000):
             raise ValueError("We only support the evaluation on 16kHz and 32kHz sampling rates.")
@@ -364,6 +575,7 @@ class EvaluationHelper:
                               classes_num=c["classes_num"]).to(device)
         self.mel_model = mel_model.eval()
         self.clap_model = clap_model
+        self.vggish_model = vggish_model.eval() if vggish_model is not None else None
 
     def file_init_check(self, dir):
         assert os.path.exists(dir), "The path does not exist %s" % dir
@@ -396,6 +608,38 @@ class EvaluationHelper:
         res["file_path_"] = [name for _, name in items]
         return res
 
+    def get_vggish_embeddings(self, datadir, target_length=1000):
+        """metrics/fad.py:62-79: the VGGish embeddings of every .wav file of a directory, loaded by `load_audio_task` at
+        16 kHz whatever the helper's own rate is (fad.py:62), stacked in file order -> (N, 128) CPU tensor.  Clips of equal
+        length go through the model together; a file too short for one 0.96 s example contributes no rows."""
+        from scipy.io import wavfile
+        m = self.vggish_model
+        paths = [os.path.join(datadir, f) for f in sorted(os.listdir(datadir)) if f.endswith(".wav")]
+        limit = int(target_length * 16000 / 100)
+
+        def length(path):                                    # samples `load_audio_task` will return, from the header alone
+            sr, data = wavfile.read(path, mmap=True)
+            return min(-(-data.shape[0] // (sr // 16000)), limit) if sr % 16000 == 0 else limit
+
+        lengths = [length(p) for p in paths]
+        order = sorted((i for i in range(len(paths)) if m.n_examples(lengths[i]) > 0), key=lambda i: lengths[i])
+        embds = {}
+        i = 0
+        with torch.no_grad():
+            while i < len(order):                            # one batch of files in host memory at a time
+                j = i
+                while j < len(order) and j - i < 32 and lengths[order[j]] == lengths[order[i]]:
+                    j += 1
+                waves = [torch.from_numpy(load_audio_task(paths[order[k]], 16000, target_length)).float() for k in range(i, j)]
+                out = m(torch.stack(waves).to(self.device)).cpu()
+                rows = out.shape[0] // (j - i)
+                for k in range(i, j):
+                    embds[order[k]] = out[(k - i) * rows:(k - i + 1) * rows]
+                i = j
+        if not embds:
+            return torch.zeros(0, m.cfg["embedding"])
+        return torch.cat([embds[i] for i in sorted(embds)])
+
     @staticmethod
     def captions_from_dataset_json(dataset_json_path):
         """{generated file name: caption} as `T2APairedDataset` pairs them (tools/t2a_dataset.py:79-87,118-119): line i of the
@@ -412,7 +656,8 @@ class EvaluationHelper:
         """eval.py:181-308 (same positional order) on two directories of identically named .wav files.  The captions of the
         CLAP scores come from `dataset_json_path` as in the reference (or from `captions`: {file name: text}); `mel_path`
         (pre-computed generated mels for the reference's optional mel metrics) is accepted and unused.  Returns the
-        reference's dictionary, rounded to 4 digits; metrics whose third-party model is not rebuilt are NaN."""
+        reference's dictionary, rounded to 4 digits; metrics whose third-party model is not rebuilt are NaN, and so is
+        `frechet_audio_distance` without a `vggish_model`."""
         if captions is None and dataset_json_path is not None:
             captions = self.captions_from_dataset_json(dataset_json_path)
         gen_files = sorted(f for f in os.listdir(generate_files_path) if f.endswith(".wav"))
@@ -426,6 +671,10 @@ class EvaluationHelper:
         featuresdict_2 = self.get_featuresdict(gt[i] for i in range(len(gt)))
         featuresdict_1 = self.get_featuresdict(gen[i] for i in range(len(gen)))
         out = {}
+        if self.vggish_model is not None:                    # eval.py:232-236 -> FrechetAudioDistance.score (fad.py:146-168)
+            fad = calculate_fad(self.get_vggish_embeddings(generate_files_path, target_length=target_length),
+                                self.get_vggish_embeddings(groundtruth_path, target_length=1000))
+            out.update(fad if isinstance(fad, dict) else {"frechet_audio_distance": float(fad)})
         if self.clap_model is not None and captions is not None:
             out.update(self.clap_scores([gt[i] for i in range(len(gt))], [gen[i] for i in range(len(gen))], captions))
         metric_kl, _, _ = calculate_kl(featuresdict_1, featuresdict_2, "logits", same_name)

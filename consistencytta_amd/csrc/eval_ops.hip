@@ -6,6 +6,8 @@
 //                          of conv_block1 with its single channel padded to 8
 //   ctta_avgpool2          F.avg_pool2d(kernel 2, stride 2; a trailing odd row / column is dropped) on NHWC bf16
 //   ctta_cnn14_head        torch.mean(x, dim=3) over frequency, then max + mean over time (models.py:305-309) -> fp32
+//   ctta_maxpool2          F.max_pool2d(kernel 2, stride 2) on NHWC bf16: the pooling of VGGish (torchvggish `VGG.features`, the
+//                          embedding model of metrics/fad.py)
 #include "common.h"
 
 __global__ __launch_bounds__(256) void logmel_to_image_kernel(const float* __restrict__ lm, const float* __restrict__ scale,
@@ -63,6 +65,44 @@ extern "C" ctta_status ctta_avgpool2(const void* x, void* y, int batch, int hi, 
   long long blocks = cdiv64(total, 256);
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y,
+                     batch, hi, wi, c);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+// the maximum of the four values themselves (no zero seed: a window of negative numbers keeps its largest); NaN propagates
+// like torch's
+__global__ __launch_bounds__(256) void maxpool2_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int B, int hi,
+                                                       int wi, int C) {
+  const int ho = hi / 2, wo = wi / 2, vc = C / 8;
+  const long long total = (long long)B * ho * wo * vc;
+  for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+    const int v = (int)(idx % vc);
+    long long p = idx / vc;
+    const int ox = (int)(p % wo); p /= wo;
+    const int oy = (int)(p % ho);
+    const int b = (int)(p / ho);
+    const bf16_t* src = x + ((((size_t)b * hi + 2 * oy) * wi) + 2 * ox) * C + v * 8;
+    float m[8];
+    unpack8(*reinterpret_cast<const uint4*>(src), m);
+#pragma unroll
+    for (int t = 1; t < 4; ++t) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(src + ((size_t)(t >> 1) * wi + (t & 1)) * C), f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) m[e] = (f[e] > m[e] || f[e] != f[e]) ? f[e] : m[e];
+    }
+    *reinterpret_cast<uint4*>(y + (size_t)idx * 8) = pack8(m);
+  }
+}
+
+extern "C" ctta_status ctta_maxpool2(const void* x, void* y, int batch, int hi, int wi, int c, void* stream) {
+  CTTA_REQUIRE(x && y && batch >= 1 && hi >= 2 && wi >= 2 && c >= 8 && c % 8 == 0,
+               "maxpool2: bad arguments (hi=%d wi=%d c=%d: the channel count must be a multiple of 8)", hi, wi, c);
+  const long long total = (long long)batch * (hi / 2) * (wi / 2) * (c / 8);
+  long long blocks = cdiv64(total, 256);
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y,
                      batch, hi, wi, c);
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;

@@ -27,6 +27,9 @@ struct ctta_mel_frontend {
   bf16_t* basis_t = nullptr;
   float* dframes = nullptr;
   int kpad = 0;
+  // VGGish mode (ctta_vggish_frontend_create): window of `win` samples zero-extended to the n_fft-point DFT, basis rows
+  // [n_rows][bk_pad] with only the first `win` columns live, no padding of the signal
+  int vggish = 0, win = 0, bk_pad = 0;
 };
 
 // clip to [-1, 1], nan_to_num, reflect-pad n_fft/2 on both sides, split into bf16 hi + lo
@@ -187,6 +190,7 @@ extern "C" ctta_status ctta_mel_frontend_create(int filter_length, int hop_lengt
 extern "C" ctta_status ctta_wav_to_fbank(ctta_mel_frontend* M, const float* wav, int batch, int n_samples,
                                          int target_length, float* fbank, float* logmag, void* stream) {
   CTTA_REQUIRE(M && wav && fbank, "wav_to_fbank: null pointer");
+  CTTA_REQUIRE(!M->vggish, "wav_to_fbank: the handle was built by ctta_vggish_frontend_create");
   CTTA_REQUIRE(batch >= 1 && batch <= M->max_batch && n_samples > M->n_fft / 2 && n_samples <= M->max_samples &&
                    target_length >= 1,
                "wav_to_fbank: batch %d / samples %d outside the handle's limits (%d, %d)", batch, n_samples, M->max_batch,
@@ -309,6 +313,7 @@ __global__ __launch_bounds__(256) void stft_overlap_add_kernel(const float* __re
 extern "C" ctta_status ctta_wav_to_logmel_db(ctta_mel_frontend* M, const float* wav, int batch, int n_samples, float amin,
                                              float* logmel, void* stream) {
   CTTA_REQUIRE(M && wav && logmel, "wav_to_logmel_db: null pointer");
+  CTTA_REQUIRE(!M->vggish, "wav_to_logmel_db: the handle was built by ctta_vggish_frontend_create");
   CTTA_REQUIRE(batch >= 1 && batch <= M->max_batch && n_samples > M->n_fft / 2 && n_samples <= M->max_samples,
                "wav_to_logmel_db: batch %d / samples %d outside the handle's limits (%d, %d)", batch, n_samples, M->max_batch,
                M->max_samples);
@@ -341,6 +346,7 @@ extern "C" ctta_status ctta_wav_to_logmel_db(ctta_mel_frontend* M, const float* 
 extern "C" ctta_status ctta_wav_to_logmel_db_bwd(ctta_mel_frontend* M, const float* dlogmel, int batch, int n_samples,
                                                  float amin, float* dwav, void* stream) {
   CTTA_REQUIRE(M && dlogmel && dwav, "wav_to_logmel_db_bwd: null pointer");
+  CTTA_REQUIRE(!M->vggish, "wav_to_logmel_db_bwd: the handle was built by ctta_vggish_frontend_create");
   CTTA_REQUIRE(batch >= 1 && batch <= M->max_batch && n_samples > M->n_fft / 2 && n_samples <= M->max_samples,
                "wav_to_logmel_db_bwd: batch %d / samples %d outside the handle's limits", batch, n_samples);
   hipStream_t s = (hipStream_t)stream;
@@ -371,6 +377,155 @@ extern "C" ctta_status ctta_wav_to_logmel_db_bwd(ctta_mel_frontend* M, const flo
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(stft_overlap_add_kernel, dim3(blocks, batch), dim3(256), 0, s, M->dframes, frames, N, M->hop, n_samples,
                      dwav);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------------------------
+// VGGish front end for the Frechet Audio Distance (audioldm_eval/metrics/fad.py:53 loads harritaylor/torchvggish, whose
+// input stage is TensorFlow models' vggish_input.waveform_to_examples / mel_features.py / vggish_params.py): 16 kHz mono,
+// frames of 400 samples at hop 160 taken from the signal as it is (no padding, no centring), periodic Hann, zero-extended
+// to a 512-point rfft, MAGNITUDE -> 64 HTK mel bands between 125 and 7500 Hz (triangles in the mel domain over the bin
+// centres, no area normalisation, DC row zero) -> ln(mel + 0.01); examples are 96 frames at hop 96, the incomplete tail
+// dropped.  The STFT is the split-bf16 GEMM above with 50 taps of 8 samples (K = 400 inside basis rows of 448 columns) and
+// only the frames that land in an example are computed.
+#define VGGISH_WIN 400
+#define VGGISH_HOP 160
+#define VGGISH_NFFT 512
+#define VGGISH_MELS 64
+#define VGGISH_EXAMPLE_FRAMES 96
+
+static int vggish_examples(int n_samples) {
+  if (n_samples < VGGISH_WIN) return 0;
+  return (1 + (n_samples - VGGISH_WIN) / VGGISH_HOP) / VGGISH_EXAMPLE_FRAMES;
+}
+
+// one block per frame: magnitude -> mel filterbank -> ln(x + 0.01)
+__global__ __launch_bounds__(256) void vggish_logmel_kernel(const float* __restrict__ ft, int frames, int n_rows, int cutoff,
+                                                            const float* __restrict__ mel_w, int n_mels,
+                                                            float* __restrict__ out) {
+  extern __shared__ float vmag[];
+  const int f = blockIdx.x, b = blockIdx.y;
+  const float* row = ft + ((size_t)b * frames + f) * n_rows;
+  for (int k = threadIdx.x; k < cutoff; k += 256) {
+    const float re = row[k], im = row[cutoff + k];
+    vmag[k] = sqrtf(re * re + im * im);
+  }
+  __syncthreads();
+  const int j = threadIdx.x >> 2, part = threadIdx.x & 3;
+  if (j < n_mels) {
+    const float* w = mel_w + (size_t)j * cutoff;
+    float acc = 0.f;
+    for (int k = part; k < cutoff; k += 4) acc += w[k] * vmag[k];
+    acc += __shfl_xor(acc, 1, 64);
+    acc += __shfl_xor(acc, 2, 64);
+    if (part == 0) out[((size_t)b * frames + f) * n_mels + j] = logf(acc + 0.01f);
+  }
+}
+
+extern "C" ctta_status ctta_vggish_frontend_create(int max_batch, int max_samples, ctta_mel_frontend** out) {
+  CTTA_REQUIRE(out && max_batch >= 1 && vggish_examples(max_samples) >= 1,
+               "vggish_frontend_create: max_batch %d / max_samples %d (one example needs 15600 samples)", max_batch, max_samples);
+  ctta_mel_frontend* M = new ctta_mel_frontend();
+  const int N = VGGISH_NFFT, cutoff = N / 2 + 1, win = VGGISH_WIN, n_mels = VGGISH_MELS;
+  M->vggish = 1; M->win = win; M->bk_pad = round_up(win, 64);
+  M->n_fft = N; M->hop = VGGISH_HOP; M->n_mels = n_mels; M->cutoff = cutoff; M->n_rows = round_up(2 * cutoff, 4);
+  M->max_batch = max_batch; M->max_samples = max_samples;
+  // basis row of bin k: w[n] exp(-2 pi i k n / 512) for n < 400 (the zero extension contributes nothing), evaluated in
+  // float64 like the numpy original and split into three bf16 parts
+  std::vector<bf16_t> parts[3];
+  for (auto& v : parts) v.assign((size_t)M->n_rows * M->bk_pad, 0);
+  auto to_bf16 = [](float v) {
+    uint32_t bits;
+    memcpy(&bits, &v, 4);
+    return (bf16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
+  };
+  auto from_bf16 = [](bf16_t h) {
+    const uint32_t hb = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &hb, 4);
+    return f;
+  };
+  for (int r = 0; r < 2 * cutoff; ++r) {
+    const int k = r < cutoff ? r : r - cutoff;
+    for (int n = 0; n < win; ++n) {
+      const double ang = 2.0 * M_PI * (double)(((long long)k * n) % N) / N;
+      const double hann = 0.5 - 0.5 * cos(2.0 * M_PI * n / win);
+      float rem = (float)((r < cutoff ? cos(ang) : -sin(ang)) * hann);
+      for (int part = 0; part < 3; ++part) {
+        const bf16_t h = to_bf16(rem);
+        parts[part][(size_t)r * M->bk_pad + n] = h;
+        rem -= from_bf16(h);
+      }
+    }
+  }
+  // mel_features.spectrogram_to_mel_matrix(64, 257, 16000, 125, 7500)
+  std::vector<float> w((size_t)n_mels * cutoff, 0.f);
+  {
+    auto hz_to_mel_htk = [](double f) { return 1127.0 * log(1.0 + f / 700.0); };
+    const double m_lo = hz_to_mel_htk(125.0), m_hi = hz_to_mel_htk(7500.0), nyquist = 8000.0;
+    std::vector<double> edges(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) edges[i] = i == n_mels + 1 ? m_hi : m_lo + i * ((m_hi - m_lo) / (n_mels + 1));
+    for (int k = 1; k < cutoff; ++k) {          // k = 0: the DC row stays zero
+      const double mel_bin = hz_to_mel_htk(k == cutoff - 1 ? nyquist : k * (nyquist / (cutoff - 1)));
+      for (int i = 0; i < n_mels; ++i) {
+        const double lower = (mel_bin - edges[i]) / (edges[i + 1] - edges[i]);
+        const double upper = (edges[i + 2] - mel_bin) / (edges[i + 2] - edges[i + 1]);
+        w[(size_t)i * cutoff + k] = (float)fmax(0.0, fmin(lower, upper));
+      }
+    }
+  }
+  const size_t lp = (size_t)round_up(max_samples, 8);
+  const size_t frames = (size_t)vggish_examples(max_samples) * VGGISH_EXAMPLE_FRAMES;
+  M->lp_max = lp; M->frames_max = frames;
+  bool ok = hipMalloc((void**)&M->mel_w, w.size() * 4) == hipSuccess &&
+            hipMalloc((void**)&M->ft, (size_t)max_batch * frames * M->n_rows * 4) == hipSuccess;
+  for (int part = 0; part < 3 && ok; ++part)
+    ok = hipMalloc((void**)&M->b[part], parts[part].size() * 2) == hipSuccess &&
+         hipMalloc((void**)&M->x[part], (size_t)max_batch * lp * 2) == hipSuccess &&
+         hipMemcpy(M->b[part], parts[part].data(), parts[part].size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) ok = hipMemcpy(M->mel_w, w.data(), w.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) ok = M->splitws.init() == CTTA_OK;
+  if (!ok) {
+    ctta_set_error("vggish_frontend_create: device allocation / upload failed");
+    ctta_mel_frontend_destroy(M);
+    return CTTA_ERR_NOMEM;
+  }
+  *out = M;
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_wav_to_vggish_logmel(ctta_mel_frontend* M, const float* wav, int batch, int n_samples, float* logmel,
+                                                 void* stream) {
+  CTTA_REQUIRE(M && wav && logmel, "wav_to_vggish_logmel: null pointer");
+  CTTA_REQUIRE(M->vggish, "wav_to_vggish_logmel: the handle was not built by ctta_vggish_frontend_create");
+  const int n_examples = vggish_examples(n_samples);
+  CTTA_REQUIRE(n_examples >= 1, "wav_to_vggish_logmel: %d samples hold no 96-frame example (15600 at least)", n_samples);
+  CTTA_REQUIRE(batch >= 1 && batch <= M->max_batch && n_samples <= M->max_samples,
+               "wav_to_vggish_logmel: batch %d / samples %d outside the handle's limits (%d, %d)", batch, n_samples, M->max_batch,
+               M->max_samples);
+  hipStream_t s = (hipStream_t)stream;
+  WsBind bind(M->splitws);
+  const int lp = round_up(n_samples, 8);
+  const int frames = n_examples * VGGISH_EXAMPLE_FRAMES;          // the last one ends at 160 (frames - 1) + 400 <= n_samples
+  // half = 0, clip = 0: the signal as it is, zeros up to the pixel boundary, split into the three bf16 parts
+  hipLaunchKernelGGL(mel_prepare_kernel, dim3((lp + 255) / 256 > 1024 ? 1024 : (lp + 255) / 256, batch), dim3(256), 0, s, wav,
+                     n_samples, lp, 0, M->x[0], M->x[1], M->x[2], 0);
+  CTTA_LAUNCH_CHECK();
+  const int xi[6] = {2, 1, 0, 1, 0, 0}, bj[6] = {0, 1, 2, 0, 1, 0};
+  for (int pass = 0; pass < 6; ++pass) {
+    ctta_conv_desc d;
+    desc_init(&d);
+    d.x0 = M->x[xi[pass]]; d.c0 = 8;
+    d.batch = batch; d.hi = 1; d.wi = lp / 8; d.ho = 1; d.wo = frames;
+    d.kh = 1; d.kw = M->win / 8; d.stride_w = M->hop / 8;
+    d.w = M->b[bj[pass]]; d.k_pad = M->bk_pad; d.n = M->n_rows;
+    d.out = M->ft; d.ldc = M->n_rows; d.out_f32 = 1; d.accumulate = pass > 0 ? 1 : 0;
+    CTTA_TRY(ctta_conv_gemm(&d, s));
+  }
+  hipLaunchKernelGGL(vggish_logmel_kernel, dim3(frames, batch), dim3(256), (size_t)M->cutoff * sizeof(float), s, M->ft, frames,
+                     M->n_rows, M->cutoff, M->mel_w, M->n_mels, logmel);
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }

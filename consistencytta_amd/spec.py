@@ -569,3 +569,37 @@ def clap_det_weight(name, shape, seed=0):
     if name.endswith("bn0.weight"):
         return (0.1 + 0.02 * det_uniform(name, shape, seed)).astype(np.float32)
     return det_weight(name, shape, seed)
+
+
+# ---------------------------------------------------------------------------------------------- Frechet Audio Distance
+# VGGish as audioldm_eval/metrics/fad.py:53 loads it (harritaylor/torchvggish `VGG`): 16 kHz audio, 96 x 64 log-mel patches
+VGGISH_CONFIG = dict(sample_rate=16000, window=400, hop=160, n_fft=512, mel_bins=64, fmin=125, fmax=7500, log_offset=0.01,
+                     example_frames=96, example_hop=96, embedding=128,
+                     convs=[(0, 1, 64), (3, 64, 128), (6, 128, 256), (8, 256, 256), (11, 256, 512), (13, 512, 512)],
+                     pool_after=(0, 3, 8, 13), linears=[(0, 12288, 4096), (2, 4096, 4096), (4, 4096, 128)])
+
+
+def vggish_param_spec():
+    """State-dict keys / shapes of the released `vggish-10086976.pth` in the module's registration order: the `features`
+    Sequential holds its six 3x3 convolutions at indices 0, 3, 6, 8, 11, 13 (ReLU and MaxPool entries have no parameters),
+    the `embeddings` Sequential its three Linear layers at 0, 2, 4.  A hub-built model also carries the `pproc.*` PCA tables
+    of the post-processor, which fad.py switches off; they are not part of the spec."""
+    sd = OrderedDict()
+    for i, cin, cout in VGGISH_CONFIG["convs"]:
+        sd["features.%d.weight" % i] = (cout, cin, 3, 3)
+        sd["features.%d.bias" % i] = (cout,)
+    for i, cin, cout in VGGISH_CONFIG["linears"]:
+        sd["embeddings.%d.weight" % i] = (cout, cin)
+        sd["embeddings.%d.bias" % i] = (cout,)
+    return sd
+
+
+def vggish_det_weight(name, shape, seed=0):
+    """Deterministic VGGish test weights (no checkpoint exists offline), by the Cnn14 rule: He-scaled matrices and
+    convolutions so that nine ReLU layers keep their activations O(1), small biases."""
+    shape = tuple(shape)
+    u = det_uniform(name, shape, seed)
+    if len(shape) == 1:
+        return (0.05 * u).astype(np.float32)
+    fan_in = int(np.prod(shape[1:]))
+    return (np.sqrt(6.0 / fan_in) * u).astype(np.float32)

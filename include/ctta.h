@@ -735,6 +735,24 @@ ctta_status ctta_logmel_to_image(const float* logmel, int batch, int frames, int
 ctta_status ctta_avgpool2(const void* x, void* y, int batch, int hi, int wi, int c, void* stream);
 ctta_status ctta_cnn14_head(const void* x, int batch, int frames, int freq, int c, float* y, void* stream);
 
+/* VGGish for the Frechet Audio Distance (audioldm_eval/metrics/fad.py:39-79; the model is harritaylor/torchvggish, its input
+ * stage TensorFlow models' vggish_input.py / mel_features.py / vggish_params.py):
+ *   ctta_vggish_frontend_create  a ctta_mel_frontend handle with the VGGish basis (periodic Hann of 400 samples, zero-extended
+ *                                512-point DFT) and mel matrix (64 HTK bands, 125-7500 Hz, no area norm, DC row zero) for up
+ *                                to max_batch clips of max_samples samples at 16 kHz; ctta_mel_frontend_destroy frees it, the
+ *                                other ctta_mel_frontend entries refuse it;
+ *   ctta_wav_to_vggish_logmel    wav (batch, n_samples) f32, taken as it is (no padding, clipping or NaN scrubbing) -> frames
+ *                                of 400 samples at hop 160 -> ln(|rfft| @ mel + 0.01) -> logmel f32
+ *                                [batch][n_examples * 96][64] = [batch * n_examples][96][64], n_examples =
+ *                                (1 + (n_samples - 400) / 160) / 96; only frames inside an example are computed;
+ *                                CTTA_ERR_INVALID below 15600 samples (no example);
+ *   ctta_maxpool2                F.max_pool2d(2, 2) (torchvggish `VGG.features`) on NHWC bf16 [batch][hi][wi][c] ->
+ *                                [batch][hi/2][wi/2][c], c % 8 == 0, a trailing odd row / column dropped as torch does. */
+ctta_status ctta_vggish_frontend_create(int max_batch, int max_samples, ctta_mel_frontend** out);
+ctta_status ctta_wav_to_vggish_logmel(ctta_mel_frontend* h, const float* wav, int batch, int n_samples, float* logmel,
+                                      void* stream);
+ctta_status ctta_maxpool2(const void* x, void* y, int batch, int hi, int wi, int c, void* stream);
+
 /* Small fp32 linear: y[m][n] = act_out(sum_k act_in(x[m][k]) * w[n][k] + b[n]); m <= 1024.
  * act: 0 none, 1 silu. */
 ctta_status ctta_linear_f32(const float* x, const float* w, const float* b, float* y, int m,
