@@ -254,6 +254,12 @@ SIGNATURES = {
     "ctta_vggish_frontend_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
     "ctta_wav_to_vggish_logmel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ctta_maxpool2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ctta_stft_create_dft": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "ctta_lsd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "ctta_ssim_tiles": (c_int64, [c_int, c_int, c_int]),
+    "ctta_ssim_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int, c_double, c_int, c_void_p,
+                               c_void_p, c_void_p]),
+    "ctta_psnr_mse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "ctta_reschain_supported": (c_int, [c_int, c_int, c_void_p]),
     "ctta_reschain_conv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_float, c_void_p, c_int, c_float, c_float, c_void_p]),

@@ -22,12 +22,25 @@ arithmetic on its features.
     kid,kl,fad}.py: same names, dictionary keys and random streams; `load_audio_task` is fad.py's own file loader.
   * `EvaluationHelper` -- audioldm_eval/eval.py:58-349: `get_featuresdict`, `calculate_metrics` on two directories of .wav
     files (or two lists of waveforms), the CLAP scores through `consistencytta_amd.clap.CLAP_Module`, the Frechet Audio
-    Distance through a `VGGish` passed as `vggish_model`.
+    Distance through a `VGGish` passed as `vggish_model`, the paired metrics with `paired_metrics=True`.
+  * `MelPairedDataset`, `calculate_lsd`, `calculate_psnr_ssim` -- datasets/load_mel.py:32-120 and eval.py:137-179: `lsd` /
+    `ssim_stft` / `psnr` / `ssim`, clip by clip between a generated file and the ground-truth file of the same name.  The
+    reference takes the arithmetic from two pip packages outside its tree, `ssr_eval.metrics.AudioMetrics` and
+    `skimage.metrics`; it is built here from the published definitions (restated in float64 numpy in
+    tests/paired_metrics_ref.py): |librosa.stft| at n_fft = int(2048 / (44100 / sr)) = 743 (16 kHz) or 1486 (32 kHz), hop
+    sr / 100, periodic Hann window, on ctta_stft_create_dft + ctta_stft_magnitude (split-bf16 GEMM); the log-spectral distance
+    on ctta_lsd; skimage's `structural_similarity` (uniform 7x7 window, K1 = 0.01, K2 = 0.03, sample covariance, mean over the
+    positions whose window lies inside the image) on ctta_ssim_mean with fp64 moments; the mean squared error under
+    `peak_signal_noise_ratio` on ctta_psnr_mse; the normalised mels from `TacotronSTFT.fbank`.  Pairs are batched through the
+    kernels in chunks.  Three choices depend on the versions of those packages and are constructor arguments of
+    `EvaluationHelper`: `stft_pad_mode="reflect"` (librosa 0.9, which ssr_eval was released against; "constant" is librosa
+    0.10), `stft_ssim_data_range=2.0` (skimage infers it from the float dtype of the spectrograms) and the frame count
+    1 + len // hop, which for the odd n_fft = 743 takes the last frame one sample past the centre padding.
 
-Not rebuilt, and reported as NaN exactly like a key the reference leaves out (eval.py:297-299 `out.get(key, nan)`): lsd /
-ssim_stft (`ssr_eval`, a pip dependency) and psnr / ssim (`skimage`); frechet_audio_distance is NaN too when no `vggish_model`
-is given.  Resampling of files whose rate is not an integer multiple of the target (`resampy`, load_mel.py:25-28,
-fad.py:33-34) is refused loudly.
+The four paired keys are computed only by a helper built with `paired_metrics=True`; otherwise they are reported as NaN, exactly
+like a key the reference leaves out (eval.py:297-299 `out.get(key, nan)`), and so is frechet_audio_distance when no
+`vggish_model` is given.  Resampling of files whose rate is not an integer multiple of the target (`resampy`,
+load_mel.py:25-28, fad.py:33-34) is refused loudly.
 """
 import os
 from collections import OrderedDict
@@ -38,11 +51,12 @@ import torch
 
 from . import _native as N
 from . import spec
+from .audio import TacotronSTFT
 from .clap import PackedLinear, _check_cuda, _conv, _desc
 from .modules import _ParamTree
 
 __all__ = ["Cnn14", "VGGish", "EvaluationHelper", "calculate_fid", "calculate_isc", "calculate_kid", "calculate_kl",
-           "calculate_fad", "read_centered_wav", "pad_short_audio", "load_audio_task"]
+           "calculate_fad", "read_centered_wav", "pad_short_audio", "load_audio_task", "MelPairedDataset", "WaveDataset"]
 
 
 # ------------------------------------------------------------------------------------------------ classifier
@@ -552,19 +566,149 @@ class WaveDataset:
         return audio, os.path.basename(filename)
 
 
+def _normalised_mels(stft, audios):
+    """datasets/load_mel.py:100-120 for a list of float64 waveforms: clip to [-1, 1], `stft.fbank` (the natural log of the
+    clamped mel magnitudes) -> log10 -> clip((20 x - 20 + 100) / 100, 0, 1).  Clips of equal length share a launch.  Returns
+    one (n_mels, frames) fp32 GPU tensor per waveform (a transposed view of the front end's (frames, n_mels) rows)."""
+    out = [None] * len(audios)
+    order = sorted(range(len(audios)), key=lambda i: len(audios[i]))
+    i = 0
+    while i < len(order):
+        n = len(audios[order[i]])
+        j = i
+        while j < len(order) and j - i < 32 and len(audios[order[j]]) == n:
+            j += 1
+        wav = torch.from_numpy(np.stack([audios[order[k]] for k in range(i, j)])).float().clip(-1, 1)
+        fb, _ = stft.fbank(wav, want_logmag=False)
+        mel = fb / float(np.log(10.0))                       # normalize_fun=torch.log10 on the same clamp(m, 1e-5)
+        mel = (((mel * 20) - 20) + 100) / 100
+        mel = torch.clip(mel, min=0, max=1.0)
+        for k in range(i, j):
+            out[order[k]] = mel[k - i].t()
+        i = j
+    return out
+
+
+class MelPairedDataset:
+    """datasets/load_mel.py:32-120: the .wav files two directories have in common, by base name (sorted; the reference
+    iterates a set) -> (generated mel, ground-truth mel, base name, (generated audio, ground-truth audio)).  The mels are the
+    normalised (n_mels, frames) float32 arrays of `get_mel_from_wav`, cut to the shorter of the two; the audio is what
+    `read_centered_wav` returns, whole.  `_stft`: a `TacotronSTFT` on the GPU (None: no mels).  `fbin_mean`, `fbin_std` and
+    `augment` are accepted and unused, as in the reference.  `EvaluationHelper` reads the audio through `audio_pair` and
+    batches the mels itself instead of indexing pair by pair."""
+
+    def __init__(self, datadir1, datadir2, _stft, sr=16000, fbin_mean=None, fbin_std=None, augment=False, limit_num=None):
+        lists = []
+        for d in (datadir1, datadir2):
+            files = [x for x in sorted(os.path.join(d, x) for x in os.listdir(d)) if x.endswith(".wav")]
+            lists.append(files[:limit_num] if limit_num is not None else files)
+        d1, d2 = ({os.path.basename(x): x for x in files} for files in lists)
+        keys = sorted(set(d1) & set(d2))
+        self.datalist1, self.datalist2 = [d1[k] for k in keys], [d2[k] for k in keys]
+        self._stft, self.sr, self.augment = _stft, sr, augment
+
+    def __len__(self):
+        return len(self.datalist1)
+
+    def name(self, index):
+        return os.path.basename(self.datalist1[index])
+
+    def audio_pair(self, index):
+        return read_centered_wav(self.datalist1[index], self.sr), read_centered_wav(self.datalist2[index], self.sr)
+
+    def get_mel_from_wav(self, audio):
+        return _normalised_mels(self._stft, [np.asarray(audio, dtype=np.float64)])[0].cpu().numpy(), None
+
+    def get_mel_from_file(self, audio_file):
+        audio = read_centered_wav(audio_file, self.sr)
+        melspec, energy = self.get_mel_from_wav(audio) if self._stft is not None else (None, None)
+        return melspec, energy, audio
+
+    def __getitem__(self, index):
+        mel1, _, audio1 = self.get_mel_from_file(self.datalist1[index])
+        mel2, _, audio2 = self.get_mel_from_file(self.datalist2[index])
+        if mel1 is not None:
+            min_len = min(mel1.shape[-1], mel2.shape[-1])
+            mel1, mel2 = mel1[..., :min_len], mel2[..., :min_len]
+        return mel1, mel2, self.name(index), (audio1, audio2)
+
+
+class _DftMagnitude:
+    """|librosa.stft(x, n_fft, hop, window="hann", center=True, pad_mode)| on a ctta_stft_create_dft handle, which grows with
+    the largest batch and the longest clip it has seen."""
+
+    def __init__(self, n_fft, hop, pad_mode):
+        if pad_mode not in ("reflect", "constant"):
+            raise ValueError("stft_pad_mode must be 'reflect' (librosa 0.9) or 'constant' (librosa 0.10), got %r" % (pad_mode,))
+        self.n_fft, self.hop, self.pad_zero = int(n_fft), int(hop), int(pad_mode == "constant")
+        self._h = self._key = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _release(self):
+        if self._h is not None:
+            N.lib().ctta_stft_destroy(self._h)
+            self._h = self._key = None
+
+    def __call__(self, wav):
+        """(B, n) fp32 on the GPU -> (B, 1 + n // hop, 1 + n_fft // 2) fp32."""
+        _check_cuda(wav, "waveform")
+        B, n = wav.shape
+        key = self._key
+        if self._h is None or B > key[0] or n > key[1] or key[2] != wav.device:
+            Bm, nm = (max(B, key[0]), max(n, key[1])) if key and key[2] == wav.device else (B, n)
+            self._release()
+            h = N.c_void_p()
+            with torch.cuda.device(wav.device):
+                N.check(N.lib().ctta_stft_create_dft(self.n_fft, self.hop, self.pad_zero, Bm, nm, h))
+            self._h, self._key = h, (Bm, nm, wav.device)
+        mag = torch.empty(B, n // self.hop + 1, self.n_fft // 2 + 1, dtype=torch.float32, device=wav.device)
+        with torch.cuda.device(wav.device):
+            N.check(N.lib().ctta_stft_magnitude(self._h, N.ptr(wav), B, n, N.ptr(mag), N.stream_ptr()))
+        return mag
+
+
+def _lengths(values):
+    return (N.c_int32 * len(values))(*values)
+
+
+def _ssim_mean(x, y, rows, win, data_range):
+    """ctta_ssim_mean on two (P, h_max, w) fp32 GPU tensors with `rows[p]` valid rows -> P float64 numbers on the host."""
+    P, h_max, w = x.shape
+    L_ = N.lib()
+    out = torch.empty(P, dtype=torch.float64, device=x.device)
+    ws = torch.empty(P * max(1, L_.ctta_ssim_tiles(h_max, w, win)), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        N.check(L_.ctta_ssim_mean(N.ptr(x), N.ptr(y), P, h_max, w, _lengths(rows), win, float(data_range), 1, N.ptr(out),
+                                  N.ptr(ws), N.stream_ptr()))
+    return out.cpu().numpy()
+
+
 # ------------------------------------------------------------------------------------------------ driver
 class EvaluationHelper:
     """eval.py:58-349 for the metrics this build computes.  `clap_model`: a `consistencytta_amd.clap.CLAP_Module` (or None
     to skip the three CLAP scores); the reference constructs one from `ckpt/music_audioset_epoch_15_esc_90.14.pt`.
     `vggish_model`: a `VGGish` holding the released torchvggish weights (or None to leave `frechet_audio_distance` NaN); the
-    reference downloads one through `torch.hub` (eval.py:65, metrics/fad.py:53)."""
+    reference downloads one through `torch.hub` (eval.py:65, metrics/fad.py:53).  `paired_metrics=True` computes `lsd`,
+    `ssim_stft`, `psnr` and `ssim` (eval.py:137-179) on the HIP path; the default leaves them NaN.  Their version-dependent
+    choices: `stft_pad_mode` -- the centre padding of the LSD's |librosa.stft|, "reflect" (librosa 0.9, which `ssr_eval` was
+    released against) or "constant" (librosa 0.10); `stft_ssim_data_range` -- the data range of `ssim_stft`, 2.0 being what
+    skimage infers for a float image."""
 
     KEYS = ["frechet_distance", "frechet_audio_distance", "lsd", "psnr", "kullback_leibler_divergence_sigmoid",
             "kullback_leibler_divergence_softmax", "ssim", "ssim_stft", "inception_score_mean", "inception_score_std",
             "kernel_inception_distance_mean", "kernel_inception_distance_std", "gt_text_clap_score", "gen_text_clap_score",
             "gen_gt_clap_score"]
 
-    def __init__(self, sampling_rate, device, backbone="cnn14", mel_model=None, clap_model=None, vggish_model=None):
+    PAIR_CHUNK = 32         # pairs per pass of the paired metrics: 64 clips through the STFT (0.5 GB of frames at 10 s, 16 kHz)
+    SSIM_WIN = 7            # skimage's default win_size
+
+    def __init__(self, sampling_rate, device, backbone="cnn14", mel_model=None, clap_model=None, vggish_model=None,
+                 paired_metrics=False, stft_pad_mode="reflect", stft_ssim_data_range=2.0):
         self.device, self.backbone, self.sampling_rate = device, backbone, sampling_rate
         if sampling_rate not in (16000, 32000):
             raise ValueError("We only support the evaluation on 16kHz and 32kHz sampling rates.")
@@ -576,6 +720,13 @@ class EvaluationHelper:
         self.mel_model = mel_model.eval()
         self.clap_model = clap_model
         self.vggish_model = vggish_model.eval() if vggish_model is not None else None
+        self.paired_metrics = bool(paired_metrics)
+        self.stft_pad_mode, self.stft_ssim_data_range = stft_pad_mode, float(stft_ssim_data_range)
+        if self.stft_ssim_data_range <= 0.0:
+            raise ValueError("stft_ssim_data_range must be positive, got %r" % (stft_ssim_data_range,))
+        # AudioMetrics(rate) of ssr_eval: n_fft = int(2048 / (44100 / rate)), hop = int(rate / 100) (eval.py:66)
+        self._lsd_stft = _DftMagnitude(int(2048 / (44100 / sampling_rate)), int(sampling_rate / 100), stft_pad_mode)
+        self._stft = None       # eval.py:89-98, built with the first paired pass
 
     def file_init_check(self, dir):
         assert os.path.exists(dir), "The path does not exist %s" % dir
@@ -656,8 +807,8 @@ class EvaluationHelper:
         """eval.py:181-308 (same positional order) on two directories of identically named .wav files.  The captions of the
         CLAP scores come from `dataset_json_path` as in the reference (or from `captions`: {file name: text}); `mel_path`
         (pre-computed generated mels for the reference's optional mel metrics) is accepted and unused.  Returns the
-        reference's dictionary, rounded to 4 digits; metrics whose third-party model is not rebuilt are NaN, and so is
-        `frechet_audio_distance` without a `vggish_model`."""
+        reference's dictionary, rounded to 4 digits; `lsd` / `ssim_stft` / `psnr` / `ssim` are NaN unless the helper was built
+        with `paired_metrics=True`, and so is `frechet_audio_distance` without a `vggish_model`."""
         if captions is None and dataset_json_path is not None:
             captions = self.captions_from_dataset_json(dataset_json_path)
         gen_files = sorted(f for f in os.listdir(generate_files_path) if f.endswith(".wav"))
@@ -683,7 +834,121 @@ class EvaluationHelper:
         out.update(calculate_kid(featuresdict_1, featuresdict_2, feat_layer_name="2048", degree=3, gamma=None, subsets=100,
                                  subset_size=len(gen) if subset_size is None else subset_size, coef0=1, rng_seed=2020))
         out.update(calculate_fid(featuresdict_1, featuresdict_2, feat_layer_name="2048"))
+        if self.paired_metrics:                              # eval.py:222-228,238-240,259-263
+            paired = MelPairedDataset(generate_files_path, groundtruth_path, self.mel_stft(), sr, limit_num=limit_num)
+            out.update(self.calculate_lsd(paired, same_name=same_name))
+            out.update(self.calculate_psnr_ssim(paired, same_name=same_name))
         return {key: round(out.get(key, float("nan")), 4) for key in self.KEYS}
+
+    def mel_stft(self):
+        """The `TacotronSTFT` of eval.py:89-98 on the helper's device."""
+        if self._stft is None:
+            c = {16000: (512, 160, 512, 64, 16000, 50, 8000), 32000: (1024, 320, 1024, 64, 32000, 50, 14000)}[self.sampling_rate]
+            self._stft = TacotronSTFT(*c).to(self.device)
+        return self._stft
+
+    def _pair_chunks(self, pairs, want_mel):
+        """Lists of at most PAIR_CHUNK (generated mel, ground-truth mel, name, (generated audio, ground-truth audio)) items.
+        A `MelPairedDataset` is read through `audio_pair` and its mels come from one batched front-end pass per chunk (GPU
+        tensors); any other iterable of such tuples (a DataLoader over the dataset, as in the reference) is taken as it is."""
+        if isinstance(pairs, MelPairedDataset):
+            for i0 in range(0, len(pairs), self.PAIR_CHUNK):
+                idx = list(range(i0, min(len(pairs), i0 + self.PAIR_CHUNK)))
+                audio = [pairs.audio_pair(i) for i in idx]
+                m1 = m2 = [None] * len(idx)
+                if want_mel:
+                    stft = pairs._stft if pairs._stft is not None else self.mel_stft()
+                    m1 = _normalised_mels(stft, [a for a, _ in audio])
+                    m2 = _normalised_mels(stft, [a for _, a in audio])
+                yield [(m1[k], m2[k], pairs.name(i), audio[k]) for k, i in enumerate(idx)]
+            return
+        buf = []
+        for item in pairs:
+            buf.append(item)
+            if len(buf) == self.PAIR_CHUNK:
+                yield buf
+                buf = []
+        if buf:
+            yield buf
+
+    def calculate_lsd(self, pairs, same_name=True, time_offset=160 * 7):
+        """eval.py:137-162 -> {"lsd", "ssim_stft"}, the means over all pairs of `AudioMetrics.lsd` and `AudioMetrics.ssim` on
+        the magnitude spectrograms.  Per pair (float64 on the host, as the reference): the generated audio from `time_offset`
+        on, (a - mean) / max|a| on both sides with the maximum taken before the mean is removed, both cut to the shorter.  The
+        pairs of a chunk that share a length go through the STFT, ctta_lsd and ctta_ssim_mean together."""
+        if not same_name:
+            return {"lsd": -1, "ssim_stft": -1}
+        lsd_avg, ssim_avg = [], []
+        hop = self._lsd_stft.hop
+        for chunk in self._pair_chunks(pairs, want_mel=False):
+            by_len = {}
+            for _, _, name, (a1, a2) in chunk:
+                a1, a2 = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (a1, a2))
+                if a1.shape[0] <= time_offset:
+                    raise ValueError("%s: %d generated samples, not more than the time offset of %d" % (name, a1.shape[0], time_offset))
+                a1 = a1[time_offset:]
+                a1 = (a1 - a1.mean()) / np.abs(a1).max()
+                a2 = (a2 - a2.mean()) / np.abs(a2).max()
+                n = min(a1.shape[0], a2.shape[0])
+                if 1 + n // hop < self.SSIM_WIN:
+                    raise ValueError("%s: %d samples are %d frames, fewer than one %dx%d window of ssim_stft"
+                                     % (name, n, 1 + n // hop, self.SSIM_WIN, self.SSIM_WIN))
+                by_len.setdefault(n, []).append((a1[:n], a2[:n]))
+            for n, group in sorted(by_len.items()):
+                P = len(group)
+                wav = torch.from_numpy(np.stack([a for a, _ in group] + [a for _, a in group])).float().to(self.device)
+                mag = self._lsd_stft(wav)                    # (2 P, frames, bins): generated first, ground truth behind
+                frames, bins = mag.shape[1], mag.shape[2]
+                out = torch.empty(P, dtype=torch.float64, device=mag.device)
+                ws = torch.empty(P * frames, dtype=torch.float64, device=mag.device)
+                with torch.cuda.device(mag.device):
+                    N.check(N.lib().ctta_lsd(N.ptr(mag[:P]), N.ptr(mag[P:]), P, frames, bins, _lengths([frames] * P), N.ptr(out),
+                                             N.ptr(ws), N.stream_ptr()))
+                lsd_avg += out.cpu().tolist()
+                ssim_avg += _ssim_mean(mag[:P], mag[P:], [frames] * P, self.SSIM_WIN, self.stft_ssim_data_range).tolist()
+        return {"lsd": float(np.mean(lsd_avg)), "ssim_stft": float(np.mean(ssim_avg))}
+
+    def calculate_psnr_ssim(self, pairs, same_name=True):
+        """eval.py:164-179 -> {"psnr", "ssim"}: skimage's `peak_signal_noise_ratio` (data range 1, inferred for a non-negative
+        float image) and `structural_similarity(data_range=1.)` of the normalised mels, the means over the pairs whose PSNR is
+        finite: a pair of identical mels is left out of both, as in the reference.  The mels of a chunk are padded to its
+        longest pair and go through ctta_psnr_mse and ctta_ssim_mean together, as (frames, n_mels) images: both metrics are
+        the same on a transposed image."""
+        if not same_name:
+            return {"psnr": -1, "ssim": -1}
+        psnr_avg, ssim_avg = [], []
+        win = self.SSIM_WIN
+        for chunk in self._pair_chunks(pairs, want_mel=True):
+            imgs, rows, names = [], [], []
+            for m1, m2, name, _ in chunk:
+                m1, m2 = (torch.as_tensor(m).float() for m in (m1, m2))
+                m1, m2 = (m.reshape(m.shape[-2], m.shape[-1]).t().to(self.device) for m in (m1, m2))      # (frames, n_mels)
+                if m1.shape[1] != m2.shape[1]:
+                    raise ValueError("%s: mels of %d and %d bands" % (name, m1.shape[1], m2.shape[1]))
+                h = min(m1.shape[0], m2.shape[0])
+                if h < win or m1.shape[1] < win:
+                    raise ValueError("%s: a mel of %d frames x %d bands holds no %dx%d window" % (name, h, m1.shape[1], win, win))
+                imgs.append((m1, m2))
+                rows.append(h)
+                names.append(name)
+            P, h_max, w = len(imgs), max(rows), imgs[0][0].shape[1]
+            x = torch.zeros(2, P, h_max, w, dtype=torch.float32, device=self.device)
+            for k, (m1, m2) in enumerate(imgs):
+                x[0, k, :rows[k]] = m1[:rows[k]]
+                x[1, k, :rows[k]] = m2[:rows[k]]
+            mse = torch.empty(P, dtype=torch.float64, device=self.device)
+            ws = torch.empty(P * h_max, dtype=torch.float64, device=self.device)
+            with torch.cuda.device(x.device):
+                N.check(N.lib().ctta_psnr_mse(N.ptr(x[0]), N.ptr(x[1]), P, h_max, w, _lengths(rows), N.ptr(mse), N.ptr(ws),
+                                              N.stream_ptr()))
+            ssim = _ssim_mean(x[0], x[1], rows, win, 1.0)
+            for k, err in enumerate(mse.cpu().tolist()):
+                if err == 0.0:
+                    print("Infinite value encountered in psnr %s " % names[k])
+                    continue
+                psnr_avg.append(10.0 * np.log10(1.0 / err))
+                ssim_avg.append(float(ssim[k]))
+        return {"psnr": float(np.mean(psnr_avg)), "ssim": float(np.mean(ssim_avg))}
 
     def _clap_wave(self, w, seconds=10.0):
         """What `T2APairedDataset` hands the CLAP tower (tools/t2a_dataset.py:111-125 -> tools/torch_tools.py:54-75): the clip at

@@ -18,6 +18,8 @@
 
 struct ctta_stft {
   int n_fft = 0, hop = 0, win = 0, cutoff = 0, n_rows = 0, kpad = 0;
+  int n_valid = 0, half = 0;   // samples of a frame that carry signal (n_fft; the DFT length of a _create_dft handle), centre padding
+  int pad_zero = 0, raw = 0;   // _create_dft handles: zero instead of reflect padding; no 1e-8 clamp and no backward
   int max_batch = 0, max_samples = 0;
   size_t frames_max = 0;
   bf16_t* b[3] = {nullptr, nullptr, nullptr};    // basis parts [n_rows][n_fft]
@@ -29,17 +31,21 @@ struct ctta_stft {
   SplitWs splitws;
 };
 
-// frames of the reflect-padded waveform, split into three bf16 parts
+// frames of the reflect-padded (pad_zero: zero-padded) waveform, split into three bf16 parts; columns from n_valid up to the
+// row stride N (the K padding of a DFT length that is no multiple of 64) are zero
 __global__ __launch_bounds__(256) void stft_frames_kernel(const float* __restrict__ wav, int T, int frames, int N, int hop,
-                                                          bf16_t* __restrict__ p0, bf16_t* __restrict__ p1,
-                                                          bf16_t* __restrict__ p2) {
-  const int f = blockIdx.x, b = blockIdx.y, half = N / 2;
+                                                          int n_valid, int half, int pad_zero, bf16_t* __restrict__ p0,
+                                                          bf16_t* __restrict__ p1, bf16_t* __restrict__ p2) {
+  const int f = blockIdx.x, b = blockIdx.y;
   const size_t row = ((size_t)b * frames + f) * N;
   for (int n = threadIdx.x; n < N; n += 256) {
     int j = f * hop + n - half;
-    if (j < 0) j = -j;
-    if (j >= T) j = 2 * (T - 1) - j;
-    const float v = wav[(size_t)b * T + j];
+    bool live = n < n_valid;
+    if (j < 0 || j >= T) {
+      if (pad_zero) live = false;
+      j = j < 0 ? -j : 2 * (T - 1) - j;
+    }
+    const float v = live ? wav[(size_t)b * T + j] : 0.f;
     const bf16_t h0 = f2bf(v);
     const float r1 = v - bf2f(h0);
     const bf16_t h1 = f2bf(r1);
@@ -50,13 +56,13 @@ __global__ __launch_bounds__(256) void stft_frames_kernel(const float* __restric
 }
 
 __global__ __launch_bounds__(256) void stft_mag_kernel(const float* __restrict__ ft, long long rows, int n_rows, int cutoff,
-                                                       float* __restrict__ mag) {
+                                                       float floor_pw, float* __restrict__ mag) {
   const long long total = rows * cutoff;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long r = i / cutoff;
     const int k = (int)(i - r * cutoff);
     const float re = ft[r * n_rows + k], im = ft[r * n_rows + cutoff + k];
-    mag[i] = sqrtf(fmaxf(re * re + im * im, 1e-8f));
+    mag[i] = sqrtf(fmaxf(re * re + im * im, floor_pw));
   }
 }
 
@@ -110,6 +116,56 @@ extern "C" void ctta_stft_destroy(ctta_stft* S) {
   delete S;
 }
 
+static bf16_t stft_to_bf16(float v) {
+  uint32_t bits;
+  memcpy(&bits, &v, 4);
+  return (bf16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
+}
+
+static float stft_from_bf16(bf16_t h) {
+  const uint32_t hb = (uint32_t)h << 16;
+  float f;
+  memcpy(&f, &hb, 4);
+  return f;
+}
+
+// basis rows [re block ; im block] of a DFT of length `n_dft` under a periodic Hann window of `win_length` samples placed
+// at column `left`, split into three bf16 parts with row stride S->n_fft; then the device buffers of the handle
+static ctta_status stft_finish_create(ctta_stft* S, int n_dft, int win_length, int left, const char* who, ctta_stft** out) {
+  const int N = S->n_fft, cutoff = S->cutoff;
+  std::vector<bf16_t> parts[3];
+  for (auto& v : parts) v.assign((size_t)S->n_rows * N, 0);
+  for (int r = 0; r < 2 * cutoff; ++r) {
+    const int k = r < cutoff ? r : r - cutoff;
+    for (int n = 0; n < n_dft; ++n) {
+      const int wn = n - left;
+      if (wn < 0 || wn >= win_length) continue;
+      const double win = 0.5 - 0.5 * cos(2.0 * M_PI * wn / win_length);   // torch.hann_window (periodic)
+      const double ang = 2.0 * M_PI * (double)(((long long)k * n) % n_dft) / n_dft;
+      float rem = (float)((r < cutoff ? cos(ang) : -sin(ang)) * win);
+      for (int part = 0; part < 3; ++part) {
+        const bf16_t h = stft_to_bf16(rem);
+        parts[part][(size_t)r * N + n] = h;
+        rem -= stft_from_bf16(h);
+      }
+    }
+  }
+  const size_t rows = (size_t)S->max_batch * S->frames_max;
+  bool ok = hipMalloc((void**)&S->ft, rows * S->n_rows * 4) == hipSuccess;
+  for (int part = 0; part < 3 && ok; ++part)
+    ok = hipMalloc((void**)&S->b[part], parts[part].size() * 2) == hipSuccess &&
+         hipMalloc((void**)&S->fr[part], rows * N * 2) == hipSuccess &&
+         hipMemcpy(S->b[part], parts[part].data(), parts[part].size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) ok = S->splitws.init() == CTTA_OK;
+  if (!ok) {
+    ctta_set_error("%s: device allocation / upload failed", who);
+    ctta_stft_destroy(S);
+    return CTTA_ERR_NOMEM;
+  }
+  *out = S;
+  return CTTA_OK;
+}
+
 extern "C" ctta_status ctta_stft_create(int fft_size, int hop_size, int win_length, int max_batch, int max_samples,
                                         ctta_stft** out) {
   CTTA_REQUIRE(out && fft_size >= 64 && fft_size % 64 == 0 && hop_size >= 1 && win_length >= 1 && win_length <= fft_size,
@@ -119,56 +175,37 @@ extern "C" ctta_status ctta_stft_create(int fft_size, int hop_size, int win_leng
   ctta_stft* S = new ctta_stft();
   const int N = fft_size, cutoff = N / 2 + 1;
   S->n_fft = N; S->hop = hop_size; S->win = win_length; S->cutoff = cutoff; S->n_rows = round_up(2 * cutoff, 4);
+  S->n_valid = N; S->half = N / 2;
   S->kpad = round_up(2 * cutoff, 64);
   S->max_batch = max_batch; S->max_samples = max_samples;
   S->frames_max = (size_t)max_samples / hop_size + 1;
-  std::vector<bf16_t> parts[3];
-  for (auto& v : parts) v.assign((size_t)S->n_rows * N, 0);
-  auto to_bf16 = [](float v) {
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    return (bf16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
-  };
-  auto from_bf16 = [](bf16_t h) {
-    const uint32_t hb = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &hb, 4);
-    return f;
-  };
-  const int left = (N - win_length) / 2;   // torch.stft centres a short window inside n_fft
-  for (int r = 0; r < 2 * cutoff; ++r) {
-    const int k = r < cutoff ? r : r - cutoff;
-    for (int n = 0; n < N; ++n) {
-      const int wn = n - left;
-      if (wn < 0 || wn >= win_length) continue;
-      const double win = 0.5 - 0.5 * cos(2.0 * M_PI * wn / win_length);   // torch.hann_window (periodic)
-      const double ang = 2.0 * M_PI * (double)(((long long)k * n) % N) / N;
-      float rem = (float)((r < cutoff ? cos(ang) : -sin(ang)) * win);
-      for (int part = 0; part < 3; ++part) {
-        const bf16_t h = to_bf16(rem);
-        parts[part][(size_t)r * N + n] = h;
-        rem -= from_bf16(h);
-      }
-    }
-  }
-  const size_t rows = (size_t)max_batch * S->frames_max;
-  bool ok = hipMalloc((void**)&S->ft, rows * S->n_rows * 4) == hipSuccess;
-  for (int part = 0; part < 3 && ok; ++part)
-    ok = hipMalloc((void**)&S->b[part], parts[part].size() * 2) == hipSuccess &&
-         hipMalloc((void**)&S->fr[part], rows * N * 2) == hipSuccess &&
-         hipMemcpy(S->b[part], parts[part].data(), parts[part].size() * 2, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) ok = S->splitws.init() == CTTA_OK;
-  if (!ok) {
-    ctta_set_error("stft_create: device allocation / upload failed");
-    ctta_stft_destroy(S);
-    return CTTA_ERR_NOMEM;
-  }
-  *out = S;
-  return CTTA_OK;
+  // torch.stft centres a short window inside n_fft
+  return stft_finish_create(S, N, win_length, (N - win_length) / 2, "stft_create", out);
+}
+
+// |librosa.stft(x, n_fft = n_dft, hop_length, window = periodic Hann of n_dft, center = True)| of
+// ssr_eval.metrics.AudioMetrics (behind audioldm_eval/eval.py:137-162): the frames hold n_dft samples followed by zeros up
+// to the GEMM's K multiple, the basis rows likewise (the VGGish front end's 400-in-512 layout), the bins are k / n_dft.
+// Frame f starts at f * hop - n_dft / 2 and there are n_samples / hop + 1 of them; for an odd n_dft the last one ends one
+// sample past the n_dft / 2 padding, which is continued by the same rule (the next reflected sample, or another zero).
+extern "C" ctta_status ctta_stft_create_dft(int n_dft, int hop_size, int pad_zero, int max_batch, int max_samples,
+                                            ctta_stft** out) {
+  CTTA_REQUIRE(out && n_dft >= 16 && n_dft <= 8192 && hop_size >= 1 && (pad_zero == 0 || pad_zero == 1),
+               "stft_create_dft: 16 <= n_dft=%d <= 8192, hop_size=%d >= 1, pad_zero=%d in {0, 1}", n_dft, hop_size, pad_zero);
+  CTTA_REQUIRE(max_batch >= 1 && max_samples > n_dft / 2 + (n_dft & 1), "stft_create_dft: bad sizes");
+  ctta_stft* S = new ctta_stft();
+  const int cutoff = n_dft / 2 + 1;
+  S->n_fft = round_up(n_dft, 64); S->hop = hop_size; S->win = n_dft; S->cutoff = cutoff; S->n_rows = round_up(2 * cutoff, 4);
+  S->n_valid = n_dft; S->half = n_dft / 2; S->pad_zero = pad_zero; S->raw = 1;
+  S->kpad = round_up(2 * cutoff, 64);
+  S->max_batch = max_batch; S->max_samples = max_samples;
+  S->frames_max = (size_t)max_samples / hop_size + 1;
+  return stft_finish_create(S, n_dft, n_dft, 0, "stft_create_dft", out);
 }
 
 static ctta_status stft_check(const ctta_stft* S, int batch, int n_samples, const char* who) {
-  CTTA_REQUIRE(batch >= 1 && batch <= S->max_batch && n_samples > S->n_fft / 2 && n_samples <= S->max_samples,
+  // the last frame of an odd DFT length reaches one sample past the centre padding (see ctta_stft_create_dft)
+  CTTA_REQUIRE(batch >= 1 && batch <= S->max_batch && n_samples > S->half + (S->n_valid & 1) && n_samples <= S->max_samples,
                "%s: batch %d / samples %d outside the handle's limits (%d, %d; at least n_fft / 2 + 1 samples for the reflect "
                "padding)", who, batch, n_samples, S->max_batch, S->max_samples);
   return CTTA_OK;
@@ -184,8 +221,8 @@ extern "C" ctta_status ctta_stft_magnitude(ctta_stft* S, const float* wav, int b
   WsBind bind(S->splitws);
   const int N = S->n_fft, frames = n_samples / S->hop + 1;
   const long long rows = (long long)batch * frames;
-  hipLaunchKernelGGL(stft_frames_kernel, dim3(frames, batch), dim3(256), 0, s, wav, n_samples, frames, N, S->hop, S->fr[0],
-                     S->fr[1], S->fr[2]);
+  hipLaunchKernelGGL(stft_frames_kernel, dim3(frames, batch), dim3(256), 0, s, wav, n_samples, frames, N, S->hop,
+                     S->n_valid, S->half, S->pad_zero, S->fr[0], S->fr[1], S->fr[2]);
   CTTA_LAUNCH_CHECK();
   const int xi[6] = {2, 1, 0, 1, 0, 0}, bj[6] = {0, 1, 2, 0, 1, 0};   // smallest products first
   for (int pass = 0; pass < 6; ++pass) {
@@ -200,7 +237,8 @@ extern "C" ctta_status ctta_stft_magnitude(ctta_stft* S, const float* wav, int b
   const long long total = rows * S->cutoff;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(stft_mag_kernel, dim3(blocks), dim3(256), 0, s, S->ft, rows, S->n_rows, S->cutoff, mag);
+  hipLaunchKernelGGL(stft_mag_kernel, dim3(blocks), dim3(256), 0, s, S->ft, rows, S->n_rows, S->cutoff,
+                     S->raw ? 0.f : 1e-8f, mag);
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }
@@ -209,6 +247,7 @@ extern "C" ctta_status ctta_stft_magnitude(ctta_stft* S, const float* wav, int b
 extern "C" ctta_status ctta_stft_magnitude_bwd(ctta_stft* S, const float* dmag, int batch, int n_samples, float* dwav,
                                                void* stream) {
   CTTA_REQUIRE(S && dmag && dwav, "stft_magnitude_bwd: null pointer");
+  CTTA_REQUIRE(!S->raw, "stft_magnitude_bwd: a ctta_stft_create_dft handle has no backward");
   CTTA_TRY(stft_check(S, batch, n_samples, "stft_magnitude_bwd"));
   hipStream_t s = (hipStream_t)stream;
   WsBind bind(S->splitws);

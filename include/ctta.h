@@ -753,6 +753,42 @@ ctta_status ctta_wav_to_vggish_logmel(ctta_mel_frontend* h, const float* wav, in
                                       void* stream);
 ctta_status ctta_maxpool2(const void* x, void* y, int batch, int hi, int wi, int c, void* stream);
 
+/* |librosa.stft(x, n_fft = n_dft, hop_length = hop_size, window = periodic Hann of n_dft samples, center = True)| as
+ * ssr_eval.metrics.AudioMetrics computes it for `lsd` and `ssim_stft` (behind audioldm_eval/eval.py:137-162; n_dft =
+ * int(2048 / (44100 / sr)) = 743 at 16 kHz, 1486 at 32 kHz).  ctta_stft_create requires fft_size % 64 == 0; this entry takes
+ * any 16 <= n_dft <= 8192, odd ones included: frames and basis rows hold n_dft samples followed by zeros up to the GEMM's K
+ * multiple (the layout of the VGGish front end's 400-in-512 basis), the bins are k / n_dft, n_dft / 2 + 1 of them.  Centre
+ * padding of n_dft / 2 samples on both sides, reflect (pad_zero = 0: librosa 0.9, which ssr_eval was released against) or
+ * zeros (pad_zero = 1: librosa 0.10); frames = n_samples / hop_size + 1; for an odd n_dft the last frame ends one sample past
+ * the padding, which is continued by the same rule.  The handle goes to ctta_stft_magnitude (same split-bf16 arithmetic,
+ * (batch, frames, n_dft / 2 + 1) output) and gives sqrt(re^2 + im^2) WITHOUT the loss path's 1e-8 clamp;
+ * ctta_stft_magnitude_bwd refuses it. */
+ctta_status ctta_stft_create_dft(int n_dft, int hop_size, int pad_zero, int max_batch, int max_samples, ctta_stft** out);
+
+/* Paired metrics of the evaluation suite (audioldm_eval/eval.py:137-179; ssr_eval and skimage are pip dependencies of the
+ * reference: built from the published definitions), batched over at most CTTA_PAIR_MAX pairs per call.  Inputs are fp32
+ * device tensors padded to the chunk's longest pair, the per-pair extents are HOST int32 arrays, outputs are fp64 device
+ * arrays [pairs].  All sums run in fp64 and in a fixed order (partials in the caller's device workspace `ws`, added by a
+ * second launch): the same inputs give the same bits.
+ *   ctta_lsd        eval.py:154,160-162 -> AudioMetrics.lsd on magnitude spectrograms est / tgt [pairs][frames_max][bins],
+ *                   frames[p] valid frames: mean_t sqrt(mean_f log10(tgt^2 / (est + 1e-12)^2 + 1e-12)^2); ws: pairs *
+ *                   frames_max doubles;
+ *   ctta_ssim_mean  eval.py:177 / AudioMetrics.ssim -> skimage.metrics.structural_similarity(x, y, win_size = win, data_range)
+ *                   on images [pairs][h_max][w] with h_valid[p] valid rows: uniform window, K1 = 0.01, K2 = 0.03, sample
+ *                   covariance (win^2 / (win^2 - 1)) when sample_covariance, mean over the positions whose whole window lies
+ *                   inside the image; win odd, 3..11; ws: pairs * ctta_ssim_tiles(h_max, w, win) doubles;
+ *   ctta_psnr_mse   eval.py:172 -> the mean of (x - y)^2 under skimage.metrics.peak_signal_noise_ratio (an exact 0 for identical
+ *                   images: the caller skips such a pair, eval.py:173-175); ws: pairs * h_max doubles.
+ * CTTA_ERR_INVALID for an image smaller than one window, a pair without frames, more than CTTA_PAIR_MAX pairs. */
+#define CTTA_PAIR_MAX 256
+ctta_status ctta_lsd(const float* est, const float* tgt, int pairs, int frames_max, int bins, const int32_t* frames, double* lsd,
+                     double* ws, void* stream);
+int64_t ctta_ssim_tiles(int h, int w, int win);
+ctta_status ctta_ssim_mean(const float* x, const float* y, int pairs, int h_max, int w, const int32_t* h_valid, int win,
+                           double data_range, int sample_covariance, double* ssim, double* ws, void* stream);
+ctta_status ctta_psnr_mse(const float* x, const float* y, int pairs, int h_max, int w, const int32_t* h_valid, double* mse,
+                          double* ws, void* stream);
+
 /* Small fp32 linear: y[m][n] = act_out(sum_k act_in(x[m][k]) * w[n][k] + b[n]); m <= 1024.
  * act: 0 none, 1 silu. */
 ctta_status ctta_linear_f32(const float* x, const float* w, const float* b, float* y, int m,
