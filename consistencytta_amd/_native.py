@@ -94,6 +94,22 @@ class ConvDesc(Structure):
     ]
 
 
+class ConvPlanEnv(Structure):
+    """ctta_conv_plan_env (include/ctta.h)"""
+    _fields_ = [("cu_count", c_int), ("xcd", c_int), ("splitk", c_int), ("streamk", c_int), ("streamk_grid", c_int),
+                ("suppress_splitk", c_int), ("stamps_bound", c_int), ("workspace_bytes", c_int64),
+                ("workspace_header_zeroed", c_int)]
+
+
+class ConvPlanInfo(Structure):
+    """ctta_conv_plan_info (include/ctta.h): all ints"""
+    _fields_ = [(n, c_int) for n in (
+        "variant", "kind", "halo", "prof_code", "grid_x", "grid_y", "grid_z", "splits", "nk", "nk_split",
+        "finish_blocks", "tail_rows", "tail_variant", "tail_grid_x", "tail_grid_y", "tail_nk",
+        "xcd_per", "m_tiles", "n_tiles", "n_inner", "slab_total", "slab_per", "sk_chunks", "sk_m_inner", "gn_nchunk",
+        "plain_out", "wide_store", "wide_f32", "splitk_wide_f32", "epi_fast", "epi_fast_geglu", "epi_act")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/ctta.h
 SIGNATURES = {
     "ctta_last_error": (c_char_p, []),
@@ -209,6 +225,7 @@ SIGNATURES = {
     "ctta_attention_debug_stamps": (None, [c_void_p]),
     "ctta_conv_gemm_num_variants": (c_int, []),
     "ctta_conv_gemm_variant_name": (c_char_p, [c_int]),
+    "ctta_conv_plan": (c_int, [POINTER(ConvDesc), POINTER(ConvPlanEnv), POINTER(ConvPlanInfo)]),
     "ctta_attention_fullbias": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ctta_attention_fullbias_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,

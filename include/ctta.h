@@ -446,6 +446,33 @@ void ctta_attention_debug_stamps(void* buf);
 size_t ctta_conv_workspace_bytes(void);
 int ctta_conv_gemm_num_variants(void);
 const char* ctta_conv_gemm_variant_name(int id);
+/* The PLAN of a ctta_conv_gemm call, without a device: which kernel the dispatch rules pick for descriptor `d` and how they
+ * schedule it, in an environment the caller describes.  ctta_conv_gemm launches from the same plan, built from the live
+ * process.  Pointers in `d` are only tested against NULL.  Returns the status, and leaves the ctta_last_error() text, that
+ * ctta_conv_gemm would give for the descriptor. */
+typedef struct {
+  int cu_count;                       /* compute units of the device */
+  int xcd, splitk, streamk, streamk_grid;   /* values of the options of these names (ctta_get_option) */
+  int suppress_splitk;                /* ctta_conv_suppress_splitk is on */
+  int stamps_bound;                   /* ctta_conv_debug_stamps has a buffer */
+  int64_t workspace_bytes;            /* the split-K workspace the launch would find (bound, or the per-device default); 0: none */
+  int workspace_header_zeroed;        /* ... and whether stream-K may use it (ctta_conv_bind_workspace_ex) */
+} ctta_conv_plan_env;
+typedef struct {
+  int variant, kind, halo;            /* tile id (0 with halo), its kind (2: stream-K), 1: the C = 32 conv1d halo kernel */
+  int prof_code;                      /* variant code of the launch's profiler record */
+  int grid_x, grid_y, grid_z;         /* grid of the (first) launch */
+  int splits, nk, nk_split;           /* two-pass split-K factor (1: none), K tiles, K tiles per split */
+  int finish_blocks;                  /* workgroups of the split-K second pass */
+  int tail_rows, tail_variant;        /* ragged last row tile cut off into a second launch: its rows and tile (0: none) */
+  int tail_grid_x, tail_grid_y, tail_nk;
+  int xcd_per, m_tiles, n_tiles, n_inner;   /* XCD-aware tile order */
+  int slab_total, slab_per;           /* weight-slab affinity */
+  int sk_chunks, sk_m_inner;          /* stream-K: XCD chunks, tile order */
+  int gn_nchunk;                      /* GroupNorm partial chunks per sample (0: the launch writes none) */
+  int plain_out, wide_store, wide_f32, splitk_wide_f32, epi_fast, epi_fast_geglu, epi_act;   /* epilogue flags */
+} ctta_conv_plan_info;
+ctta_status ctta_conv_plan(const ctta_conv_desc* d, const ctta_conv_plan_env* env, ctta_conv_plan_info* out);
 
 /* Fused HiFi-GAN ResBlock unit (hifigan/models.py:56-63) for C = 32 / 64 / 128 / 256 channels, odd k <= 11 (C = 512: k = 3 / 7 / 11):
  *   out = act( alpha * ( [old out +] x + conv2(leaky_relu(conv1(leaky_relu(x, slope)) + b1, slope)) + b2 ) )

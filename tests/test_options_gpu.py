@@ -212,3 +212,54 @@ def test_ffn_fuse_off_runs_the_two_launches_and_gives_the_same_bits(option):
     option("ffn_fuse", 1)
     assert n_off - n_on == 30, (n_on, n_off)
     assert torch.equal(a, b) and bool(torch.isfinite(a).all())
+
+
+def test_launches_run_the_variant_ctta_conv_plan_names(tmp_path):
+    """ctta_conv_plan, given this process (the device's CU count, the current options, the workspace a raw launch finds),
+    names the kernel ctta_conv_gemm launches: the variant code of the launch's profiler record is the plan's, for the small
+    conv shapes of the suite, an N <= 32 linear, a fused-GEGLU linear, an in_act conv and the C = 32 conv1d halo kernel."""
+    L = N.lib()
+    opts = N.options()
+    ws, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
+    L.ctta_conv_bound_workspace(ctypes.byref(ws), ctypes.byref(nbytes))
+    env = N.ConvPlanEnv(cu_count=torch.cuda.get_device_properties(0).multi_processor_count, xcd=opts["xcd"], splitk=opts["splitk"],
+                        streamk=opts["streamk"], streamk_grid=opts["streamk_grid"], suppress_splitk=0, stamps_bound=0,
+                        workspace_bytes=nbytes.value if ws.value else L.ctta_conv_workspace_bytes(),
+                        workspace_header_zeroed=L.ctta_conv_bound_workspace_header() if ws.value else 1)
+
+    def conv(B, Cin, H, W, Cout, kh=3, kw=3, n_out=None, **kw_):
+        x = torch.zeros(B, H, W, Cin, dtype=torch.bfloat16, device=DEV)
+        k_pad = (kh * kw * Cin + 63) // 64 * 64
+        w = torch.zeros(Cout, k_pad, dtype=torch.bfloat16, device=DEV)
+        out = torch.zeros(B, H, W, n_out or Cout, dtype=torch.bfloat16, device=DEV)
+        bias = torch.zeros(Cout, device=DEV)
+        return conv_desc(x0=x, c0=Cin, batch=B, hi=H, wi=W, ho=H, wo=W, kh=kh, kw=kw, pad_h=kh // 2, pad_w=kw // 2, w=w, k_pad=k_pad,
+                         n=Cout, bias=bias, out=out, ldc=n_out or Cout, **kw_), (x, w, out, bias)
+    shapes = {
+        "conv 2x64x24x16 -> 96": conv(2, 64, 24, 16, 96),
+        "conv 3x256x4x2 -> 256": conv(3, 256, 4, 2, 256),
+        "linear n = 32": conv(512, 256, 1, 1, 32, 1, 1),
+        "GEGLU linear n = 64": conv(512, 256, 1, 1, 64, 1, 1, n_out=32, out_act=4),
+        "in_act conv": conv(2, 64, 24, 16, 96, in_act=1, in_slope=0.1),
+        "conv1d halo C = 32": conv(2, 32, 1, 1000, 32, 1, 3),
+    }
+    N.check(L.ctta_prof_collect(0, None, None, None, None))      # (drops what earlier tests left in the log)
+    planned, launched = {}, {}
+    for name, (d, keep) in shapes.items():
+        info = N.ConvPlanInfo()
+        N.check(L.ctta_conv_plan(ctypes.byref(d), ctypes.byref(env), ctypes.byref(info)))
+        planned[name] = info.prof_code
+        csv = tmp_path / "launch.csv"
+        L.ctta_prof_enable(1)
+        try:
+            run_conv(d)
+        finally:
+            L.ctta_prof_enable(0)
+        N.check(L.ctta_prof_collect(0, None, None, None, str(csv).encode()))
+        rows = [r.split(",") for r in csv.read_text().split()]
+        csv.unlink()
+        assert len(rows) == 1, (name, rows)      # one record per ctta_conv_gemm
+        launched[name] = int(rows[0][1])
+        assert bool(torch.isfinite(keep[2].float()).all()), name
+    assert launched == planned
+    assert planned["conv1d halo C = 32"] == 39 and planned["in_act conv"] % 100 <= 8

@@ -4,7 +4,7 @@
     python tools/sweep_conv.py [out.json]
 
 Prints one line per shape with the TFLOP/s of each variant (executed FLOPs, random data) and
-writes the table as JSON; the result drives pick_variant() in csrc/conv_gemm.hip."""
+writes the table as JSON; the result drives pick_variant() in csrc/conv_plan.hip."""
 import ctypes
 import json
 import os
