@@ -101,6 +101,38 @@ __global__ void cfg_combine_kernel(const float4* __restrict__ u, const float4* _
   }
 }
 
+// One sampler step between two U-Net queries of the few-step consistency sampler (easy_inference/consistencytta.py:152-197)
+// in one pass:
+//   x0  = CFG ? (1 - w) * uncond + w * cond : cond           (the post-CFG combine, consistencytta.py:178-181)
+//   z   = x0 + noise * sigma                                 (add_noise, scheduling_heun_discrete.py:364-385)
+//   out = z / sqrt(sigma^2 + 1)                              (scale_model_input, :151-172)
+// written COPIES times, stacked along the batch (the 2B-row input of a CFG query).  Every element sees the fp32 operations
+// of torch's mul, mul, add, then heun_add_noise_kernel, then heun_scale_kernel, in their order and with the contractions
+// written out (this translation unit is built without fp contraction), so the result is bit-identical to that chain.
+template <bool CFG, int COPIES>
+__global__ void consistency_renoise_kernel(const float4* __restrict__ c, const float4* __restrict__ u,
+                                           const float* __restrict__ w, const float4* __restrict__ nz,
+                                           const float* __restrict__ sigma, float4* __restrict__ out, long long nvec_per,
+                                           long long total) {
+  VEC_LOOP(total) {
+    const int b = (int)(i / nvec_per);
+    const float s = sigma[b];
+    const float d = sqrtf(s * s + 1.0f);
+    float4 x0 = c[i];
+    if (CFG) {
+      const float ww = w[b];
+      const float a = 1.0f - ww;
+      const float4 uu = u[i];
+      x0 = make_float4(a * uu.x + ww * x0.x, a * uu.y + ww * x0.y, a * uu.z + ww * x0.z, a * uu.w + ww * x0.w);
+    }
+    const float4 n = nz[i];
+    float4 z = make_float4(x0.x + n.x * s, x0.y + n.y * s, x0.z + n.z * s, x0.w + n.w * s);
+    z.x /= d; z.y /= d; z.z /= d; z.w /= d;
+    out[i] = z;
+    if (COPIES == 2) out[total + i] = z;
+  }
+}
+
 // out = a[b]*x + b_[b]*y per sample (optionally clamped): DDPM/DDIM add_noise and the v-prediction step pieces
 __global__ void lincomb2_kernel(const float4* __restrict__ x, const float4* __restrict__ y, const float* __restrict__ a,
                                 const float* __restrict__ b_, float4* __restrict__ out, long long nvec_per, long long total,
@@ -457,6 +489,24 @@ extern "C" ctta_status ctta_cfg_combine(const float* uncond, const float* cond, 
   const long long nv = n_per_sample / 4, total = nv * batch;
   hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                      (const float4*)uncond, (const float4*)cond, w, (float4*)out, nv, total);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_consistency_renoise(const float* cond, const float* uncond, const float* w_post,
+                                                const float* noise, const float* sigma, float* out, int copies,
+                                                int batch, int64_t n_per_sample, void* stream) {
+  CTTA_REQUIRE(cond && noise && sigma && out && (!uncond || w_post), "consistency_renoise: null pointer");
+  REQ_VEC(n_per_sample);
+  CTTA_REQUIRE(copies == 1 || copies == 2, "consistency_renoise: copies=%d (1 or 2)", copies);
+  CTTA_REQUIRE(batch > 0 && n_per_sample > 0, "consistency_renoise: empty tensor");
+  const long long nv = n_per_sample / 4, total = nv * batch;
+#define RENOISE(CFG, CP)                                                                                             \
+  hipLaunchKernelGGL((consistency_renoise_kernel<CFG, CP>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, \
+                     (const float4*)cond, (const float4*)uncond, w_post, (const float4*)noise, sigma, (float4*)out, nv, total)
+  if (uncond) { if (copies == 2) RENOISE(true, 2); else RENOISE(true, 1); }
+  else        { if (copies == 2) RENOISE(false, 2); else RENOISE(false, 1); }
+#undef RENOISE
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }

@@ -36,6 +36,25 @@ def randn_tensor(shape, generator=None, device=None, dtype=None):
     return torch.randn(shape, generator=generator, device=device, dtype=dtype)
 
 
+def _check_step_noise(step_noise, count, noise):
+    """`step_noise=` of the few-step samplers: (count, *noise.shape), one re-noising draw per sampler step after the first
+    query.  Raises before anything is launched."""
+    if step_noise is None:
+        return
+    want = (int(count),) + tuple(noise.shape)
+    if not torch.is_tensor(step_noise) or tuple(step_noise.shape) != want:
+        got = tuple(step_noise.shape) if torch.is_tensor(step_noise) else type(step_noise).__name__
+        raise ValueError("step_noise %s: expected %s (one draw per re-noising step)" % (got, want))
+
+
+def _post_cfg_fusable(w):
+    """Whether the kernels' post-CFG combine (ctta_consistency_renoise, ctta_cfg_combine: a = 1 - w subtracted in fp32) gives
+    torch's `(1 - w) * u + w * c` bit for bit: torch rounds the Python double 1 - w to fp32, so the two coefficients are the
+    same number whenever 1 - w is exact in fp32 (every dyadic scale: 1.5, 2, 2.5, 3 ...).  Any other scale keeps torch's own
+    combine inside the captured sequence."""
+    return bool(np.float32(1.0 - float(w)) == np.float32(1.0) - np.float32(w))
+
+
 def optimizer_tail(source_model, shadow_models, decay_consts, optimizer, lr_scheduler, grad_scale, do_step):
     """The end of a training step, tools/train_utils.py:177-183: optimizer.step() (skipped on a NaN loss, :167-172) ->
     lr_scheduler.step() -> optimizer.zero_grad() -> update_ema().  With the fused AdamW on `source_model` and every network
@@ -635,9 +654,13 @@ class AudioLCM(AudioDistilledModel):
     @torch.no_grad()
     def inference(self, prompt, inference_scheduler, guidance_scale_input=3, guidance_scale_post=1, num_steps=20,
                   use_edm=False, num_samples=1, use_ema=True, query_teacher=False, num_teacher_steps=18,
-                  return_all=False, noise=None, graph_teacher=False):
+                  return_all=False, noise=None, graph_teacher=False, step_noise=None, graph_student=False):
         """`graph_teacher=True` runs the teacher loop as replays of ONE captured hipGraph (Heun: a full 2nd-order
         step = 2 CFG teacher queries; DDIM: one query + step); results are identical to the eager loop.
+        `step_noise`: the student's re-noising draws, (n, B, C, H, W) with one row per entry of the timesteps `[1::order]`
+        (n = num_steps - 1 when scheduler and `self.use_edm` agree); None draws them with `torch.randn_like`.
+        `graph_student=True` runs the student loop as `num_steps` replays of ONE captured hipGraph (a query, then the
+        post-CFG combine + re-noising + scaling that feeds the next one); identical to the eager loop on the same draws.
         `inference_scheduler` is a HeunDiscreteScheduler or a DDIMScheduler, chosen by the CALLER (inference.py:160,
         demo.py:94) whatever `self.use_edm` is; the re-noising stride still follows `self.use_edm` (:497-499)."""
         self.check_eval_mode()
@@ -656,6 +679,8 @@ class AudioLCM(AudioDistilledModel):
         C = self.student_target_unet.config.in_channels
         if noise is None:
             noise = randn_tensor((B, C, 256, 16), device=dev, dtype=torch.float32)
+        order = 2 if self.use_edm else 1
+        _check_step_noise(step_noise, len(range(1, 2 * num_steps - 1 if heun else num_steps, order)), noise)
         time_embed = time() - t0
         unet = self.student_ema_unet if use_ema else self.student_target_unet
 
@@ -672,12 +697,19 @@ class AudioLCM(AudioDistilledModel):
         t1 = time()
         sch.set_timesteps(18, device=dev)
         z_N = noise * sch.init_noise_sigma
-        zhat_0 = calc_zhat_0(z_N, host_timesteps()[0])
-        sch.set_timesteps(num_steps, device=dev)
-        order = 2 if self.use_edm else 1
-        for t in host_timesteps()[1::order]:
-            zhat_n = sch.add_noise(zhat_0, torch.randn_like(zhat_0), t)
-            zhat_0 = calc_zhat_0(zhat_n, t)
+        if graph_student:
+            t_first = host_timesteps()[0]
+            z_first = sch.scale_model_input(torch.cat([z_N] * 2) if use_cf else z_N, t_first)
+            sch.set_timesteps(num_steps, device=dev)
+            zhat_0 = self._student_loop_graphed(sch, unet, z_first, t_first, host_timesteps()[1::order], step_noise, enc_stu,
+                                                mask_stu, guidance_scale_input, guidance_scale_post)
+        else:
+            zhat_0 = calc_zhat_0(z_N, host_timesteps()[0])
+            sch.set_timesteps(num_steps, device=dev)
+            for k, t in enumerate(host_timesteps()[1::order]):
+                draw = torch.randn_like(zhat_0) if step_noise is None else step_noise[k]
+                zhat_n = sch.add_noise(zhat_0, draw, t)
+                zhat_0 = calc_zhat_0(zhat_n, t)
         time_stu = time() - t1
         zhat_tea, time_tea = None, None
         if query_teacher:
@@ -1020,6 +1052,91 @@ def _teacher_loop_graphed_ddim(self, sch, z, enc, mask, guidance_scale):
 
 
 AudioLCM._teacher_loop_graphed_ddim = _teacher_loop_graphed_ddim
+
+
+def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, enc, mask, w_in, w_post):
+    """The student loop of `inference` (audio_consistency_model.py:480-503) with its launch sequence captured once, the way
+    `_teacher_loop_graphed` does it: one graph = one student query (on 2B rows with post-CFG) followed by what turns its
+    output into the NEXT query's input -- post-CFG combine, add_noise, scale_model_input, the 2B-row stacking
+    (Heun: ONE launch, ctta_consistency_renoise; DDIM: the eager loop's own combine and ctta_lincomb2_rows, its scaling
+    is the identity).  Timesteps, sigmas / coefficients and the draws live in device tables indexed by a device-side
+    counter, so the loop is len(later) + 1 replays; the last replay's re-noising reads a dummy table row and its result is
+    dropped.  `z_first`: the scaled input of the first query; `later`: the timesteps of the re-noising steps."""
+    dev = z_first.device
+    use_cf = w_post > 1.
+    heun = hasattr(sch, "_timesteps_host")
+    rows = z_first.shape[0]
+    B = rows // 2 if use_cf else rows
+    n = z_first[0].numel()
+    K = len(later)
+    L_ = N.lib()
+    if step_noise is None:          # today's draws, in today's order
+        step_noise = [torch.randn_like(z_first[:B]) for _ in range(K)]
+        step_noise = torch.stack(step_noise) if K else None
+    nz = (step_noise.to(dev, torch.float32).contiguous() if K else torch.zeros((1, B) + tuple(z_first.shape[1:]), device=dev))
+    ts_dev = torch.tensor([t_first] + list(later), dtype=torch.float32, device=dev)
+    if heun:        # what add_noise / scale_model_input look up at each later timestep; the dummy row is sigma = 0
+        sig = [float(sch._sigmas_host[sch.index_for_timestep(t)][0]) for t in later] + [0.0]
+        tab = torch.tensor([sig], dtype=torch.float32, device=dev)                              # (1, K + 1)
+    else:           # DDIMScheduler.add_noise's coefficient pair; the dummy row is (1, 0)
+        cols = [sch.noise_coeffs(t, 1) for t in later] + [torch.tensor([[1.0], [0.0]])]
+        tab = torch.cat(cols, dim=1).to(dev)                                                    # (2, K + 1)
+    fused_cfg = use_cf and heun and _post_cfg_fusable(w_post)
+    w_dev = torch.full((B,), float(w_post), dtype=torch.float32, device=dev)
+    zin = z_first.clone().contiguous()
+    zh = torch.empty_like(zin)
+    idx = torch.zeros(1, dtype=torch.int64, device=dev)
+    first = [True]
+
+    def one():
+        t_b = ts_dev.index_select(0, idx).expand(rows).contiguous()
+        c = tab.index_select(1, idx).expand(tab.shape[0], B).contiguous()
+        draw = nz.index_select(0, idx.clamp(max=nz.shape[0] - 1))[0]
+        # the text states are the same tensors for the whole loop: only the very first query projects their K / V
+        out = unet(zin, t_b, guidance=w_in, encoder_hidden_states=enc, encoder_attention_mask=mask,
+                   reuse_text=not first[0]).sample
+        first[0] = False
+        zh.copy_(out)
+        if fused_cfg:
+            cond, unc = out[B:], out[:B]
+        elif use_cf:
+            cond, unc = (1 - w_post) * out[:B] + w_post * out[B:], None
+        else:
+            cond, unc = out, None
+        if heun:
+            N.check(L_.ctta_consistency_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
+                                                N.ptr(draw), N.ptr(c[0]), N.ptr(zin), 2 if use_cf else 1, B, n,
+                                                N.stream_ptr()))
+        else:
+            N.check(L_.ctta_lincomb2_rows(N.ptr(cond.contiguous()), N.ptr(draw), N.ptr(c[0]), N.ptr(c[1]), N.ptr(zin), B, n,
+                                          0.0, N.stream_ptr()))
+            if use_cf:
+                zin[B:].copy_(zin[:B])
+        idx.add_(1)
+
+    # one eager step on a side stream first (handles, kernel attributes, allocator pool, the text K / V), then rewind
+    # and capture
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        one()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    zin.copy_(z_first)
+    idx.zero_()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        one()
+    zin.copy_(z_first)
+    idx.zero_()
+    for _ in range(K + 1):
+        graph.replay()
+    unet._text_key = None       # the handle's text cache was last filled outside the module's own bookkeeping
+    if use_cf:
+        return (1 - w_post) * zh[:B] + w_post * zh[B:]
+    return zh.clone()
+
+
+AudioLCM._student_loop_graphed = _student_loop_graphed
 
 
 class _DistillStepGraph:
@@ -1617,10 +1734,13 @@ class ConsistencyTTA(nn.Module):
 
     @torch.no_grad()
     def generate_latent(self, encoder_states, encoder_mask, noise, cfg_scale_input=3., cfg_scale_post=1.,
-                        num_steps=1, uncond_states=None, uncond_mask=None):
-        """consistencytta.py:152-197 from pre-computed text states (T5 excluded)."""
+                        num_steps=1, uncond_states=None, uncond_mask=None, step_noise=None):
+        """consistencytta.py:152-197 from pre-computed text states (T5 excluded).  `step_noise`: the re-noising draws of
+        the few-step sampler, (num_steps - 1, B, C, H, W), one per entry of `_timesteps_host[1::2]`; None draws them with
+        `torch.randn_like` as the reference does."""
         sch = self.scheduler
         use_cf = cfg_scale_post > 1.
+        _check_step_noise(step_noise, int(num_steps) - 1, noise)
         if use_cf:
             encoder_states = torch.cat([uncond_states, encoder_states])
             encoder_mask = torch.cat([uncond_mask, encoder_mask])
@@ -1639,27 +1759,161 @@ class ConsistencyTTA(nn.Module):
 
         zhat_0 = calc(z_N, float(sch._timesteps_host[0]))
         sch.set_timesteps(num_steps, device=noise.device)
-        for t in sch._timesteps_host[1::2]:
-            zhat_n = sch.add_noise(zhat_0, torch.randn_like(zhat_0), float(t))
+        for k, t in enumerate(sch._timesteps_host[1::2]):
+            draw = torch.randn_like(zhat_0) if step_noise is None else step_noise[k]
+            zhat_n = sch.add_noise(zhat_0, draw, float(t))
             zhat_0 = calc(zhat_n, float(t))
         return zhat_0
 
+    def _generate_latent_static(self, encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps,
+                                uncond_states=None, uncond_mask=None):
+        """`generate_latent` in the form the captured paths record: `noise` is (num_steps, B, C, H, W) -- row 0 the initial
+        draw, rows 1.. the step noise, nothing random happens here --, every query after the first takes the text K / V
+        from the handle's cache on the caller's word (`reuse_text=True`: the text states are the same tensors for the
+        whole call, the teacher loop's rule), the post-CFG combine, add_noise, scale_model_input and the 2B-row stacking
+        between two queries are ONE launch (ctta_consistency_renoise) and the final combine is ctta_cfg_combine.  Same
+        fp32 operations per element as the eager sequence, so the latent is bit-identical to `generate_latent` with
+        `step_noise=noise[1:]`."""
+        sch = self.scheduler
+        L_ = N.lib()
+        use_cf = cfg_scale_post > 1.
+        B = noise.shape[1]
+        n = noise[0, 0].numel()
+        dev = noise.device
+        if use_cf:
+            encoder_states = torch.cat([uncond_states, encoder_states])
+            encoder_mask = torch.cat([uncond_mask, encoder_mask])
+            w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev)
+            fused_cfg = _post_cfg_fusable(cfg_scale_post)
+        sch.set_timesteps(18, device=dev)
+        z_N = noise[0] * sch.init_noise_sigma
+        z_in = sch.scale_model_input(torch.cat([z_N] * 2) if use_cf else z_N, float(sch._timesteps_host[0]))
+        t = float(sch._timesteps_host[0])
+        sch.set_timesteps(num_steps, device=dev)
+        later = [float(v) for v in sch._timesteps_host[1::2]]
+        assert len(later) == noise.shape[0] - 1, (len(later), tuple(noise.shape))
+        for k in range(len(later) + 1):
+            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=encoder_states,
+                           encoder_attention_mask=encoder_mask, reuse_text=k > 0).sample
+            if k == len(later):
+                break
+            t = later[k]
+            sig = sch._sigma_dev(sch.index_for_timestep(t), B, dev)
+            z_in = torch.empty_like(zh)
+            if use_cf and not fused_cfg:
+                cond, unc = (1 - cfg_scale_post) * zh[:B] + cfg_scale_post * zh[B:], None
+            else:
+                cond, unc = (zh[B:], zh[:B]) if use_cf else (zh, None)
+            N.check(L_.ctta_consistency_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_post) if unc is not None else N.c_void_p(0),
+                                                N.ptr(noise[k + 1]), N.ptr(sig), N.ptr(z_in), 2 if use_cf else 1, B, n,
+                                                N.stream_ptr()))
+        if not use_cf:
+            return zh
+        if not fused_cfg:
+            return (1 - cfg_scale_post) * zh[:B] + cfg_scale_post * zh[B:]
+        out = torch.empty_like(zh[:B])
+        N.check(L_.ctta_cfg_combine(N.ptr(zh[:B]), N.ptr(zh[B:]), N.ptr(w_post), N.ptr(out), B, n, N.stream_ptr()))
+        return out
+
+    def _serving_inputs(self, batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post, uncond_states,
+                        uncond_mask, from_tokens):
+        """Static inputs of a captured serving path and the function that refills them from a replay's arguments.
+        States-in: `(encoder_states, encoder_mask, noise)`; tokens-in: `(input_ids, attention_mask, noise)`.  `noise` is
+        (num_steps, B, C, H, W) -- row 0 the initial draw, rows 1.. the step noise --, or (B, C, H, W) when num_steps == 1.
+        With post-CFG the uncond states are static inputs fixed HERE: (B, L, D) or (1, L, D) (broadcast); tokens-in
+        captures compute them once, from the prompt "" padded to the bucket's length, when none are given."""
+        from .text_encoder import check_tokens
+        dev = self.unet.device
+        num_steps = int(num_steps)
+        if num_steps < 1:
+            raise ValueError("num_steps must be at least 1, got %d" % num_steps)
+        nshape = (num_steps, batch) + tuple(latent)
+        st = {"noise": torch.zeros(nshape, device=dev)}
+        if from_tokens:
+            if self.text_encoder is None:          # the tokens are the caller's: no tokenizer is needed here
+                self._require_text_encoder()
+            te = self.text_encoder
+            if not hasattr(te, "encode_static"):
+                raise N.CttaError("from_tokens needs the HIP text encoder (text_encoder.T5EncoderModel): a torch module's "
+                                  "forward cannot be recorded without its device -> host checks")
+            if te.config["d_model"] != cross_attention_dim:
+                raise ValueError("cross_attention_dim %d is not the text encoder's d_model %d"
+                                 % (cross_attention_dim, te.config["d_model"]))
+            st["ids"] = torch.zeros(batch, text_len, dtype=torch.int64, device=dev)
+            st["attn"] = torch.ones(batch, text_len, dtype=torch.int64, device=dev)
+        else:
+            st["enc"] = torch.zeros(batch, text_len, cross_attention_dim, device=dev)
+            st["mask"] = torch.ones(batch, text_len, dtype=torch.bool, device=dev)
+        if cfg_scale_post > 1.:
+            if uncond_states is None and from_tokens:
+                # encode_text_classifier_free's uncond half: the prompt "" at the bucket's length -- a constant of the bucket
+                uncond_states, uncond_mask = self.encode_text([""] * batch, max_length=text_len, padding="max_length")
+            if uncond_states is None or uncond_mask is None:
+                raise ValueError("cfg_scale_post > 1 needs uncond_states and uncond_mask")
+            if (uncond_states.ndim != 3 or uncond_states.shape[0] not in (1, batch)
+                    or tuple(uncond_states.shape[1:]) != (text_len, cross_attention_dim)
+                    or tuple(uncond_mask.shape) != tuple(uncond_states.shape[:2])):
+                raise ValueError("uncond_states %s / uncond_mask %s: expected (%d or 1, %d, %d) and its (B, L) mask"
+                                 % (tuple(uncond_states.shape), tuple(uncond_mask.shape), batch, text_len, cross_attention_dim))
+            st["unc"] = uncond_states.detach().to(dev, torch.float32).expand(batch, -1, -1).clone()
+            st["unc_mask"] = uncond_mask.detach().to(dev, torch.bool).expand(batch, -1).clone()
+
+        def load_noise(noise):
+            if tuple(noise.shape) == nshape:
+                st["noise"].copy_(noise)
+            elif num_steps == 1 and tuple(noise.shape) == nshape[1:]:
+                st["noise"][0].copy_(noise)
+            else:
+                raise ValueError("noise %s: expected %s (row 0 the initial draw, rows 1.. the step noise)"
+                                 % (tuple(noise.shape), nshape))
+
+        def load_states(encoder_states, encoder_mask, noise):
+            load_noise(noise)
+            st["enc"].copy_(encoder_states)
+            st["mask"].copy_(encoder_mask)
+
+        def load_tokens(input_ids, attention_mask, noise):
+            if not input_ids.is_cuda and not attention_mask.is_cuda:
+                check_tokens(input_ids, attention_mask, self.text_encoder.config["vocab_size"], batch, text_len)
+            elif tuple(input_ids.shape) != (batch, text_len) or tuple(attention_mask.shape) != (batch, text_len):
+                raise ValueError("tokens %s / %s are not the captured bucket (%d, %d)"
+                                 % (tuple(input_ids.shape), tuple(attention_mask.shape), batch, text_len))
+            # tokens already on the device are uploaded unchecked: t5_embed_kernel clamps ids into the vocabulary
+            load_noise(noise)
+            st["ids"].copy_(input_ids)
+            st["attn"].copy_(attention_mask)
+
+        return st, (load_tokens if from_tokens else load_states)
+
+    def _encode_static(self, st):
+        """`encode_text` on the static token buffers, launches only: (states, bool mask)."""
+        return self.text_encoder.encode_static(st["ids"], st["attn"]), st["attn"] == 1
+
     @torch.no_grad()
-    def capture_graph(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16)):
-        """Captures the whole single-step pipeline (U-Net query -> VAE decoder -> HiFi-GAN -> int16) for a fixed
+    def capture_graph(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
+                      num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None, from_tokens=False):
+        """Captures the whole pipeline (U-Net queries -> VAE decoder -> HiFi-GAN -> int16) for a fixed
         (batch, text_len) into ONE hipGraph and returns a callable `(encoder_states, encoder_mask, noise) -> pcm` that
         copies its arguments into the graph's static inputs and replays it.  The ~1500 kernel launches of a clip cost
         more host time than GPU time at batch 1 (demo.py / easy_inference latency); a replay is a single launch.
-        Results are identical to `forward_from_embeds(..., cfg_scale_post=1, num_steps=1)`."""
+        Results are identical to `forward_from_embeds(..., cfg_scale_post, num_steps, step_noise=noise[1:])`.
+        `num_steps > 1` (the reference's --num_steps): `noise` is (num_steps, B, C, H, W), row 0 the initial draw and
+        rows 1.. the re-noising draws -- nothing random happens inside the graph.  `cfg_scale_post > 1`
+        (--guidance_scale_post): every query runs on 2B rows; the uncond states and mask ((B, L, D) or (1, L, D)) are
+        static inputs fixed at capture.  `from_tokens=True`: the callable takes `(input_ids, attention_mask, noise)` --
+        int64 (B, L) ids and a (B, L) mask, on the host or on the device -- and FLAN-T5 runs inside the graph; host tokens
+        pass `text_encoder.check_tokens` before the upload, device tokens are taken as they are (t5_embed_kernel clamps
+        ids into the vocabulary); with post-CFG the uncond states are those of the prompt "" at length `text_len`."""
         self.check_eval_mode()
         dev = self.unet.device
-        st = {"enc": torch.zeros(batch, text_len, cross_attention_dim, device=dev),
-              "mask": torch.ones(batch, text_len, dtype=torch.bool, device=dev),
-              "noise": torch.zeros((batch,) + tuple(latent), device=dev)}
+        st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
+                                        uncond_states, uncond_mask, from_tokens)
         scratch = torch.empty(4, dtype=torch.float32, device=dev)
 
         def run():
-            lat = self.generate_latent(st["enc"], st["mask"], st["noise"], cfg_scale_input, 1.0, 1)
+            enc, mask = self._encode_static(st) if from_tokens else (st["enc"], st["mask"])
+            lat = self._generate_latent_static(enc, mask, st["noise"], cfg_scale_input, cfg_scale_post, num_steps,
+                                               st.get("unc"), st.get("unc_mask"))
             mel = self.vae.decode_first_stage(lat)
             wav = self.vae.vocode(mel)
             pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
@@ -1675,32 +1929,36 @@ class ConsistencyTTA(nn.Module):
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             out = run()
 
-        def replay(encoder_states, encoder_mask, noise):
-            st["enc"].copy_(encoder_states)
-            st["mask"].copy_(encoder_mask)
-            st["noise"].copy_(noise)
+        def replay(*args):
+            load(*args)
             graph.replay()
+            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
             return out[2]
 
         replay.graph, replay.outputs = graph, out
+        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
         return replay
 
     def capture_pipeline(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
-                         candidates=8):
-        """The same single-step pipeline as a 3-deep SOFTWARE PIPELINE over batches for a throughput-bound server: three
-        hipGraphs -- U-Net query, VAE decoder, HiFi-GAN + int16 -- replayed per call on three streams for three DIFFERENT
+                         candidates=8, num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None,
+                         from_tokens=False):
+        """The same pipeline as a 3-deep SOFTWARE PIPELINE over batches for a throughput-bound server: three
+        hipGraphs -- U-Net queries, VAE decoder, HiFi-GAN + int16 -- replayed per call on three streams for three DIFFERENT
         batches (the batch of this call, of the previous call, of the call before).  The stages of one batch stay strictly
         ordered; stages of different batches share nothing, and each one's thin launches (the U-Net's deep levels, the
         vocoder's C <= 64 stages) fill the CUs the others leave idle.  Returns `f(encoder_states, encoder_mask, noise) ->
         int16 waveforms of the batch fed TWO calls earlier` (the buffer is overwritten by the next call; the first two calls
         return warm-up garbage -- feed two extra batches, e.g. the last one again, to drain).  Results are bit-identical to
         `capture_graph` / the eager path.  Which streams the U-Net and decoder graphs run on is measured at capture: HIP maps
-        streams onto 4 hardware queues and two graphs on one queue do not overlap (see `_DistillStepGraph._place_teacher_stream`)."""
+        streams onto 4 hardware queues and two graphs on one queue do not overlap (see `_DistillStepGraph._place_teacher_stream`).
+        `num_steps`, `cfg_scale_post`, `uncond_states`, `uncond_mask`, `from_tokens`: as in `capture_graph`.  With
+        `from_tokens=True` FLAN-T5 is a FOURTH graph on a fourth stream, placed by the same measurement, one batch ahead of
+        the U-Net: `f(input_ids, attention_mask, noise)` returns the batch fed THREE calls earlier (`f.depth == 3`); a
+        batch's noise is held back one call so that it meets its own text states."""
         self.check_eval_mode()
         dev = self.unet.device
-        st = {"enc": torch.zeros(batch, text_len, cross_attention_dim, device=dev),
-              "mask": torch.ones(batch, text_len, dtype=torch.bool, device=dev),
-              "noise": torch.zeros((batch,) + tuple(latent), device=dev)}
+        st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
+                                        uncond_states, uncond_mask, from_tokens)
         scratch = torch.empty(4, dtype=torch.float32, device=dev)
 
         def graphed(fn):
@@ -1715,7 +1973,13 @@ class ConsistencyTTA(nn.Module):
                 out = fn()
             return gr, out
 
-        g_u, lat = graphed(lambda: self.generate_latent(st["enc"], st["mask"], st["noise"], cfg_scale_input, 1.0, 1))
+        if from_tokens:
+            g_t, (enc, mask) = graphed(lambda: self._encode_static(st))
+            u_in = {"enc": enc.clone(), "mask": mask.clone(), "noise": st["noise"].clone()}
+        else:
+            g_t, u_in = None, st
+        g_u, lat = graphed(lambda: self._generate_latent_static(u_in["enc"], u_in["mask"], u_in["noise"], cfg_scale_input,
+                                                                cfg_scale_post, num_steps, st.get("unc"), st.get("unc_mask")))
         lat_in = lat.clone()
         g_v, mel = graphed(lambda: self.vae.decode_first_stage(lat_in))
         mel_in = mel.clone()
@@ -1726,18 +1990,25 @@ class ConsistencyTTA(nn.Module):
             N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
             return pcm
         g_h, pcm = graphed(voc)
-        streams = {"u": torch.cuda.Stream(device=dev), "v": torch.cuda.Stream(device=dev)}
+        side_graphs = [("v", g_v), ("u", g_u)] + ([("t", g_t)] if from_tokens else [])
+        streams = {k: torch.cuda.Stream(device=dev) for k, _ in side_graphs}
 
-        def iteration():
-            cur = torch.cuda.current_stream(dev)
-            lat_in.copy_(lat)                          # hand-over at the call boundary: batch i-1 to the decoder, i-2 to the vocoder
+        def hand_over():
+            lat_in.copy_(lat)                          # at the call boundary: batch i-1 to the decoder, i-2 to the vocoder
             mel_in.copy_(mel)
-            for k, g_ in (("v", g_v), ("u", g_u)):
+            if from_tokens:                            # ... and the text states + noise of the batch fed last call to the U-Net
+                u_in["enc"].copy_(enc)
+                u_in["mask"].copy_(mask)
+                u_in["noise"].copy_(st["noise"])
+
+        def launch():
+            cur = torch.cuda.current_stream(dev)
+            for k, g_ in side_graphs:
                 streams[k].wait_stream(cur)
                 with torch.cuda.stream(streams[k]):
                     g_.replay()
             g_h.replay()                               # the largest stage on the caller's stream
-            for k in ("v", "u"):
+            for k, _ in side_graphs:
                 cur.wait_stream(streams[k])
 
         def timed():
@@ -1746,13 +2017,14 @@ class ConsistencyTTA(nn.Module):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize(dev)
                 e0.record()
-                iteration()
+                hand_over()
+                launch()
                 e1.record()
                 torch.cuda.synchronize(dev)
                 ms = e0.elapsed_time(e1)
             return ms
         placement = {}
-        for k in ("v", "u"):                           # decoder first, then the U-Net beside both
+        for k, _ in side_graphs:                       # decoder first, then the U-Net beside both, then the text encoder
             best = (streams[k], float("inf"))
             tried = []
             for s_ in [streams[k]] + [torch.cuda.Stream(device=dev) for _ in range(max(0, candidates - 1))]:
@@ -1764,14 +2036,16 @@ class ConsistencyTTA(nn.Module):
             streams[k] = best[0]
             placement[k] = tried
 
-        def replay(encoder_states, encoder_mask, noise):
-            st["enc"].copy_(encoder_states)
-            st["mask"].copy_(encoder_mask)
-            st["noise"].copy_(noise)
-            iteration()
+        def replay(*args):
+            hand_over()                                # reads the previous call's inputs and results, before ...
+            load(*args)                                # ... this call's arguments overwrite the static inputs
+            launch()
+            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
             return pcm
 
-        replay.depth, replay.placement_ms, replay.graphs = 2, placement, (g_u, g_v, g_h)
+        replay.depth, replay.placement_ms = (3 if from_tokens else 2), placement
+        replay.graphs = (g_u, g_v, g_h) + ((g_t,) if from_tokens else ())
+        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
         return replay
 
     # ---- text side, easy_inference/consistencytta.py:82-132 (FLAN-T5 on the HIP engine, tokenizer on the host)
@@ -1797,8 +2071,9 @@ class ConsistencyTTA(nn.Module):
 
     @torch.no_grad()
     def forward_from_embeds(self, encoder_states, encoder_mask, noise, cfg_scale_input=3., cfg_scale_post=1.,
-                            num_steps=1, sr=16000, **kw):
+                            num_steps=1, sr=16000, step_noise=None, **kw):
         self.check_eval_mode()
-        lat = self.generate_latent(encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps, **kw)
+        lat = self.generate_latent(encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps,
+                                   step_noise=step_noise, **kw)
         mel = self.vae.decode_first_stage(lat.float())
         return self.vae.decode_to_waveform(mel)[:, :int(sr * 9.5)]

@@ -34,6 +34,27 @@ class _Config(dict):
             raise AttributeError(name)
 
 
+def check_tokens(input_ids, attention_mask, vocab_size, batch, text_len):
+    """The range checks of `T5EncoderModel.forward` as a HOST-side function, for the captured tokens-in paths
+    (`ConsistencyTTA.capture_graph(from_tokens=True)`): it runs on the CPU copies of the tokens BEFORE they are uploaded
+    into the graph's static buffers, so no replay waits on the device.  Raises like `forward` does: IndexError on an id
+    outside [0, vocab_size), ValueError on a row without a token or a shape other than the captured (batch, text_len)
+    bucket.  Tokens that already live on the device are not checked at all (reading them back would be the sync this
+    avoids); for those, t5_embed_kernel's clamp of the id to [0, vocab_size) is the only guard."""
+    if input_ids.is_cuda or attention_mask.is_cuda:
+        raise ValueError("check_tokens runs on host tensors; device tokens are uploaded unchecked")
+    if tuple(input_ids.shape) != (batch, text_len):
+        raise ValueError("input_ids %s is not the captured bucket (%d, %d)" % (tuple(input_ids.shape), batch, text_len))
+    if tuple(attention_mask.shape) != (batch, text_len):
+        raise ValueError("attention_mask must match input_ids, got %s" % (tuple(attention_mask.shape),))
+    if input_ids.dtype != torch.int64:
+        raise ValueError("input_ids must be int64, got %s" % input_ids.dtype)
+    if input_ids.numel() and (int(input_ids.min()) < 0 or int(input_ids.max()) >= vocab_size):
+        raise IndexError("input_ids outside [0, %d)" % vocab_size)
+    if not bool((attention_mask != 0).any(dim=1).all()):
+        raise ValueError("every row of attention_mask needs at least one token")
+
+
 class T5EncoderModel(_ParamTree):
     def __init__(self, config=None):
         super().__init__()
@@ -98,6 +119,25 @@ class T5EncoderModel(_ParamTree):
                 N.check(N.lib().ctta_t5_create(c, table, len(table), N.stream_ptr(), h))
             self._h_t5, self._h_t5_key, self._h_t5_ver = h, (B, max(L, 8)) + key, ver
         return self._h_t5
+
+    @torch.no_grad()
+    def encode_static(self, input_ids, attention_mask, out=None):
+        """`forward` without its range checks (each one is a device -> host sync, which a hipGraph capture cannot hold):
+        launches only, on the current stream.  `input_ids` int64 (B, L) and `attention_mask` (B, L, any integer / bool
+        dtype) on this device; the caller has validated the tokens with `check_tokens` on the host, otherwise
+        t5_embed_kernel clamps ids into the vocabulary.  Returns the (B, L, d_model) float32 states (`out` when given)."""
+        if not input_ids.is_cuda or input_ids.dtype != torch.int64 or input_ids.ndim != 2 or not input_ids.is_contiguous():
+            raise ValueError("input_ids must be a contiguous int64 (batch, length) tensor on the device")
+        B, L = input_ids.shape
+        if tuple(attention_mask.shape) != (B, L):
+            raise ValueError("attention_mask must match input_ids, got %s" % (tuple(attention_mask.shape),))
+        mask = (attention_mask != 0).to(torch.uint8).contiguous()
+        h = self._ensure(B, L)
+        if out is None:
+            out = torch.empty((B, L, self.config["d_model"]), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().ctta_t5_encode(h, N.ptr(input_ids), N.ptr(mask), B, L, N.ptr(out), N.stream_ptr()))
+        return out
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, **kwargs):

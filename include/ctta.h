@@ -315,6 +315,17 @@ ctta_status ctta_heun_step_second(const float* v, const float* x_hat, const floa
  * out = (1-w)*uncond + w*cond, per-sample w (B) f32. */
 ctta_status ctta_cfg_combine(const float* uncond, const float* cond, const float* w, float* out,
                              int batch, int64_t n_per_sample, void* stream);
+/* One sampler step between two U-Net queries of the few-step consistency sampler
+ * (easy_inference/consistencytta.py:152-197; scheduling_heun_discrete.py:151-172,364-385) in one pass over (B, n) f32:
+ *   x0  = uncond == NULL ? cond : (1 - w_post[b]) * uncond + w_post[b] * cond      (post-CFG combine)
+ *   z   = x0 + noise * sigma[b]                                                    (add_noise)
+ *   out = z / sqrt(sigma[b]^2 + 1)                                                 (scale_model_input)
+ * `out` holds copies * B rows: the result is written `copies` (1 or 2) times, stacked along the batch (the 2B-row input of
+ * a CFG query).  sigma and w_post are (B) f32 on device; w_post may be NULL when uncond is.  Bit-identical to torch's
+ * (1 - w) * u + w * c, then ctta_heun_add_noise, then ctta_heun_scale_model_input, then a concatenation. */
+ctta_status ctta_consistency_renoise(const float* cond, const float* uncond, const float* w_post, const float* noise,
+                                     const float* sigma, float* out, int copies, int batch, int64_t n_per_sample,
+                                     void* stream);
 /* get_loss with MSELoss('instance') and SNR clamp (models/audio_consistency_model.py:250-266,
  * tools/losses.py:28-33): loss = mean_b( mean((pred-target)^2) * min(sigma^-2, gamma) ).
  * gamma <= 0 disables the weighting.  loss: 1 float on device. */
