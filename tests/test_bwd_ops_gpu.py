@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import attention_ref as AR  # noqa: E402
 from consistencytta_amd import _native as N  # noqa: E402
 from gpu_util import DEV, bf16_round, conv_desc, det, from_nhwc, nhwc_bf16, pack_conv_weight, rel_err, run_conv, sync  # noqa: E402
 
@@ -500,7 +501,10 @@ def test_embedding_mlp_backward_loss_grad_and_adamw():
 @pytest.mark.parametrize("B,heads,dh,nq,nk,krows,use_bias", [(2, 3, 51, 200, 200, 200, False), (2, 2, 64, 256, 256, 256, False),
                                                             (3, 3, 13, 70, 7, 8, True), (1, 5, 51, 130, 31, 32, True),
                                                             (1, 2, 51, 2100, 20, 24, True),
-                                                            (2, 6, 40, 4, 4, 4, False)])
+                                                            (2, 6, 40, 4, 4, 4, False)]
+                         # the PLAIN instantiations (no bias, nq and nk multiples of 64) away from 256 x 256: one key tile,
+                         # an odd tile count, nq != nk; then a plain2 forward (nk = 128) with a non-plain backward
+                         + AR.BWD_CASES_NEW)
 def test_flash_attention_backward(B, heads, dh, nq, nk, krows, use_bias):
     """ctta_attention_lse + ctta_attention_bwd vs autograd of softmax(q k^T * scale + bias) v (fp32 on the
     bf16-rounded operands); heads padded to 64 lanes as in the engine."""

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import attention_ref as AR  # noqa: E402
 from consistencytta_amd import _native as N  # noqa: E402
 from gpu_util import (DEV, bf16_round, conv_desc, det, from_nhwc, nhwc_bf16, pack_conv_weight,  # noqa: E402
                       rel_err, run_conv, sync)
@@ -1047,9 +1048,15 @@ def test_geglu_and_softmax():
 
 @pytest.mark.parametrize("B,heads,dh,nq,nk,masked", [(2, 3, 13, 256, 256, False), (2, 5, 51, 200, 200, False),
                                                      (2, 6, 13, 4, 4, False), (1, 2, 64, 130, 70, False),
-                                                     (2, 3, 13, 64, 7, True), (3, 5, 51, 300, 32, True)])
+                                                     (2, 3, 13, 64, 7, True), (3, 5, 51, 300, 32, True)]
+                         + AR.FWD_CASES_NEW)
 def test_attention(B, heads, dh, nq, nk, masked):
-    """Flash attention with head dim padded to 64 vs softmax(q k^T / sqrt(dh) + bias) v."""
+    """Flash attention with head dim padded to 64 vs softmax(q k^T / sqrt(dh) + bias) v.
+
+    Beside the global bound, every query row is held to twice what the CPU emulation of the kernel's arithmetic
+    (tests/attention_ref.py) loses against float64 on the same case, and never more than 2.5 * BF16_TOL: a global
+    max-abs bound says nothing about one wrong row whose output is small.  FWD_CASES_NEW enters attention_kernel<3>
+    (no bias, nk = 64) and attention_plain2_kernel at its minimum, with odd tile counts and with ragged query blocks."""
     q = bf16_round(det("at.q", (B, heads, nq, dh), 1))
     k = bf16_round(det("at.k", (B, heads, nk, dh), 2))
     v = bf16_round(det("at.v", (B, heads, nk, dh), 3))
@@ -1074,14 +1081,78 @@ def test_attention(B, heads, dh, nq, nk, masked):
         vtd[:, h * 64:h * 64 + 64, :nk] = 0
         vtd[:, h * 64:h * 64 + dh, :nk] = v[:, h].transpose(1, 2)
     qd, kd, vtd = (t.to(torch.bfloat16).to(DEV) for t in (qd, kd, vtd))
-    out = torch.zeros(B, nq, hp, dtype=torch.bfloat16, device=DEV)
+    # out batches lie nq rows apart (no room between them): the two guard rows follow the last batch
+    out = torch.full((B * nq + 2, hp), float("nan"), dtype=torch.bfloat16, device=DEV)
+    lse = torch.full((B, heads, nq), float("nan"), device=DEV)
     bd = bias.contiguous().to(DEV) if bias is not None else None
-    N.check(lib().ctta_attention(N.ptr(qd), hp, N.ptr(kd), hp, k_rows, N.ptr(vtd), vt_ld, N.ptr(bd), N.ptr(out), hp,
-                                 B, heads, nq, nk, 1.0 / math.sqrt(dh), N.stream_ptr()))
+    N.check(lib().ctta_attention_lse(N.ptr(qd), hp, N.ptr(kd), hp, k_rows, N.ptr(vtd), vt_ld, N.ptr(bd), N.ptr(out), hp,
+                                     B, heads, nq, nk, 1.0 / math.sqrt(dh), N.ptr(lse), N.stream_ptr()))
     sync()
-    o = out.to(torch.float32).cpu().reshape(B, nq, heads, 64)[..., :dh].permute(0, 2, 1, 3)
+    full = out.to(torch.float32).cpu()
+    assert bool(torch.isnan(full[B * nq:]).all())             # rows behind the last query are not the kernel's
+    full = full[:B * nq].reshape(B, nq, heads, 64)
+    assert bool(torch.isfinite(full).all())
+    if dh < 64:
+        assert float(full[..., dh:].abs().max()) == 0.0       # head-pad lanes: V^T is zero there, so is the output
+    o = full[..., :dh].permute(0, 2, 1, 3)
     # P is rounded to bf16 before the PV product: 2^-8 relative on each probability
     assert rel_err(o, ref) < 2.5 * BF16_TOL
+    ref64, lse64 = AR.attention_fp64(q, k, v, 1.0 / math.sqrt(dh), bias)
+    assert float((lse.cpu().double() - lse64).abs().max()) < 2e-2
+    emu_worst = float(AR.row_errors(AR.attention_bf16_emulated(q, k, v, 1.0 / math.sqrt(dh), bias), ref64).max())
+    worst = float(AR.row_errors(o, ref64).max())
+    print("attention %s: worst row %.3e (emulation %.3e)" % ((B, heads, dh, nq, nk, masked), worst, emu_worst))
+    assert worst <= min(AR.KERNEL_OVER_EMULATION * emu_worst, AR.ROW_BOUND)
+
+
+def _rel_case(B, heads, dh, nq, nk, one_offset):
+    """ctta_attention_rel in engine_t5's layout: q and k are the two column halves of one [B][Lp][2 * inner] buffer,
+    every batch Lp > L rows tall; V^T [B][inner][Lp] with NaN behind the keys; out [B][Lp][inner]."""
+    q, k, v, bias, rel, scale = AR.rel_inputs(B, heads, dh, nq, nk, one_offset)
+    inner = heads * 64
+    L = max(nq, nk)
+    Lp = (L + 3 + 7) // 8 * 8
+    qk = torch.zeros(B, Lp, 2 * inner)
+    vtd = torch.full((B, inner, Lp), float("nan"))
+    for h in range(heads):
+        qk[:, :nq, h * 64:h * 64 + dh] = q[:, h]
+        qk[:, :nk, inner + h * 64:inner + h * 64 + dh] = k[:, h]
+        vtd[:, h * 64:h * 64 + 64, :nk] = 0
+        vtd[:, h * 64:h * 64 + dh, :nk] = v[:, h].transpose(1, 2)
+    qk, vtd = qk.to(torch.bfloat16).to(DEV), vtd.to(torch.bfloat16).to(DEV)
+    out = torch.full((B, Lp, inner), float("nan"), dtype=torch.bfloat16, device=DEV)
+    bd = bias.contiguous().to(DEV)
+    reld = (rel * AR.LOG2E).contiguous().to(DEV)              # the kernel takes the table in the log2 domain
+    kptr = N.c_void_p(qk.data_ptr() + inner * 2)
+    N.check(lib().ctta_attention_rel(N.ptr(qk), 2 * inner, Lp, kptr, 2 * inner, Lp, N.ptr(vtd), Lp, N.ptr(bd), N.ptr(reld),
+                                     N.ptr(out), inner, B, heads, nq, nk, scale, N.stream_ptr()))
+    sync()
+    full = out.to(torch.float32).cpu()
+    assert bool(torch.isnan(full[:, nq:]).all())              # rows L .. Lp-1 of every batch keep their poison
+    full = full[:, :nq].reshape(B, nq, heads, 64)
+    assert bool(torch.isfinite(full).all())
+    if dh < 64:
+        assert float(full[..., dh:].abs().max()) == 0.0
+    o = full[..., :dh].permute(0, 2, 1, 3)
+    ref64, _ = AR.attention_fp64(q, k, v, scale, bias, rel)
+    emu_worst = float(AR.row_errors(AR.attention_bf16_emulated(q, k, v, scale, bias, rel), ref64).max())
+    worst = float(AR.row_errors(o, ref64).max())
+    print("attention_rel %s%s: worst row %.3e (emulation %.3e)" % ((B, heads, dh, nq, nk), " one offset" if one_offset else "",
+                                                                 worst, emu_worst))
+    assert worst <= min(AR.KERNEL_OVER_EMULATION * emu_worst, AR.ROW_BOUND)
+
+
+@pytest.mark.parametrize("B,heads,dh,nq,nk", AR.REL_CASES)
+def test_attention_rel(B, heads, dh, nq, nk):
+    """attention_kernel<1> (T5's relative-position table, one per head, index key - query + nq - 1) vs float64, per
+    query row, with ragged key masks; nq != nk is where that index goes wrong."""
+    _rel_case(B, heads, dh, nq, nk, False)
+
+
+def test_attention_rel_single_offset_table():
+    """A table that is zero except at one offset per head puts nearly all of a row's weight on key = query + offset:
+    reading the table one entry off moves that weight to another key and the row is wrong outright."""
+    _rel_case(*AR.REL_ONE_OFFSET_CASE, True)
 
 
 def test_small_fp32_kernels():
