@@ -433,3 +433,68 @@ def tensor_table(sd):
         for d in range(v.ndim):
             arr[i].shape[d] = v.shape[d]
     return arr, keep
+
+
+def param_table(named):
+    """(name, parameter) pairs  =>  `tensor_table` of the detached parameters; each must already live on the device."""
+    sd = {}
+    for k, p in named:
+        if not p.is_cuda:
+            raise CttaError("parameter '%s' is on %s: the HIP engine has no CPU path" % (k, p.device))
+        sd[k] = p.detach()
+    return tensor_table(sd)
+
+
+class EngineHandle:
+    """Owner of one native engine handle (ctta_unet / vae / vae_encoder / hifigan / t5): the handle, the capacity tuple it
+    was created for, the identity key (extent, flags, device) and the weights version it packed.  WHEN a handle is replaced
+    is the caller's policy, expressed in what it passes to `fits` / `replace`; a captured hipGraph holds the handle's
+    address, so a replacement invalidates every graph recorded through it."""
+
+    def __init__(self, destroy):
+        self.destroy = destroy          # name of the ctta_*_destroy symbol
+        self.h = self.capacity = self.key = self.version = None
+
+    def fits(self, capacity, key, version):
+        """A live handle of this identity and weights version whose every capacity covers the request."""
+        return (self.h is not None and key == self.key and version == self.version
+                and all(n <= c for n, c in zip(capacity, self.capacity)))
+
+    def replace(self, create_fn, capacity, key, version, device):
+        """Destroys the old handle FIRST (two generations never hold device memory together), then
+        `create_fn(out_handle) -> status` on `device`.  A failed create leaves the holder empty."""
+        import torch
+        self.release()
+        h = c_void_p()
+        with torch.cuda.device(device):
+            check(create_fn(h))
+        self.h, self.capacity, self.key, self.version = h, tuple(capacity), key, version
+        return h
+
+    def release(self):
+        h, self.h = self.h, None
+        if h:
+            getattr(lib(), self.destroy)(h)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def read_taps(prefix, handle, device):
+    """name -> NCHW fp32 tensor of every intermediate a debug_taps handle recorded (`prefix`: "ctta_unet", ...)."""
+    import torch
+    from collections import OrderedDict
+    L = lib()
+    num, info, read = (getattr(L, "%s_%s" % (prefix, f)) for f in ("num_taps", "tap_info", "tap_read"))
+    out = OrderedDict()
+    for i in range(num(handle)):
+        name = c_char_p()
+        dims = (c_int * 4)()
+        check(info(handle, i, name, dims))
+        t = torch.empty(tuple(dims), dtype=torch.float32, device=device)
+        check(read(handle, i, ptr(t), stream_ptr()))
+        out[name.value.decode()] = t
+    return out

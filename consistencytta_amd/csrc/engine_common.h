@@ -38,7 +38,7 @@ struct Arena {
 struct SplitWs {
   void* p = nullptr;
   size_t bytes = 0;
-  ctta_status init() {
+  __attribute__((noinline)) ctta_status init() {   // cold: one out-of-line copy, not one per create
     bytes = ctta_conv_workspace_bytes();
     if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; ctta_set_error("hipMalloc of the split-K workspace failed"); return CTTA_ERR_NOMEM; }
     // the stream-K header (ticket / finished / epoch words and the flags) starts at zero; the launches keep it consistent
@@ -514,6 +514,90 @@ static inline void gn_emit_done(RunCtx& c, const ctta_conv_desc& d) {
 // it now agrees to bf16 round-off instead of bit for bit (tests/test_engines_gpu.py, both properties; with the fusion
 // off the old bit-for-bit property across sizes is asserted too).
 static inline bool gn_fuse_enabled() { return ctta_gn_fuse_on(); }
+
+// ---------------------------------------------------------------------------------- engine handles
+// What every weight-carrying handle (ctta_unet / vae / vae_encoder / hifigan / t5) owns, and the lifecycle around it.
+// A create validates its config (every CTTA_REQUIRE comes BEFORE the `new`: nothing may return between the `new` and the
+// status check at the end, which hands a failed handle to its destroy), fills `store`, runs its own dry forward (and
+// backward) over the still-dry `arena`, then calls allocate_after_dry_run().  The handle's destroy calls destroy_base().
+struct __attribute__((visibility("hidden"))) EngineBase {   // internal: the library exports nothing of it
+  WeightStore store;
+  Arena arena;
+  std::vector<Tap> taps;
+  float* gn_scratch = nullptr;     // HiFi-GAN and T5 have none
+  size_t gn_scratch_floats = 0;
+  size_t gn_fpart_floats = 0;      // fused-statistics partials, stored behind the gn_scratch_floats of scratch
+  SplitWs splitws;                 // this handle's split-K workspace (bound per entry point)
+
+  // The one place that fills a RunCtx from a handle.  gn_groups == 0: the pass emits / consumes no fused statistics
+  // (the backward passes of the U-Net, HiFi-GAN and T5), so it gets no partials pointer either.
+  void bind(RunCtx& c, hipStream_t stream, bool dry, bool record_taps, int gn_groups) {
+    c.arena = &arena; c.stream = stream; c.dry = dry;
+    c.taps = record_taps ? &taps : nullptr;
+    c.gn_scratch = gn_scratch; c.gn_scratch_floats = gn_scratch_floats;
+    if (gn_scratch && gn_groups > 0 && gn_fuse_enabled()) { c.gn_fpart = gn_scratch + gn_scratch_floats; c.gn_fpart_floats = gn_fpart_floats; }
+    c.gn_groups = gn_groups;
+  }
+
+  ctta_status load_weights(const ctta_tensor* weights, int n_weights, hipStream_t stream) {
+    WeightTable wt;
+    wt.build(weights, n_weights);
+    return store.run_all(wt, stream);
+  }
+
+  // Tail of every create: the dry-run peak becomes the arena, the GroupNorm scratch (gn_need + 64 floats, the partials
+  // behind them) is allocated where the handle has one, then the split-K workspace; ends with the stream idle.
+  ctta_status allocate_after_dry_run(const char* what, size_t gn_need, size_t fpart_floats, bool zero_arena, hipStream_t stream) {
+    const size_t bytes = arena.peak + (1 << 20);
+    arena.dry = false;
+    arena.cap = bytes;
+    const bool has_gn = gn_need != 0 || fpart_floats != 0;
+    if (hipMalloc((void**)&arena.base, bytes) != hipSuccess ||
+        (has_gn && hipMalloc((void**)&gn_scratch, (gn_need + 64 + fpart_floats) * sizeof(float)) != hipSuccess)) {
+      ctta_set_error("%s: hipMalloc of %zu-byte activation arena failed", what, bytes);
+      return CTTA_ERR_NOMEM;
+    }
+    if (has_gn) { gn_scratch_floats = gn_need + 64; gn_fpart_floats = fpart_floats; }
+    if (zero_arena && ctta_zero_async(arena.base, bytes, stream) != hipSuccess) return CTTA_ERR_HIP;
+    CTTA_TRY(splitws.init());
+    if (hipStreamSynchronize(stream) != hipSuccess) { ctta_set_error("%s: stream sync failed", what); return CTTA_ERR_HIP; }
+    return CTTA_OK;
+  }
+
+  void destroy_base() {
+    store.destroy();
+    if (arena.base) (void)hipFree(arena.base);
+    if (gn_scratch) (void)hipFree(gn_scratch);
+    splitws.destroy();
+    arena.base = nullptr; gn_scratch = nullptr;
+  }
+
+  size_t arena_bytes() const { return arena.cap + store.arena.cap; }
+};
+
+// Debug taps of a handle (a null handle has none: every index is out of range).
+static inline const std::vector<Tap>& taps_of(const EngineBase* e) {
+  static const std::vector<Tap>& none = *new std::vector<Tap>();   // never destroyed: no exit-time destructor
+  return e ? e->taps : none;
+}
+static inline ctta_status tap_info(const std::vector<Tap>& taps, int i, const char** name, int dims[4]) {
+  CTTA_REQUIRE(i >= 0 && i < (int)taps.size(), "tap index out of range");
+  const Tap& t = taps[i];
+  *name = t.name.c_str();
+  dims[0] = t.b; dims[1] = t.c; dims[2] = t.h; dims[3] = t.w;
+  return CTTA_OK;
+}
+static inline ctta_status tap_read(const std::vector<Tap>& taps, int i, float* dst, void* stream) {
+  CTTA_REQUIRE(i >= 0 && i < (int)taps.size() && dst, "tap index out of range");
+  const Tap& t = taps[i];
+  CTTA_REQUIRE(t.ptr, "tap '%s' has not been produced yet", t.name.c_str());
+  if (t.f32_nchw) {   // the U-Net's fp32 embeddings
+    CTTA_CHECK_HIP(hipMemcpyAsync(dst, t.ptr, (size_t)t.b * t.c * t.h * t.w * sizeof(float), hipMemcpyDeviceToDevice,
+                                  (hipStream_t)stream));
+    return CTTA_OK;
+  }
+  return ctta_nhwc_bf16_to_nchw_f32(t.ptr, dst, t.b, t.c, t.h, t.w, t.c_stride, stream);
+}
 
 #define RUN(ctx, expr)                 \
   do {                                 \

@@ -108,17 +108,15 @@ struct T5Block {
   PackedW qk, v, o, wi, wo;
 };
 
-struct ctta_t5 {
+struct ctta_t5 : EngineBase {   // no GroupNorm and no debug taps: gn_scratch stays null, taps empty
   ctta_t5_config cfg;
-  WeightStore store;
-  Arena arena;
-  SplitWs splitws;
   float* embed = nullptr;        // fp32 [vocab][d_model]
   float* rel_emb = nullptr;      // fp32 [buckets][heads]
   float* ln_f = nullptr;
   int32_t* bucket = nullptr;     // device [2*max_len-1]: bucket(key - query), the reference's own float arithmetic
   std::vector<T5Block> blocks;
   int inner = 0, ffp = 0;
+  __attribute__((noinline)) ~ctta_t5() = default;   // out of line, like the larger handles' destructors
 };
 
 // modeling_t5.py _relative_position_bucket (bidirectional): half the buckets per sign, first half of each exact,
@@ -189,8 +187,7 @@ static ctta_status t5_forward_impl(ctta_t5* T, bool dry, const int64_t* ids, con
                                    hipStream_t stream) {
   const ctta_t5_config& cfg = T->cfg;
   RunCtx c;
-  c.arena = &T->arena; c.stream = stream; c.dry = dry;
-  c.taps = nullptr; c.gn_scratch = nullptr; c.gn_scratch_floats = 0;
+  T->bind(c, stream, dry, false, 0);
   Arena& A = T->arena;
   A.reset();
   const int d = cfg.d_model, H = cfg.num_heads, inner = T->inner, ffp = T->ffp;
@@ -253,9 +250,7 @@ static ctta_status t5_forward_impl(ctta_t5* T, bool dry, const int64_t* ids, con
 
 extern "C" void ctta_t5_destroy(ctta_t5* T) {
   if (!T) return;
-  T->store.destroy();
-  if (T->arena.base) (void)hipFree(T->arena.base);
-  T->splitws.destroy();
+  T->destroy_base();
   delete T;
 }
 
@@ -273,27 +268,13 @@ extern "C" ctta_status ctta_t5_create(const ctta_t5_config* cfg, const ctta_tens
   size_t store = 64 << 20;
   for (int i = 0; i < n_weights; ++i) store += (size_t)tensor_numel(&weights[i]) * 4 + 8192;   // bf16 packs + fp32 embedding + maps
   ctta_status st = T->store.init(store);
-  if (st != CTTA_OK) { delete T; return st; }
-  WeightTable wt;
-  wt.build(weights, n_weights);
-  st = t5_build(T);
-  if (st == CTTA_OK) st = T->store.run_all(wt, s);
+  if (st == CTTA_OK) st = t5_build(T);
+  if (st == CTTA_OK) st = T->load_weights(weights, n_weights, s);
   if (st == CTTA_OK) {
     T->arena.dry = true;
     st = t5_forward_impl(T, true, nullptr, nullptr, cfg->max_batch, cfg->max_len, nullptr, s);
   }
-  if (st == CTTA_OK) {
-    const size_t bytes = T->arena.peak + (1 << 20);
-    T->arena.dry = false;
-    T->arena.cap = bytes;
-    if (hipMalloc((void**)&T->arena.base, bytes) != hipSuccess) {
-      ctta_set_error("t5_create: hipMalloc of %zu-byte activation arena failed", bytes);
-      st = CTTA_ERR_NOMEM;
-    } else {
-      st = T->splitws.init();
-    }
-  }
-  if (st == CTTA_OK && hipStreamSynchronize(s) != hipSuccess) { ctta_set_error("t5_create: stream sync failed"); st = CTTA_ERR_HIP; }
+  if (st == CTTA_OK) st = T->allocate_after_dry_run("t5_create", 0, 0, false, s);
   if (st != CTTA_OK) { ctta_t5_destroy(T); return st; }
   *out = T;
   return CTTA_OK;
@@ -309,4 +290,4 @@ extern "C" ctta_status ctta_t5_encode(ctta_t5* T, const int64_t* input_ids, cons
   return t5_forward_impl(T, false, input_ids, attention_mask, batch, len, last_hidden_state, (hipStream_t)stream);
 }
 
-extern "C" size_t ctta_t5_arena_bytes(const ctta_t5* T) { return T ? T->arena.cap + T->store.arena.cap : 0; }
+extern "C" size_t ctta_t5_arena_bytes(const ctta_t5* T) { return T ? T->arena_bytes() : 0; }

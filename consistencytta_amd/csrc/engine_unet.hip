@@ -111,11 +111,8 @@ struct TapeOp {
   int block = 0;   // 0 conv_in (+ embeddings), 1..n down blocks, n+1 mid, n+2.. up blocks
 };
 
-struct ctta_unet {
+struct ctta_unet : EngineBase {
   ctta_unet_config cfg;
-  WeightStore store;
-  Arena arena;
-  std::vector<Tap> taps;
   std::vector<Level> down, up;
   Resnet mid_r0, mid_r1;
   Transformer mid_att;
@@ -129,10 +126,6 @@ struct ctta_unet {
   float *g_proj = nullptr, *g_w1 = nullptr, *g_b1 = nullptr, *g_w2 = nullptr, *g_b2 = nullptr;
   float *temb_w = nullptr, *temb_b = nullptr;
   int temb_dim = 0, temb_total = 0, cin_pad = 0, xp = 0;
-  float* gn_scratch = nullptr;
-  size_t gn_scratch_floats = 0;
-  size_t gn_fpart_floats = 0;   // fused-statistics partials, stored behind the gn_scratch_floats of scratch
-  SplitWs splitws;   // this handle's split-K workspace (bound per entry point)
   // Text cache: the cross-attention K / V^T projections of the text states (32 small GEMMs per forward) live in
   // persistent buffers; a caller that queries the same handle again with the SAME text states and mask (the second CFG
   // teacher query of a distillation step, every query of the Heun teacher loop) says so with ctta_unet_reuse_text and
@@ -481,11 +474,7 @@ static ctta_status unet_forward_impl(ctta_unet* U, bool dry, const float* sample
   c.train = train;
   U->ts.valid = false;
   U->tape.clear();
-  c.arena = &U->arena; c.stream = stream; c.dry = dry;
-  c.taps = cfg.debug_taps ? &U->taps : nullptr;
-  c.gn_scratch = U->gn_scratch; c.gn_scratch_floats = U->gn_scratch_floats;
-  if (U->gn_scratch && gn_fuse_enabled()) { c.gn_fpart = U->gn_scratch + U->gn_scratch_floats; c.gn_fpart_floats = U->gn_fpart_floats; }
-  c.gn_groups = cfg.norm_num_groups;
+  U->bind(c, stream, dry, cfg.debug_taps != 0, cfg.norm_num_groups);
   c.U = U; c.B = B; c.L = L; c.Lp = round_up(L, 8);
   c.reuse_text = !dry && !train && U->tc_reuse_next && U->tc_valid && U->tc_base && U->tc_B == B && U->tc_L == L;
   U->tc_reuse_next = false;
@@ -844,11 +833,8 @@ extern "C" ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_
   U->cfg = *cfg;
   ctta_status st = U->store.init(cfg->enable_training ? estimate_store_bytes_training(weights, n_weights)
                                                       : estimate_store_bytes(weights, n_weights));
-  if (st != CTTA_OK) { delete U; return st; }
-  WeightTable wt;
-  wt.build(weights, n_weights);
-  st = unet_build(U);
-  if (st == CTTA_OK) st = U->store.run_all(wt, s);
+  if (st == CTTA_OK) st = unet_build(U);
+  if (st == CTTA_OK) st = U->load_weights(weights, n_weights, s);
   size_t gn_need = 0;
   if (st == CTTA_OK) {   // sizing pass: no launches, measures the arena and the GN scratch
     U->arena.dry = true;
@@ -887,21 +873,9 @@ extern "C" ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_
       if (st != CTTA_OK) ctta_set_error("unet_create: could not create the weight-gradient stream / events");
     }
   }
-  if (st == CTTA_OK) {
-    const size_t bytes = U->arena.peak + (1 << 20);
-    U->arena.dry = false;
-    U->arena.cap = bytes;
-    if (hipMalloc((void**)&U->arena.base, bytes) != hipSuccess ||
-        hipMalloc((void**)&U->gn_scratch, (gn_need + 64 + (U->gn_fpart_floats = (size_t)cfg->max_batch * (cfg->height * cfg->width / 16 + 1) *
-                                                            cfg->norm_num_groups * 2)) * sizeof(float)) != hipSuccess) {
-      ctta_set_error("unet_create: hipMalloc of %zu-byte activation arena failed", bytes);
-      st = CTTA_ERR_NOMEM;
-    } else {
-      U->gn_scratch_floats = gn_need + 64;
-      if (ctta_zero_async(U->arena.base, bytes, s) != hipSuccess) st = CTTA_ERR_HIP;
-      if (st == CTTA_OK) st = U->splitws.init();
-    }
-  }
+  if (st == CTTA_OK)
+    st = U->allocate_after_dry_run("unet_create", gn_need,
+                                   (size_t)cfg->max_batch * (cfg->height * cfg->width / 16 + 1) * cfg->norm_num_groups * 2, true, s);
   if (st == CTTA_OK) {   // text cache: K [B][Lp][hp] + V^T [B][hp][Lp] per transformer block
     std::vector<Transformer*> ts;
     for (Level& Lv : U->down) for (Transformer& T : Lv.att) ts.push_back(&T);
@@ -921,7 +895,6 @@ extern "C" ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_
       }
     }
   }
-  if (st == CTTA_OK && hipStreamSynchronize(s) != hipSuccess) { ctta_set_error("unet_create: stream sync failed"); st = CTTA_ERR_HIP; }
   if (st != CTTA_OK) { ctta_unet_destroy(U); return st; }
   *out = U;
   return CTTA_OK;
@@ -929,11 +902,8 @@ extern "C" ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_
 
 extern "C" void ctta_unet_destroy(ctta_unet* U) {
   if (!U) return;
-  U->store.destroy();
-  if (U->arena.base) (void)hipFree(U->arena.base);
-  if (U->gn_scratch) (void)hipFree(U->gn_scratch);
+  U->destroy_base();
   if (U->tc_base) (void)hipFree(U->tc_base);
-  U->splitws.destroy();
   if (U->wg.stream) { (void)hipStreamSynchronize(U->wg.stream); (void)hipStreamDestroy(U->wg.stream); }
   for (int i = 0; i < ctta_unet::WgradSide::NS; ++i) {
     if (U->wg.ready[i]) (void)hipEventDestroy(U->wg.ready[i]);
@@ -946,10 +916,8 @@ extern "C" void ctta_unet_destroy(ctta_unet* U) {
 
 extern "C" ctta_status ctta_unet_load_weights(ctta_unet* U, const ctta_tensor* weights, int n_weights, void* stream) {
   CTTA_REQUIRE(U && weights, "unet_load_weights: null pointer");
-  WeightTable wt;
-  wt.build(weights, n_weights);
   U->tc_valid = false;   // the cached K / V^T were projected with the old weights
-  return U->store.run_all(wt, (hipStream_t)stream);
+  return U->load_weights(weights, n_weights, (hipStream_t)stream);
 }
 
 extern "C" ctta_status ctta_unet_reuse_text(ctta_unet* U, int reuse) {
@@ -971,23 +939,7 @@ extern "C" ctta_status ctta_unet_forward(ctta_unet* U, const float* sample, cons
                            nullptr);
 }
 
-extern "C" size_t ctta_unet_arena_bytes(const ctta_unet* U) { return U ? U->arena.cap + U->store.arena.cap : 0; }
-extern "C" int ctta_unet_num_taps(const ctta_unet* U) { return U ? (int)U->taps.size() : 0; }
-extern "C" ctta_status ctta_unet_tap_info(const ctta_unet* U, int i, const char** name, int dims[4]) {
-  CTTA_REQUIRE(U && i >= 0 && i < (int)U->taps.size(), "tap index out of range");
-  const Tap& t = U->taps[i];
-  *name = t.name.c_str();
-  dims[0] = t.b; dims[1] = t.c; dims[2] = t.h; dims[3] = t.w;
-  return CTTA_OK;
-}
-extern "C" ctta_status ctta_unet_tap_read(ctta_unet* U, int i, float* dst, void* stream) {
-  CTTA_REQUIRE(U && i >= 0 && i < (int)U->taps.size() && dst, "tap index out of range");
-  const Tap& t = U->taps[i];
-  CTTA_REQUIRE(t.ptr, "tap '%s' has not been produced yet", t.name.c_str());
-  if (t.f32_nchw) {
-    CTTA_CHECK_HIP(hipMemcpyAsync(dst, t.ptr, (size_t)t.b * t.c * t.h * t.w * sizeof(float), hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream));
-    return CTTA_OK;
-  }
-  return ctta_nhwc_bf16_to_nchw_f32(t.ptr, dst, t.b, t.c, t.h, t.w, t.c_stride, stream);
-}
+extern "C" size_t ctta_unet_arena_bytes(const ctta_unet* U) { return U ? U->arena_bytes() : 0; }
+extern "C" int ctta_unet_num_taps(const ctta_unet* U) { return (int)taps_of(U).size(); }
+extern "C" ctta_status ctta_unet_tap_info(const ctta_unet* U, int i, const char** name, int dims[4]) { return tap_info(taps_of(U), i, name, dims); }
+extern "C" ctta_status ctta_unet_tap_read(ctta_unet* U, int i, float* dst, void* stream) { return tap_read(taps_of(U), i, dst, stream); }

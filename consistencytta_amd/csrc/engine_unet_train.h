@@ -549,8 +549,7 @@ static ctta_status bwd_embeddings(BCtx& c) {
 // data-parallel all-reduce of that block's slice of the flat gradient buffer while the next block computes.
 static void bctx_init(BCtx& c, ctta_unet* U, bool dry, const GradTable* grads, hipStream_t stream) {
   const ctta_unet::TrainSaved& S = U->ts;
-  c.arena = &U->arena; c.stream = stream; c.dry = dry; c.taps = nullptr;
-  c.gn_scratch = U->gn_scratch; c.gn_scratch_floats = U->gn_scratch_floats;
+  U->bind(c, stream, dry, false, 0);   // the backward emits no fused GroupNorm statistics
   c.U = U; c.B = S.B; c.L = S.L; c.Lp = S.Lp; c.train = true;
   c.enc_bf = S.enc_bf; c.mask_bias = S.mask_bias; c.grads = grads;
   c.dtemb_all = U->bw.dtemb_all;

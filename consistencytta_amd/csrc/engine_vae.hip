@@ -84,11 +84,8 @@ struct VaeAttn {   // AttnBlock (modules.py:178-230): single head over H*W token
   } sv;
 };
 
-struct ctta_vae {
+struct ctta_vae : EngineBase {
   ctta_vae_config cfg;
-  WeightStore store;
-  Arena arena;
-  std::vector<Tap> taps;
   float *pq_w = nullptr, *pq_b = nullptr;
   ConvLayer conv_in;
   VaeRes mid1, mid2;
@@ -98,10 +95,6 @@ struct ctta_vae {
   GNLayer norm_out;
   ConvLayer conv_out;
   int block_in = 0, c_last = 0;
-  float* gn_scratch = nullptr;
-  size_t gn_scratch_floats = 0;
-  size_t gn_fpart_floats = 0;
-  SplitWs splitws;
   // enable_grad (CLAPLoss's differentiable decode, tools/losses.py:294-296)
   ConvLayer d_conv_in;
   std::vector<ConvLayer> d_upsample;
@@ -275,11 +268,7 @@ static ctta_status vae_forward_impl(ctta_vae* V, bool dry, const float* z, int B
                                     size_t* gn_need, bool grad = false) {
   const ctta_vae_config& cfg = V->cfg;
   VCtx c;
-  c.arena = &V->arena; c.stream = stream; c.dry = dry;
-  c.taps = cfg.debug_taps ? &V->taps : nullptr;
-  c.gn_scratch = V->gn_scratch; c.gn_scratch_floats = V->gn_scratch_floats;
-  if (V->gn_scratch && gn_fuse_enabled()) { c.gn_fpart = V->gn_scratch + V->gn_scratch_floats; c.gn_fpart_floats = V->gn_fpart_floats; }
-  c.gn_groups = 32;
+  V->bind(c, stream, dry, cfg.debug_taps != 0, 32);
   c.B = B;
   c.grad = grad;
   V->sv.B = grad ? B : 0;
@@ -459,11 +448,7 @@ static ctta_status vae_backward_impl(ctta_vae* V, bool dry, const float* gmel, i
                                      size_t* gn_need) {
   const ctta_vae_config& cfg = V->cfg;
   VCtx c;
-  c.arena = &V->arena; c.stream = stream; c.dry = dry;
-  c.taps = nullptr;
-  c.gn_scratch = V->gn_scratch; c.gn_scratch_floats = V->gn_scratch_floats;
-  if (V->gn_scratch && gn_fuse_enabled()) { c.gn_fpart = V->gn_scratch + V->gn_scratch_floats; c.gn_fpart_floats = V->gn_fpart_floats; }
-  c.gn_groups = 32;
+  V->bind(c, stream, dry, false, 32);
   c.B = B;
   Arena& A = V->arena;   // continues above the differentiable forward's saved tensors
   const int up = 1 << (cfg.n_levels - 1);
@@ -549,17 +534,14 @@ extern "C" ctta_status ctta_vae_create(const ctta_vae_config* cfg, const ctta_te
   CTTA_REQUIRE(cfg->out_ch == 1, "vae_create: out_ch=%d (only the 1-channel mel decoder is built)", cfg->out_ch);
   CTTA_REQUIRE(cfg->ch % 32 == 0, "vae_create: ch=%d must be a multiple of 32 (GroupNorm(32))", cfg->ch);
   CTTA_REQUIRE(cfg->scale_factor != 0.f, "vae_create: scale_factor is zero");
+  CTTA_REQUIRE(!cfg->enable_grad || cfg->z_channels % 8 == 0, "vae_create: enable_grad needs z_channels %% 8 == 0");
   hipStream_t s = (hipStream_t)stream;
   ctta_vae* V = new ctta_vae();
   V->cfg = *cfg;
-  CTTA_REQUIRE(!cfg->enable_grad || cfg->z_channels % 8 == 0, "vae_create: enable_grad needs z_channels %% 8 == 0");
   ctta_status st = V->store.init(cfg->enable_grad ? estimate_store_bytes_training(weights, n_weights)
                                                   : estimate_store_bytes(weights, n_weights));
-  if (st != CTTA_OK) { delete V; return st; }
-  WeightTable wt;
-  wt.build(weights, n_weights);
-  st = vae_build(V);
-  if (st == CTTA_OK) st = V->store.run_all(wt, s);
+  if (st == CTTA_OK) st = vae_build(V);
+  if (st == CTTA_OK) st = V->load_weights(weights, n_weights, s);
   size_t gn_need = 0;
   if (st == CTTA_OK) {
     V->arena.dry = true;
@@ -570,21 +552,9 @@ extern "C" ctta_status ctta_vae_create(const ctta_vae_config* cfg, const ctta_te
       if (st == CTTA_OK) st = vae_backward_impl(V, true, nullptr, cfg->max_batch, nullptr, s, &gn_need);
     }
   }
-  if (st == CTTA_OK) {
-    const size_t bytes = V->arena.peak + (1 << 20);
-    V->arena.dry = false;
-    V->arena.cap = bytes;
-    if (hipMalloc((void**)&V->arena.base, bytes) != hipSuccess ||
-        hipMalloc((void**)&V->gn_scratch, (gn_need + 64 + (V->gn_fpart_floats = (size_t)cfg->max_batch *
-                                                            ((size_t)cfg->latent_h * cfg->latent_w * 16 / 16 + 1) * 32 * 2)) * sizeof(float)) != hipSuccess) {
-      ctta_set_error("vae_create: hipMalloc of %zu-byte activation arena failed", bytes);
-      st = CTTA_ERR_NOMEM;
-    } else {
-      V->gn_scratch_floats = gn_need + 64;
-      st = V->splitws.init();
-    }
-  }
-  if (st == CTTA_OK && hipStreamSynchronize(s) != hipSuccess) { ctta_set_error("vae_create: stream sync failed"); st = CTTA_ERR_HIP; }
+  if (st == CTTA_OK)
+    st = V->allocate_after_dry_run("vae_create", gn_need,
+                                   (size_t)cfg->max_batch * ((size_t)cfg->latent_h * cfg->latent_w * 16 / 16 + 1) * 32 * 2, false, s);
   if (st != CTTA_OK) { ctta_vae_destroy(V); return st; }
   *out = V;
   return CTTA_OK;
@@ -592,10 +562,7 @@ extern "C" ctta_status ctta_vae_create(const ctta_vae_config* cfg, const ctta_te
 
 extern "C" void ctta_vae_destroy(ctta_vae* V) {
   if (!V) return;
-  V->store.destroy();
-  if (V->arena.base) (void)hipFree(V->arena.base);
-  if (V->gn_scratch) (void)hipFree(V->gn_scratch);
-  V->splitws.destroy();
+  V->destroy_base();
   delete V;
 }
 
@@ -624,32 +591,18 @@ extern "C" ctta_status ctta_vae_decode_backward(ctta_vae* V, const float* grad_m
   return st;
 }
 
-extern "C" size_t ctta_vae_arena_bytes(const ctta_vae* V) { return V ? V->arena.cap + V->store.arena.cap : 0; }
-extern "C" int ctta_vae_num_taps(const ctta_vae* V) { return V ? (int)V->taps.size() : 0; }
-extern "C" ctta_status ctta_vae_tap_info(const ctta_vae* V, int i, const char** name, int dims[4]) {
-  CTTA_REQUIRE(V && i >= 0 && i < (int)V->taps.size(), "tap index out of range");
-  const Tap& t = V->taps[i];
-  *name = t.name.c_str();
-  dims[0] = t.b; dims[1] = t.c; dims[2] = t.h; dims[3] = t.w;
-  return CTTA_OK;
-}
-extern "C" ctta_status ctta_vae_tap_read(ctta_vae* V, int i, float* dst, void* stream) {
-  CTTA_REQUIRE(V && i >= 0 && i < (int)V->taps.size() && dst, "tap index out of range");
-  const Tap& t = V->taps[i];
-  CTTA_REQUIRE(t.ptr, "tap '%s' has not been produced yet", t.name.c_str());
-  return ctta_nhwc_bf16_to_nchw_f32(t.ptr, dst, t.b, t.c, t.h, t.w, t.c_stride, stream);
-}
+extern "C" size_t ctta_vae_arena_bytes(const ctta_vae* V) { return V ? V->arena_bytes() : 0; }
+extern "C" int ctta_vae_num_taps(const ctta_vae* V) { return (int)taps_of(V).size(); }
+extern "C" ctta_status ctta_vae_tap_info(const ctta_vae* V, int i, const char** name, int dims[4]) { return tap_info(taps_of(V), i, name, dims); }
+extern "C" ctta_status ctta_vae_tap_read(ctta_vae* V, int i, float* dst, void* stream) { return tap_read(taps_of(V), i, dst, stream); }
 
 // ====================================================================================== VAE encoder
 // AutoencoderKL.encode (autoencoder.py:80-85): Encoder.forward (modules.py:519-543) + quant_conv, the training-side
 // latent encoder (tools/train_utils.py:155-162 encodes every batch).  Same blocks as the decoder; Downsample
 // (modules.py:87-92) = zero-pad right/bottom by one + 3x3 stride-2 conv, which is conv_gemm with pad 0 and the
 // output extent H/2 x W/2 (the out-of-image tap reads zeros).
-struct ctta_vae_encoder {
+struct ctta_vae_encoder : EngineBase {
   ctta_vae_config cfg;
-  WeightStore store;
-  Arena arena;
-  std::vector<Tap> taps;
   ConvLayer conv_in;
   std::vector<std::vector<VaeRes>> down;   // [level][block]
   std::vector<ConvLayer> downsample;       // [level] (last level unused)
@@ -659,10 +612,6 @@ struct ctta_vae_encoder {
   ConvLayer conv_out;
   float *q_w = nullptr, *q_b = nullptr;    // quant_conv (1x1) in fp32
   int block_in = 0, zc2 = 0;
-  float* gn_scratch = nullptr;
-  size_t gn_scratch_floats = 0;
-  size_t gn_fpart_floats = 0;
-  SplitWs splitws;
 };
 
 // moments[b][o][hw] = quant_conv(h)[o] per pixel, h = conv_out result [M][zc2] bf16 -> NCHW fp32
@@ -684,11 +633,7 @@ static ctta_status vae_encode_impl(ctta_vae_encoder* E, bool dry, const float* m
                                    hipStream_t stream, size_t* gn_need) {
   const ctta_vae_config& cfg = E->cfg;
   VCtx c;
-  c.arena = &E->arena; c.stream = stream; c.dry = dry;
-  c.taps = cfg.debug_taps ? &E->taps : nullptr;
-  c.gn_scratch = E->gn_scratch; c.gn_scratch_floats = E->gn_scratch_floats;
-  if (E->gn_scratch && gn_fuse_enabled()) { c.gn_fpart = E->gn_scratch + E->gn_scratch_floats; c.gn_fpart_floats = E->gn_fpart_floats; }
-  c.gn_groups = 32;
+  E->bind(c, stream, dry, cfg.debug_taps != 0, 32);
   c.B = B;
   Arena& A = E->arena;
   A.reset();
@@ -776,10 +721,7 @@ static ctta_status vae_encoder_build(ctta_vae_encoder* E) {
 
 extern "C" void ctta_vae_encoder_destroy(ctta_vae_encoder* E) {
   if (!E) return;
-  E->store.destroy();
-  if (E->arena.base) (void)hipFree(E->arena.base);
-  if (E->gn_scratch) (void)hipFree(E->gn_scratch);
-  E->splitws.destroy();
+  E->destroy_base();
   delete E;
 }
 
@@ -795,32 +737,17 @@ extern "C" ctta_status ctta_vae_encoder_create(const ctta_vae_config* cfg, const
   ctta_vae_encoder* E = new ctta_vae_encoder();
   E->cfg = *cfg;
   ctta_status st = E->store.init(estimate_store_bytes(weights, n_weights));
-  if (st != CTTA_OK) { delete E; return st; }
-  WeightTable wt;
-  wt.build(weights, n_weights);
-  st = vae_encoder_build(E);
-  if (st == CTTA_OK) st = E->store.run_all(wt, s);
+  if (st == CTTA_OK) st = vae_encoder_build(E);
+  if (st == CTTA_OK) st = E->load_weights(weights, n_weights, s);
   size_t gn_need = 0;
   if (st == CTTA_OK) {
     E->arena.dry = true;
     E->arena.no_release = cfg->debug_taps != 0;
     st = vae_encode_impl(E, true, nullptr, cfg->max_batch, nullptr, s, &gn_need);
   }
-  if (st == CTTA_OK) {
-    const size_t bytes = E->arena.peak + (1 << 20);
-    E->arena.dry = false;
-    E->arena.cap = bytes;
-    if (hipMalloc((void**)&E->arena.base, bytes) != hipSuccess ||
-        hipMalloc((void**)&E->gn_scratch, (gn_need + 64 + (E->gn_fpart_floats = (size_t)cfg->max_batch *
-                                                            ((size_t)cfg->latent_h * cfg->latent_w * 16 / 16 + 1) * 32 * 2)) * sizeof(float)) != hipSuccess) {
-      ctta_set_error("vae_encoder_create: hipMalloc of %zu-byte activation arena failed", bytes);
-      st = CTTA_ERR_NOMEM;
-    } else {
-      E->gn_scratch_floats = gn_need + 64;
-      st = E->splitws.init();
-    }
-  }
-  if (st == CTTA_OK && hipStreamSynchronize(s) != hipSuccess) { ctta_set_error("vae_encoder_create: stream sync failed"); st = CTTA_ERR_HIP; }
+  if (st == CTTA_OK)
+    st = E->allocate_after_dry_run("vae_encoder_create", gn_need,
+                                   (size_t)cfg->max_batch * ((size_t)cfg->latent_h * cfg->latent_w * 16 / 16 + 1) * 32 * 2, false, s);
   if (st != CTTA_OK) { ctta_vae_encoder_destroy(E); return st; }
   *out = E;
   return CTTA_OK;
@@ -835,24 +762,11 @@ extern "C" ctta_status ctta_vae_encode(ctta_vae_encoder* E, const float* mel, in
 extern "C" ctta_status ctta_vae_encoder_load_weights(ctta_vae_encoder* E, const ctta_tensor* weights, int n_weights,
                                                      void* stream) {
   CTTA_REQUIRE(E && weights, "vae_encoder_load_weights: null pointer");
-  WeightTable wt;
-  wt.build(weights, n_weights);
-  return E->store.run_all(wt, (hipStream_t)stream);
+  return E->load_weights(weights, n_weights, (hipStream_t)stream);
 }
-extern "C" int ctta_vae_encoder_num_taps(const ctta_vae_encoder* E) { return E ? (int)E->taps.size() : 0; }
-extern "C" ctta_status ctta_vae_encoder_tap_info(const ctta_vae_encoder* E, int i, const char** name, int dims[4]) {
-  CTTA_REQUIRE(E && i >= 0 && i < (int)E->taps.size(), "tap index out of range");
-  const Tap& t = E->taps[i];
-  *name = t.name.c_str();
-  dims[0] = t.b; dims[1] = t.c; dims[2] = t.h; dims[3] = t.w;
-  return CTTA_OK;
-}
-extern "C" ctta_status ctta_vae_encoder_tap_read(ctta_vae_encoder* E, int i, float* dst, void* stream) {
-  CTTA_REQUIRE(E && i >= 0 && i < (int)E->taps.size() && dst, "tap index out of range");
-  const Tap& t = E->taps[i];
-  CTTA_REQUIRE(t.ptr, "tap '%s' has not been produced yet", t.name.c_str());
-  return ctta_nhwc_bf16_to_nchw_f32(t.ptr, dst, t.b, t.c, t.h, t.w, t.c_stride, stream);
-}
+extern "C" int ctta_vae_encoder_num_taps(const ctta_vae_encoder* E) { return (int)taps_of(E).size(); }
+extern "C" ctta_status ctta_vae_encoder_tap_info(const ctta_vae_encoder* E, int i, const char** name, int dims[4]) { return tap_info(taps_of(E), i, name, dims); }
+extern "C" ctta_status ctta_vae_encoder_tap_read(ctta_vae_encoder* E, int i, float* dst, void* stream) { return tap_read(taps_of(E), i, dst, stream); }
 
 // ====================================================================================== HiFi-GAN
 struct Conv1d {
@@ -874,12 +788,8 @@ struct HResBlock {
   const bf16_t* sv_ract[3] = {nullptr, nullptr, nullptr};  // leaky_relu of the residual stream entering unit m
 };
 
-struct ctta_hifigan {
+struct ctta_hifigan : EngineBase {   // no GroupNorm: gn_scratch stays null
   ctta_hifigan_config cfg;
-  WeightStore store;
-  Arena arena;
-  SplitWs splitws;
-  std::vector<Tap> taps;
   Conv1d conv_pre;
   std::vector<ConvT1d> ups;
   std::vector<HResBlock> res;   // [n_ups * n_kernels]
@@ -1013,9 +923,7 @@ static ctta_status hifigan_forward_impl(ctta_hifigan* G, bool dry, const float* 
                                         hipStream_t stream, bool grad = false) {
   const ctta_hifigan_config& cfg = G->cfg;
   RunCtx c;
-  c.arena = &G->arena; c.stream = stream; c.dry = dry;
-  c.taps = cfg.debug_taps ? &G->taps : nullptr;
-  c.gn_scratch = nullptr; c.gn_scratch_floats = 0;
+  G->bind(c, stream, dry, cfg.debug_taps != 0, 0);
   Arena& A = G->arena;
   A.reset();
   const int nk = cfg.n_kernels;
@@ -1148,8 +1056,7 @@ static ctta_status hifigan_backward_impl(ctta_hifigan* G, bool dry, const float*
                                          hipStream_t stream) {
   const ctta_hifigan_config& cfg = G->cfg;
   RunCtx c;
-  c.arena = &G->arena; c.stream = stream; c.dry = dry;
-  c.taps = cfg.debug_taps ? &G->taps : nullptr; c.gn_scratch = nullptr; c.gn_scratch_floats = 0;
+  G->bind(c, stream, dry, cfg.debug_taps != 0, 0);
   Arena& A = G->arena;   // continues above the differentiable forward's saved tensors
   const int nk = cfg.n_kernels, last = cfg.n_ups - 1;
   int len = G->sv.len[last], ch = G->c_last;
@@ -1273,11 +1180,8 @@ extern "C" ctta_status ctta_hifigan_create(const ctta_hifigan_config* cfg, const
   G->cfg = *cfg;
   ctta_status st = G->store.init(cfg->enable_grad ? estimate_store_bytes_training(weights, n_weights)
                                                   : estimate_store_bytes(weights, n_weights));
-  if (st != CTTA_OK) { delete G; return st; }
-  WeightTable wt;
-  wt.build(weights, n_weights);
-  st = hifigan_build(G);
-  if (st == CTTA_OK) st = G->store.run_all(wt, s);
+  if (st == CTTA_OK) st = hifigan_build(G);
+  if (st == CTTA_OK) st = G->load_weights(weights, n_weights, s);
   if (st == CTTA_OK) {
     G->arena.dry = true;
     G->arena.no_release = cfg->debug_taps != 0;
@@ -1288,18 +1192,7 @@ extern "C" ctta_status ctta_hifigan_create(const ctta_hifigan_config* cfg, const
       G->sv.B = 0;
     }
   }
-  if (st == CTTA_OK) {
-    const size_t bytes = G->arena.peak + (1 << 20);
-    G->arena.dry = false;
-    G->arena.cap = bytes;
-    if (hipMalloc((void**)&G->arena.base, bytes) != hipSuccess) {
-      ctta_set_error("hifigan_create: hipMalloc of %zu-byte activation arena failed", bytes);
-      st = CTTA_ERR_NOMEM;
-    } else {
-      st = G->splitws.init();
-    }
-  }
-  if (st == CTTA_OK && hipStreamSynchronize(s) != hipSuccess) { ctta_set_error("hifigan_create: stream sync failed"); st = CTTA_ERR_HIP; }
+  if (st == CTTA_OK) st = G->allocate_after_dry_run("hifigan_create", 0, 0, false, s);
   if (st != CTTA_OK) { ctta_hifigan_destroy(G); return st; }
   *out = G;
   return CTTA_OK;
@@ -1307,9 +1200,7 @@ extern "C" ctta_status ctta_hifigan_create(const ctta_hifigan_config* cfg, const
 
 extern "C" void ctta_hifigan_destroy(ctta_hifigan* G) {
   if (!G) return;
-  G->store.destroy();
-  if (G->arena.base) (void)hipFree(G->arena.base);
-  G->splitws.destroy();
+  G->destroy_base();
   delete G;
 }
 
@@ -1344,18 +1235,7 @@ extern "C" ctta_status ctta_hifigan_backward(ctta_hifigan* G, const float* grad_
   return st;
 }
 
-extern "C" size_t ctta_hifigan_arena_bytes(const ctta_hifigan* G) { return G ? G->arena.cap + G->store.arena.cap : 0; }
-extern "C" int ctta_hifigan_num_taps(const ctta_hifigan* G) { return G ? (int)G->taps.size() : 0; }
-extern "C" ctta_status ctta_hifigan_tap_info(const ctta_hifigan* G, int i, const char** name, int dims[4]) {
-  CTTA_REQUIRE(G && i >= 0 && i < (int)G->taps.size(), "tap index out of range");
-  const Tap& t = G->taps[i];
-  *name = t.name.c_str();
-  dims[0] = t.b; dims[1] = t.c; dims[2] = t.h; dims[3] = t.w;
-  return CTTA_OK;
-}
-extern "C" ctta_status ctta_hifigan_tap_read(ctta_hifigan* G, int i, float* dst, void* stream) {
-  CTTA_REQUIRE(G && i >= 0 && i < (int)G->taps.size() && dst, "tap index out of range");
-  const Tap& t = G->taps[i];
-  CTTA_REQUIRE(t.ptr, "tap '%s' has not been produced yet", t.name.c_str());
-  return ctta_nhwc_bf16_to_nchw_f32(t.ptr, dst, t.b, t.c, t.h, t.w, t.c_stride, stream);
-}
+extern "C" size_t ctta_hifigan_arena_bytes(const ctta_hifigan* G) { return G ? G->arena_bytes() : 0; }
+extern "C" int ctta_hifigan_num_taps(const ctta_hifigan* G) { return (int)taps_of(G).size(); }
+extern "C" ctta_status ctta_hifigan_tap_info(const ctta_hifigan* G, int i, const char** name, int dims[4]) { return tap_info(taps_of(G), i, name, dims); }
+extern "C" ctta_status ctta_hifigan_tap_read(ctta_hifigan* G, int i, float* dst, void* stream) { return tap_read(taps_of(G), i, dst, stream); }

@@ -1504,7 +1504,7 @@ class _DistillStepGraph:
             torch.cuda.current_stream(self.dev).wait_stream(warm)
             torch.cuda.synchronize(self.dev)
             for net in (m.student_unet, m.student_target_unet):   # their bf16 re-pack belongs to every replay
-                net._h_version = None
+                net._engine.version = None
             if self.pipelined:
                 self.teacher_graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.teacher_graph, stream=warm, capture_error_mode="thread_local"):

@@ -220,15 +220,19 @@ class _ParamTree(nn.Module):
         return sd
 
     # handles are not copyable / picklable: a deepcopy (audio_consistency_model.py:65) gets fresh ones
+    @staticmethod
+    def _without_handles(k, v):
+        """(handled, value a copy gets): empty holders of the same kind, nothing native"""
+        if isinstance(v, N.EngineHandle):
+            return True, N.EngineHandle(v.destroy)
+        if k == "_eng":
+            return True, {w: [N.EngineHandle(e.destroy) for e in es] for w, es in v.items()}
+        if k.startswith("_h_") or k in ("_vae_pending", "_voc_pending"):
+            return True, None
+        return False, v
+
     def __getstate__(self):
-        d = self.__dict__.copy()
-        for k in list(d):
-            if k.startswith("_h_"):
-                d[k] = None
-        if "_eng" in d:
-            d["_eng"] = {"vae": [None, None], "voc": [None, None]}
-            d["_vae_pending"] = d["_voc_pending"] = None
-        return d
+        return {k: self._without_handles(k, v)[1] for k, v in self.__dict__.items()}
 
     def __deepcopy__(self, memo):
         import copy
@@ -236,12 +240,8 @@ class _ParamTree(nn.Module):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k == "_eng":
-                new.__dict__[k] = {"vae": [None, None], "voc": [None, None]}
-            elif k in ("_vae_pending", "_voc_pending"):
-                new.__dict__[k] = None
-            else:
-                new.__dict__[k] = None if k.startswith(("_h_", "_flat")) else copy.deepcopy(v, memo)
+            handled, fresh = self._without_handles(k, v)
+            new.__dict__[k] = fresh if handled else None if k.startswith("_flat") else copy.deepcopy(v, memo)
         return new
 
 
@@ -270,9 +270,7 @@ class _UNetBase(_ParamTree):
         self._cfg = cfg
         frozen = ("guidance_proj.weight",)  # embeddings.py:229 requires_grad=False
         self._register(spec.unet_param_spec(cfg, self._guided), frozen)
-        self._h_unet = None
-        self._h_key = None
-        self._h_version = None
+        self._engine = N.EngineHandle("ctta_unet_destroy")
         self.debug_taps = False
         self.enable_training = False   # True: the native handle also carries the backward pass
 
@@ -313,38 +311,27 @@ class _UNetBase(_ParamTree):
         c.enable_training = int(self.enable_training)
         return c
 
-    def _release(self):
-        if getattr(self, "_h_unet", None):
-            N.lib().ctta_unet_destroy(self._h_unet)
-        self._h_unet = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+    @property
+    def _h_unet(self):
+        return self._engine.h
 
     def _ensure(self, B, H, W, L):
-        L_ = N.lib()
-        key = self._h_key
-        need_new = (self._h_unet is None or key is None or key[1:3] != (H, W) or B > key[0] or L > key[3]
-                    or key[4] != (self.debug_taps, self.enable_training) or key[5] != self.device)
+        """Capacity (max_batch, max_text_len) only grows at a fixed (H, W); max_text_len is never below 32 and survives
+        an extent change, max_batch does not.  Changed weights are re-packed into the SAME handle."""
+        L_, e = N.lib(), self._engine
+        key = (H, W, self.debug_taps, self.enable_training, self.device)
         ver = self._weights_version()
-        if need_new:
-            self._release()
-            Bm = max(B, key[0]) if key and key[1:3] == (H, W) else B
-            Lm = max(L, key[3], 32) if key else max(L, 32)
+        if not e.fits((B, L), key, e.version):
+            Bm = max(B, e.capacity[0]) if e.key and e.key[:2] == (H, W) else B
+            Lm = max(L, e.capacity[1], 32) if e.key else max(L, 32)
             table, keep = N.tensor_table(self._table())
-            h = N.c_void_p()
             cfg = self._native_config(Bm, H, W, Lm)
-            with torch.cuda.device(self.device):
-                N.check(L_.ctta_unet_create(cfg, table, len(table), N.stream_ptr(), h))
-            self._h_unet, self._h_key, self._h_version = (
-                h, (Bm, H, W, Lm, (self.debug_taps, self.enable_training), self.device), ver)
-        elif ver != self._h_version:  # parameters changed (optimizer / EMA / load_state_dict)
+            e.replace(lambda h: L_.ctta_unet_create(cfg, table, len(table), N.stream_ptr(), h), (Bm, Lm), key, ver,
+                      self.device)
+        elif ver != e.version:  # parameters changed (optimizer / EMA / load_state_dict)
             table, keep = N.tensor_table(self._table())
-            N.check(L_.ctta_unet_load_weights(self._h_unet, table, len(table), N.stream_ptr()))
-            self._h_version = ver
+            N.check(L_.ctta_unet_load_weights(e.h, table, len(table), N.stream_ptr()))
+            e.version = ver
 
     @staticmethod
     def _per_sample(v, B, device, dtype):
@@ -391,10 +378,10 @@ class _UNetBase(_ParamTree):
         dev = self.device
         if not sample.is_cuda:
             raise N.CttaError("sample is on %s: the HIP engine has no CPU path" % sample.device)
-        had_handle, ver0 = self._h_unet is not None, self._h_version
+        had_handle, ver0 = self._h_unet is not None, self._engine.version
         self._ensure(B, H, W, L)
         reuse = self._text_unchanged(encoder_hidden_states, encoder_attention_mask, B, reuse_text)
-        reuse = reuse and not train and had_handle and ver0 == self._h_version       # same handle, same packed weights
+        reuse = reuse and not train and had_handle and ver0 == self._engine.version  # same handle, same packed weights
         x = sample.detach().to(device=dev, dtype=torch.float32).contiguous()
         enc = encoder_hidden_states.detach().to(device=dev, dtype=torch.float32).contiguous()
         t = self._per_sample(timestep, B, dev, torch.float32)  # get_timestep_embedding casts to fp32
@@ -511,16 +498,7 @@ class _UNetBase(_ParamTree):
 
     def read_taps(self):
         """name -> NCHW fp32 tensor of every recorded intermediate (debug_taps=True only)."""
-        L_ = N.lib()
-        out = OrderedDict()
-        for i in range(L_.ctta_unet_num_taps(self._h_unet)):
-            name = N.c_char_p()
-            dims = (N.c_int * 4)()
-            N.check(L_.ctta_unet_tap_info(self._h_unet, i, name, dims))
-            t = torch.empty(tuple(dims), dtype=torch.float32, device=self.device)
-            N.check(L_.ctta_unet_tap_read(self._h_unet, i, N.ptr(t), N.stream_ptr()))
-            out[name.value.decode()] = t
-        return out
+        return N.read_taps("ctta_unet", self._h_unet, self.device)
 
 
 class UNet2DConditionGuidedModel(_UNetBase):
@@ -612,7 +590,7 @@ class _VaeDecodeWithGrad(torch.autograd.Function):
         g = grad_mel.to(device=vae.device, dtype=torch.float32).contiguous()
         gz = torch.empty(ctx.shape, dtype=torch.float32, device=vae.device)
         with torch.cuda.device(vae.device):
-            N.check(N.lib().ctta_vae_decode_backward(vae._eng["vae"][1]["h"], N.ptr(g), ctx.shape[0], N.ptr(gz), N.stream_ptr()))
+            N.check(N.lib().ctta_vae_decode_backward(vae._eng["vae"][1].h, N.ptr(g), ctx.shape[0], N.ptr(gz), N.stream_ptr()))
         vae._vae_pending = None
         return gz.to(ctx.dtype), None
 
@@ -649,7 +627,7 @@ class _VocodeWithGrad(torch.autograd.Function):
         g = grad_wav.to(device=vae.device, dtype=torch.float32).contiguous()
         gm = torch.empty(ctx.shape, dtype=torch.float32, device=vae.device)
         with torch.cuda.device(vae.device):
-            N.check(N.lib().ctta_hifigan_backward(vae._eng["voc"][1]["h"], N.ptr(g), N.ptr(wav), B, T, N.ptr(gm), N.stream_ptr()))
+            N.check(N.lib().ctta_hifigan_backward(vae._eng["voc"][1].h, N.ptr(g), N.ptr(wav), B, T, N.ptr(gm), N.stream_ptr()))
         vae._voc_pending = None
         return gm.to(ctx.dtype), None
 
@@ -689,11 +667,12 @@ class AutoencoderKL(_ParamTree):
         table.update((k, v) for k, v in dec.items() if k.startswith("post_quant_conv."))
         self._register(table)
         self.vocoder = Generator(hifigan_config)
-        self._h_enc = self._h_enc_key = self._h_enc_ver = None
+        self._enc = N.EngineHandle("ctta_vae_encoder_destroy")
         self.ema_decoder = None
         # engine handles: [plain, differentiable] per stage -- separate handles, so that a plain decode (e.g. of the
         # target latent in MelLoss) never disturbs the tensors a pending differentiable decode saved for its backward
-        self._eng = {"vae": [None, None], "voc": [None, None]}
+        self._eng = {"vae": [N.EngineHandle("ctta_vae_destroy") for _ in range(2)],
+                     "voc": [N.EngineHandle("ctta_hifigan_destroy") for _ in range(2)]}
         self._h_vae = self._h_voc = None     # the handle each stage used last (debug taps)
         self._vae_pending = self._voc_pending = None
         self.debug_taps = False
@@ -730,11 +709,9 @@ class AutoencoderKL(_ParamTree):
         if T % s or F % s:
             raise ValueError("mel extent %dx%d must be a multiple of %d" % (T, F, s))
         key = (T, F, self.debug_taps, self.device)
-        ver = sum(p._version for k, p in self.named_parameters() if k.startswith(("encoder.", "quant_conv.")))
-        if self._h_enc is None or self._h_enc_key[1:] != key or B > self._h_enc_key[0] or ver != self._h_enc_ver:
-            if self._h_enc is not None:
-                L_.ctta_vae_encoder_destroy(self._h_enc)
-                self._h_enc = None
+        named = [(k, p) for k, p in self.named_parameters() if k.startswith(("encoder.", "quant_conv."))]
+        ver = sum(p._version for k, p in named)
+        if not self._enc.fits((B,), key, ver):
             dd = self.ddconfig
             c = N.VAEConfig()
             c.z_channels, c.embed_dim, c.ch, c.out_ch = dd["z_channels"], self.embed_dim, dd["ch"], dd["in_channels"]
@@ -744,17 +721,10 @@ class AutoencoderKL(_ParamTree):
             c.scale_factor = float(self.scale_factor)
             c.max_batch, c.latent_h, c.latent_w = B, T // s, F // s
             c.debug_taps = int(self.debug_taps)
-            sd = OrderedDict((k, p.detach()) for k, p in self.named_parameters()
-                             if k.startswith(("encoder.", "quant_conv.")))
-            for k, p in sd.items():
-                if not p.is_cuda:
-                    raise N.CttaError("parameter '%s' is on %s: the HIP engine has no CPU path" % (k, p.device))
-            table, keep = N.tensor_table(sd)
-            h = N.c_void_p()
-            with torch.cuda.device(self.device):
-                N.check(L_.ctta_vae_encoder_create(c, table, len(table), N.stream_ptr(), h))
-            self._h_enc, self._h_enc_key, self._h_enc_ver = h, (B,) + key, ver
-        return self._h_enc
+            table, keep = N.param_table(named)
+            self._enc.replace(lambda h: L_.ctta_vae_encoder_create(c, table, len(table), N.stream_ptr(), h), (B,), key, ver,
+                              self.device)
+        return self._enc.h
 
     @torch.no_grad()
     def encode(self, x):
@@ -786,51 +756,16 @@ class AutoencoderKL(_ParamTree):
         return self.scale_factor * z
 
     def read_encoder_taps(self):
-        L_ = N.lib()
-        out = OrderedDict()
-        for i in range(L_.ctta_vae_encoder_num_taps(self._h_enc)):
-            name = N.c_char_p()
-            dims = (N.c_int * 4)()
-            N.check(L_.ctta_vae_encoder_tap_info(self._h_enc, i, name, dims))
-            t = torch.empty(tuple(dims), dtype=torch.float32, device=self.device)
-            N.check(L_.ctta_vae_encoder_tap_read(self._h_enc, i, N.ptr(t), N.stream_ptr()))
-            out[name.value.decode()] = t
-        return out
-
-    def _release(self):
-        eng = getattr(self, "_eng", None) or {"vae": [], "voc": []}
-        live = [e for v in eng.values() for e in v if e]
-        L_ = N.lib() if (live or getattr(self, "_h_enc", None)) else None
-        if getattr(self, "_h_enc", None):
-            L_.ctta_vae_encoder_destroy(self._h_enc)
-            self._h_enc = None
-        for which, destroy in (("vae", "ctta_vae_destroy"), ("voc", "ctta_hifigan_destroy")):
-            for i, e in enumerate(eng[which]):
-                if e:
-                    getattr(L_, destroy)(e["h"])
-                    eng[which][i] = None
-        self._h_vae = self._h_voc = None
-        self._vae_pending = self._voc_pending = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _decoder_version(self):
-        return sum(p._version for k, p in self.named_parameters() if k.startswith(("decoder.", "post_quant_conv.")))
+        return N.read_taps("ctta_vae_encoder", self._enc.h, self.device)
 
     def _ensure_vae(self, B, T, F, grad=False):
         L_ = N.lib()
         sf = float(self.scale_factor)
         key = (T, F, sf, self.debug_taps, self.device)
-        ver = self._decoder_version()
+        named = [(k, p) for k, p in self.named_parameters() if k.startswith(("decoder.", "post_quant_conv."))]
+        ver = sum(p._version for k, p in named)
         e = self._eng["vae"][int(grad)]
-        if e is None or e["key"] != key or B > e["B"] or ver != e["ver"]:
-            if e is not None:
-                L_.ctta_vae_destroy(e["h"])
-                self._eng["vae"][int(grad)] = None
+        if not e.fits((B,), key, ver):
             dd = self.ddconfig
             c = N.VAEConfig()
             c.z_channels, c.embed_dim, c.ch, c.out_ch = dd["z_channels"], self.embed_dim, dd["ch"], dd["out_ch"]
@@ -843,28 +778,18 @@ class AutoencoderKL(_ParamTree):
             c.enable_grad = int(grad)
             if grad:
                 self._vae_pending = None
-            sd = OrderedDict((k, p.detach()) for k, p in self.named_parameters()
-                             if k.startswith(("decoder.", "post_quant_conv.")))
-            for k, p in sd.items():
-                if not p.is_cuda:
-                    raise N.CttaError("parameter '%s' is on %s: the HIP engine has no CPU path" % (k, p.device))
-            table, keep = N.tensor_table(sd)
-            h = N.c_void_p()
-            with torch.cuda.device(self.device):
-                N.check(L_.ctta_vae_create(c, table, len(table), N.stream_ptr(), h))
-            e = self._eng["vae"][int(grad)] = {"h": h, "key": key, "B": B, "ver": ver}
-        self._h_vae = e["h"]
-        return e["h"]
+            table, keep = N.param_table(named)
+            e.replace(lambda h: L_.ctta_vae_create(c, table, len(table), N.stream_ptr(), h), (B,), key, ver, self.device)
+        self._h_vae = e.h
+        return e.h
 
     def _ensure_voc(self, B, frames, grad=False):
         L_ = N.lib()
-        ver = sum(p._version for p in self.vocoder.parameters())
+        named = [("vocoder." + k, p) for k, p in self.vocoder.named_parameters()]
+        ver = sum(p._version for k, p in named)
         key = (self.debug_taps, self.device)
         e = self._eng["voc"][int(grad)]
-        if e is None or e["key"] != key or B > e["B"] or frames > e["frames"] or ver != e["ver"]:
-            if e is not None:
-                L_.ctta_hifigan_destroy(e["h"])
-                self._eng["voc"][int(grad)] = None
+        if not e.fits((B, frames), key, ver):
             h_ = self.vocoder.h
             c = N.HifiganConfig()
             c.num_mels, c.upsample_initial_channel = h_["num_mels"], h_["upsample_initial_channel"]
@@ -879,17 +804,11 @@ class AutoencoderKL(_ParamTree):
             c.enable_grad = int(grad)
             if grad:
                 self._voc_pending = None
-            sd = OrderedDict(("vocoder." + k, p.detach()) for k, p in self.vocoder.named_parameters())
-            for k, p in sd.items():
-                if not p.is_cuda:
-                    raise N.CttaError("parameter '%s' is on %s: the HIP engine has no CPU path" % (k, p.device))
-            table, keep = N.tensor_table(sd)
-            h = N.c_void_p()
-            with torch.cuda.device(self.device):
-                N.check(L_.ctta_hifigan_create(c, table, len(table), N.stream_ptr(), h))
-            e = self._eng["voc"][int(grad)] = {"h": h, "key": key, "B": B, "frames": frames, "ver": ver}
-        self._h_voc = e["h"]
-        return e["h"]
+            table, keep = N.param_table(named)
+            e.replace(lambda h: L_.ctta_hifigan_create(c, table, len(table), N.stream_ptr(), h), (B, frames), key, ver,
+                      self.device)
+        self._h_voc = e.h
+        return e.h
 
     # ---- reference API
     def decode(self, z, use_ema=False):
@@ -961,17 +880,6 @@ class AutoencoderKL(_ParamTree):
         return centred if return_float else pcm.cpu().numpy()
 
     def _read_taps(self, which):
-        L_ = N.lib()
-        h = self._h_vae if which == "vae" else self._h_voc
-        num = getattr(L_, "ctta_%s_num_taps" % ("vae" if which == "vae" else "hifigan"))
-        info = getattr(L_, "ctta_%s_tap_info" % ("vae" if which == "vae" else "hifigan"))
-        read = getattr(L_, "ctta_%s_tap_read" % ("vae" if which == "vae" else "hifigan"))
-        out = OrderedDict()
-        for i in range(num(h)):
-            name = N.c_char_p()
-            dims = (N.c_int * 4)()
-            N.check(info(h, i, name, dims))
-            t = torch.empty(tuple(dims), dtype=torch.float32, device=self.device)
-            N.check(read(h, i, N.ptr(t), N.stream_ptr()))
-            out[name.value.decode()] = t
-        return out
+        if which == "vae":
+            return N.read_taps("ctta_vae", self._h_vae, self.device)
+        return N.read_taps("ctta_hifigan", self._h_voc, self.device)

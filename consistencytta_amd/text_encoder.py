@@ -73,7 +73,7 @@ class T5EncoderModel(_ParamTree):
         self.encoder.embed_tokens.weight = self.shared.weight          # tied, as in T5EncoderModel
         self._register(OrderedDict((k, s) for k, s in full.items() if k not in ("shared.weight", "encoder.embed_tokens.weight")))
         self.requires_grad_(False)
-        self._h_t5 = self._h_t5_key = self._h_t5_ver = None
+        self._engine = N.EngineHandle("ctta_t5_destroy")
 
     @classmethod
     def from_pretrained(cls, name, **kwargs):
@@ -89,23 +89,10 @@ class T5EncoderModel(_ParamTree):
     def device(self):
         return self.shared.weight.device
 
-    def _release(self):
-        if getattr(self, "_h_t5", None):
-            N.lib().ctta_t5_destroy(self._h_t5)
-        self._h_t5 = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
     def _ensure(self, B, L):
         ver = self._weights_version()
         key = (self.device,)
-        if (self._h_t5 is None or self._h_t5_key[2:] != key or B > self._h_t5_key[0] or L > self._h_t5_key[1]
-                or ver != self._h_t5_ver):
-            self._release()
+        if not self._engine.fits((B, L), key, ver):
             cfg = self.config
             c = N.T5Config()
             c.vocab_size, c.d_model, c.d_kv, c.d_ff = cfg["vocab_size"], cfg["d_model"], cfg["d_kv"], cfg["d_ff"]
@@ -114,11 +101,9 @@ class T5EncoderModel(_ParamTree):
             c.eps = cfg["layer_norm_epsilon"]
             c.max_batch, c.max_len = B, max(L, 8)
             table, keep = N.tensor_table(self._table())
-            h = N.c_void_p()
-            with torch.cuda.device(self.device):
-                N.check(N.lib().ctta_t5_create(c, table, len(table), N.stream_ptr(), h))
-            self._h_t5, self._h_t5_key, self._h_t5_ver = h, (B, max(L, 8)) + key, ver
-        return self._h_t5
+            self._engine.replace(lambda h: N.lib().ctta_t5_create(c, table, len(table), N.stream_ptr(), h),
+                                 (c.max_batch, c.max_len), key, ver, self.device)
+        return self._engine.h
 
     @torch.no_grad()
     def encode_static(self, input_ids, attention_mask, out=None):
