@@ -55,18 +55,34 @@ def _post_cfg_fusable(w):
     return bool(np.float32(1.0 - float(w)) == np.float32(1.0) - np.float32(w))
 
 
+def _env_on(name):
+    """The run-time switches CTTA_TWO_STREAM / CTTA_FUSED_TAIL: on unless set to "0"; read at every call."""
+    return os.environ.get(name, "1") != "0"
+
+
+def _ema_nets(source_model, shadow_models):
+    """(networks, their flat buffers or None, the signature `do_ema_update` records once it has validated them)."""
+    nets = [source_model] + list(shadow_models)
+    return nets, [getattr(m, "_flat", None) for m in nets], tuple((id(m), getattr(m, "_rehome_count", 0)) for m in nets)
+
+
+def _ema_steady(nets, flats, sig):
+    """Steady state of the training loop: the same networks `do_ema_update` validated, still living in their flat buffers
+    (O(1) checks: the key comparison ran when the signature was recorded, and flat_is_current() only walks after a
+    re-homing event)."""
+    return (getattr(nets[0], "_ema_validated", None) == sig and all(f is not None for f in flats)
+            and all(m.flat_is_current() for m in nets))
+
+
 def optimizer_tail(source_model, shadow_models, decay_consts, optimizer, lr_scheduler, grad_scale, do_step):
     """The end of a training step, tools/train_utils.py:177-183: optimizer.step() (skipped on a NaN loss, :167-172) ->
     lr_scheduler.step() -> optimizer.zero_grad() -> update_ema().  With the fused AdamW on `source_model` and every network
     still in the flat buffers `do_ema_update` validated on an earlier step, the three device passes are ONE launch
     (FusedAdamW.step_zero_ema; bit-identical state, tests/test_train_gpu.py); anything else -- a torch optimizer, the first
     step, re-homed parameters, CTTA_FUSED_TAIL=0 -- takes the three calls."""
-    nets = [source_model] + list(shadow_models)
-    sig = tuple((id(m), getattr(m, "_rehome_count", 0)) for m in nets)
-    flats = [getattr(m, "_flat", None) for m in nets]
-    if (hasattr(optimizer, "step_zero_ema") and optimizer.module is source_model and os.environ.get("CTTA_FUSED_TAIL", "1") != "0"
-            and getattr(source_model, "_ema_validated", None) == sig and all(f is not None for f in flats)
-            and all(m.flat_is_current() for m in nets) and optimizer.can_fuse_tail(flats[1:])):
+    nets, flats, sig = _ema_nets(source_model, shadow_models)
+    if (hasattr(optimizer, "step_zero_ema") and optimizer.module is source_model and _env_on("CTTA_FUSED_TAIL")
+            and _ema_steady(nets, flats, sig) and optimizer.can_fuse_tail(flats[1:])):
         for d in decay_consts:
             assert 0 <= d <= 1
         optimizer.step_zero_ema(flats[1:], decay_consts, grad_scale=grad_scale, do_step=do_step)
@@ -89,22 +105,23 @@ def do_ema_update(source_model, shadow_models, decay_consts):
     assert len(shadow_models) == len(decay_consts)
     assert 1 <= len(shadow_models) <= 2, "the fused kernel updates one or two shadows"
     L_ = N.lib()
-    nets = [source_model] + list(shadow_models)
-    flats = [getattr(m, "_flat", None) for m in nets]
-    # steady state of the training loop: the same networks, still living in their flat buffers (O(1) checks: the key
-    # comparison below ran when this tuple was recorded, and flat_is_current() only walks after a re-homing event)
-    sig = tuple((id(m), getattr(m, "_rehome_count", 0)) for m in nets)
-    if (getattr(source_model, "_ema_validated", None) == sig and all(f is not None for f in flats)
-            and all(m.flat_is_current() for m in nets)):
-        for d in decay_consts:
-            assert 0 <= d <= 1
+    nets, flats, sig = _ema_nets(source_model, shadow_models)
+
+    def launch(p, shadows, n):
+        b = shadows[1] if len(shadows) > 1 else None
+        N.check(L_.ctta_ema_update2(N.ptr(p), N.ptr(shadows[0]), float(decay_consts[0]), N.ptr(b),
+                                    float(decay_consts[1]) if b is not None else 0.0, n, N.stream_ptr()))
+
+    def launch_flats():       # every network lives in one flat buffer with the same layout: one launch for the whole model
         with torch.cuda.device(flats[0].device):
-            N.check(L_.ctta_ema_update2(N.ptr(flats[0]), N.ptr(flats[1]), float(decay_consts[0]),
-                                        N.ptr(flats[2]) if len(flats) > 2 else N.c_void_p(0),
-                                        float(decay_consts[1]) if len(flats) > 2 else 0.0, flats[0].numel(),
-                                        N.stream_ptr()))
+            launch(flats[0], flats[1:], flats[0].numel())
         for m in shadow_models:
             m.mark_weights_changed()
+
+    if _ema_steady(nets, flats, sig):
+        for d in decay_consts:
+            assert 0 <= d <= 1
+        launch_flats()
         return
     src = dict(source_model.named_parameters())
     shadows = [dict(m.named_parameters()) for m in shadow_models]
@@ -114,45 +131,151 @@ def do_ema_update(source_model, shadow_models, decay_consts):
     # the one-launch path needs every network to STILL live in its flat buffer (a `.to()` / `.float()` after
     # flatten_parameters_ re-homes p.data and would leave the kernel updating stale memory)
     if all(f is not None and f.numel() == flats[0].numel() for f in flats) and all(m.flat_is_current() for m in nets):
-        # every network lives in one flat buffer with the same layout: one launch for the whole model
-        fa = flats[1]
-        fb = flats[2] if len(flats) > 2 else None
-        with torch.cuda.device(flats[0].device):
-            N.check(L_.ctta_ema_update2(N.ptr(flats[0]), N.ptr(fa), float(decay_consts[0]),
-                                        N.ptr(fb) if fb is not None else N.c_void_p(0),
-                                        float(decay_consts[1]) if fb is not None else 0.0, flats[0].numel(),
-                                        N.stream_ptr()))
-        for m in shadow_models:
-            m.mark_weights_changed()
+        launch_flats()
         source_model._ema_validated = sig
         return
     for name, p in src.items():
-        a = shadows[0][name]
-        b = shadows[1][name] if len(shadows) > 1 else None
         if not p.is_cuda:
             raise N.CttaError("EMA update needs CUDA(ROCm) parameters; there is no CPU path")
-        N.check(L_.ctta_ema_update2(N.ptr(p.detach()), N.ptr(a.detach()), float(decay_consts[0]),
-                                    N.ptr(b.detach()) if b is not None else N.c_void_p(0),
-                                    float(decay_consts[1]) if b is not None else 0.0, p.numel(), N.stream_ptr()))
-        # bump version counters so the engines re-pack the shadows
-        a.detach().add_(0)
-        if b is not None:
-            b.detach().add_(0)
+        mine = [sh[name].detach() for sh in shadows]
+        launch(p.detach(), mine, p.numel())
+        for t in mine:      # bump version counters so the engines re-pack the shadows
+            t.add_(0)
 
 
-class _DistillLoss(torch.autograd.Function):
-    """Gives the distillation loss a grad_fn: autograd's only job is to call the engine's backward."""
+class _EngineLoss(torch.autograd.Function):
+    """Gives a loss computed outside autograd a grad_fn whose only job is to call the engine's backward:
+    `model._student_backward(*saved, d loss)` (AudioLCM saves pred, target, sigma, gamma; AudioGDM pred, target, weights)."""
 
     @staticmethod
-    def forward(ctx, anchor, loss, model, pred, target, sig, gamma):
-        ctx.model, ctx.saved = model, (pred, target, sig, gamma)
+    def forward(ctx, anchor, loss, model, *saved):
+        ctx.model, ctx.saved = model, saved
         return loss.clone()
 
     @staticmethod
     def backward(ctx, grad_out):
-        pred, target, sig, gamma = ctx.saved
-        ctx.model._student_backward(pred, target, sig, gamma, float(grad_out))
-        return (None,) * 7
+        ctx.model._student_backward(*ctx.saved, float(grad_out))
+        return (None,) * (3 + len(ctx.saved))
+
+
+def _snr_mse_loss(pred, target, sigma, gamma):
+    """get_loss (audio_consistency_model.py:250-266) on the fused kernel: batch mean of the per-sample MSE weighted by
+    min(sigma^-2, gamma); sigma None / gamma 0: the plain MSE.  Returns the (1,) fp32 loss tensor."""
+    B = pred.shape[0]
+    inst = torch.empty(B, dtype=torch.float32, device=pred.device)
+    out = torch.empty(1, dtype=torch.float32, device=pred.device)
+    N.check(N.lib().ctta_snr_mse_loss(N.ptr(pred.contiguous()), N.ptr(target.contiguous()), N.ptr(sigma), float(gamma),
+                                      N.ptr(inst), N.ptr(out), B, pred[0].numel(), N.stream_ptr()))
+    return out
+
+
+def _snr_mse_grad(pred, target, sigma, gamma, loss_scale):
+    """loss_scale * d(_snr_mse_loss) / d pred as the (B, H*W, 8) bf16 tensor the engine's backward takes."""
+    B, C, H, W = pred.shape
+    d = torch.empty(B, H * W, 8, dtype=torch.bfloat16, device=pred.device)
+    with torch.cuda.device(pred.device):
+        N.check(N.lib().ctta_snr_mse_grad(N.ptr(pred), N.ptr(target.contiguous()), N.ptr(sigma), float(gamma),
+                                          float(loss_scale), B, C, H * W, 8, N.ptr(d), N.stream_ptr()))
+    return d
+
+
+def _warm_up(fn, dev, sync=False):
+    """What precedes every capture: one eager run of `fn` on a fresh side stream (engine handles, kernel attributes and
+    the allocator pool must exist before a capture), joined with the current stream; `sync` also waits for the device.
+    Returns the side stream, for captures that go on the warmed stream."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    if sync:
+        torch.cuda.synchronize(dev)
+    return side
+
+
+def _capture(fn, stream=None, pool=None):
+    """Records the launches of `fn` into a new hipGraph (on `stream`, default torch's own capture stream; in the memory
+    pool `pool`, default a private one): (graph, what `fn` returned)."""
+    graph = torch.cuda.CUDAGraph()
+    # thread-local capture mode: with a process group alive, RCCL's watchdog thread may touch the HIP runtime
+    # during the capture; only this thread's calls belong to it
+    with torch.cuda.graph(graph, pool=pool, stream=stream, capture_error_mode="thread_local"):
+        out = fn()
+    return graph, out
+
+
+def _replay_loop(one_step, rewind, replays, dev):
+    """The frame of the graphed sampler loops: one eager step, rewind the loop state, capture the step, rewind, replay."""
+    _warm_up(one_step, dev)
+    rewind()
+    graph, _ = _capture(one_step)
+    rewind()
+    for _ in range(replays):
+        graph.replay()
+
+
+def _place_stream(candidates, run_on, dev):
+    """Which stream a side graph is replayed on decides whether it overlaps anything: HIP maps its streams (torch's pool
+    streams, the hipGraphs' own branch streams, the handles' side streams) onto 4 hardware queues, and two streams on one
+    queue run back to back.  The mapping is not queryable, so it is MEASURED: `run_on(stream)` replays the side graph on
+    the candidate beside the main work, twice per candidate -- the second pass is the measurement (the first pays
+    first-use costs of the stream) --, and the fastest candidate stays (the first one on a tie).
+    Returns (that stream, [ms per candidate, rounded to 2 decimals])."""
+    cur = torch.cuda.current_stream(dev)
+    best, tried = (None, float("inf")), []
+    for s_ in candidates:
+        ms = float("inf")
+        for _ in range(2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(dev)
+            e0.record(cur)
+            run_on(s_)
+            e1.record(cur)
+            torch.cuda.synchronize(dev)
+            ms = e0.elapsed_time(e1)
+        tried.append(round(ms, 2))
+        if ms < best[1]:
+            best = (s_, ms)
+    return best[0], tried
+
+
+def _student_query(unet, sch, z_n, t, w_in, w_post, enc, mask):
+    """One eager query of the few-step sampler (audio_consistency_model.py:480-495, consistencytta.py:168-180): scale, the
+    guided student on B rows -- 2B with post-CFG, `enc` / `mask` then hold the uncond rows first --, post-CFG combine."""
+    use_cf = w_post > 1.
+    z_in = torch.cat([z_n] * 2) if use_cf else z_n
+    z_in = sch.scale_model_input(z_in, t)
+    zh = unet(z_in, t, guidance=w_in, encoder_hidden_states=enc, encoder_attention_mask=mask).sample
+    if use_cf:
+        u, c = zh.chunk(2)
+        zh = (1 - w_post) * u + w_post * c
+    return zh
+
+
+def _student_next_input(zh, B, w_post, w_dev, draw, sig, z_in):
+    """A captured Heun query's output -> the next query's input: post-CFG combine, add_noise, scale_model_input and the
+    2B-row stacking in ONE launch (ctta_consistency_renoise).  `zh`: B rows, or uncond + cond rows with post-CFG; a scale
+    the kernel cannot reproduce bit for bit (`_post_cfg_fusable`) is combined by torch first."""
+    use_cf = w_post > 1.
+    if use_cf and _post_cfg_fusable(w_post):
+        cond, unc = zh[B:], zh[:B]
+    elif use_cf:
+        cond, unc = (1 - w_post) * zh[:B] + w_post * zh[B:], None
+    else:
+        cond, unc = zh, None
+    N.check(N.lib().ctta_consistency_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
+                                             N.ptr(draw), N.ptr(sig), N.ptr(z_in), 2 if use_cf else 1, B, zh[0].numel(),
+                                             N.stream_ptr()))
+
+
+def _post_cfg_combine(zh, B, w_post, w_dev):
+    """The last query's post-CFG combine on the uncond + cond rows of `zh`: ctta_cfg_combine, or torch's own for a scale
+    the kernel cannot reproduce bit for bit."""
+    if not _post_cfg_fusable(w_post):
+        return (1 - w_post) * zh[:B] + w_post * zh[B:]
+    out = torch.empty_like(zh[:B])
+    N.check(N.lib().ctta_cfg_combine(N.ptr(zh[:B]), N.ptr(zh[B:]), N.ptr(w_dev), N.ptr(out), B, zh[0].numel(), N.stream_ptr()))
+    return out
 
 
 class AudioDistilledModel(nn.Module):
@@ -246,6 +369,71 @@ class AudioDistilledModel(nn.Module):
             for p in model.parameters():
                 assert p.requires_grad is False, f"The {name} is not frozen."
 
+    # ---- training plumbing shared by both distillation stages; a subclass declares the two lists below
+    def _frozen_modules(self):
+        """The submodules that stay in eval mode whatever `train()` is told (audio_distilled_model.py:154-163)."""
+        raise NotImplementedError
+
+    def _ema_shadows(self):
+        """([shadow networks of `student_unet`], [their EMA decays]): what `update_ema` moves, one or two of them."""
+        raise NotImplementedError
+
+    def train(self, mode=True):
+        super().train(mode)
+        for mod in self._frozen_modules():
+            if mod is not None:
+                mod.eval()
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def update_ema(self):
+        assert self.training, "EMA update should only be called during training"
+        do_ema_update(self.student_unet, *self._ema_shadows())
+
+    def _optimizer_tail(self, optimizer, lr_scheduler, grad_scale, do_step):
+        assert self.training, "EMA update should only be called during training"
+        optimizer_tail(self.student_unet, *self._ema_shadows(), optimizer, lr_scheduler, grad_scale, do_step)
+
+    def prepare_training(self, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, broadcast=True):
+        """Flat parameter buffers for the student family, rank-0 weights on every rank (DDP's wrap-time
+        broadcast) and the fused AdamW over the student (tools/train_utils.py:59-63)."""
+        from .optim import FusedAdamW
+        self.student_unet.enable_training = True
+        for m in [self.student_unet] + list(self._ema_shadows()[0]):
+            flat = m.flatten_parameters_()
+            if broadcast:
+                dist_util.broadcast_(flat)
+                m.mark_weights_changed()
+        return FusedAdamW(self.student_unet, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _grad_anchor(self):
+        a = getattr(self, "_anchor", None)
+        if a is None or a.device != self.device:
+            a = self._anchor = torch.zeros((), device=self.device, requires_grad=True)
+        return a
+
+    def _gradient_buckets(self, optimizer, **kw):
+        """The bucketed gradient all-reduce (RCCL) over the optimizer's flat gradient buffer, block by block."""
+        cdt = getattr(self, "allreduce_dtype", None)
+        return dist_util.GradientBuckets(optimizer.grad, self.student_unet.block_ranges(), compress=cdt,
+                                         twin=optimizer.grad_twin(cdt) if hasattr(optimizer, "grad_twin") else None, **kw)
+
+    def _boundary_step(self, loss, backward, optimizer, lr_scheduler, skip_nan):
+        """The half of a training step behind the loss, where gradients are synchronised: `backward(on_block_done)` with
+        the gradient all-reduce overlapped block by block -> AdamW -> lr schedule -> zero_grad -> EMA.  A NaN loss skips
+        the update (not the zero_grad, not the EMA; train_utils.py:167-172) on all ranks together or on none: the flag's
+        all-reduce is issued BEFORE the backward, the loss is read after the gradients have been joined.
+        Returns the loss as a Python float."""
+        buckets = self._gradient_buckets(optimizer)
+        nan_any = dist_util.AnyRankFlag(torch.isnan(loss))
+        backward(buckets.ready if buckets.enabled else None)
+        world = buckets.wait()
+        value = float(loss.item())
+        self._optimizer_tail(optimizer, lr_scheduler, 1.0 / world, not (skip_nan and nan_any.result()))
+        return value
+
     # audio_distilled_model.py:286-322
     def _query_teacher(self, z_scaled, t, prompt_embeds, prompt_mask, guidance_scale=None, reuse_text=None, raw=False):
         """`raw=True` returns (the U-Net's output, the per-sample CFG scales or None) WITHOUT the combine: the DDIM path
@@ -329,19 +517,11 @@ class AudioLCM(AudioDistilledModel):
             inst = inst * torch.clamp(sig.to(inst.device, torch.float32) ** -2, max=float(gamma))
         return inst.mean()
 
-    def train(self, mode=True):
-        super().train(mode)
-        self.teacher_unet.eval()
-        self.student_ema_unet.eval()
-        self.student_target_unet.eval()
-        if self.vae is not None:
-            self.vae.eval()
-        if self.text_encoder is not None:
-            self.text_encoder.eval()
-        return self
+    def _frozen_modules(self):
+        return (self.teacher_unet, self.student_ema_unet, self.student_target_unet, self.vae, self.text_encoder)
 
-    def eval(self):
-        return self.train(False)
+    def _ema_shadows(self):
+        return [self.student_target_unet, self.student_ema_unet], [self.target_ema_decay, self.ema_decay]
 
     def compute_snr(self, timesteps, t_indices):
         """:215-219: sigma^-2 of the Heun tables; with DDIM alphas_cumprod[t] / (1 - alphas_cumprod[t])
@@ -355,16 +535,6 @@ class AudioLCM(AudioDistilledModel):
     def _snr_sigma(self, t):
         """DDIM: the loss kernels weigh by min(sigma^-2, snr_gamma); the sigma whose -2nd power is compute_snr(t)."""
         return (1.0 / self.compute_snr(t, None).to(torch.float64)).sqrt().to(torch.float32)
-
-    def update_ema(self):
-        assert self.training, "EMA update should only be called during training"
-        do_ema_update(self.student_unet, [self.student_target_unet, self.student_ema_unet],
-                      [self.target_ema_decay, self.ema_decay])
-
-    def _optimizer_tail(self, optimizer, lr_scheduler, grad_scale, do_step):
-        assert self.training, "EMA update should only be called during training"
-        optimizer_tail(self.student_unet, [self.student_target_unet, self.student_ema_unet],
-                       [self.target_ema_decay, self.ema_decay], optimizer, lr_scheduler, grad_scale, do_step)
 
     def check_eval_mode(self):
         super().check_eval_mode()
@@ -455,20 +625,23 @@ class AudioLCM(AudioDistilledModel):
                                      guidance_scale, want_grad)
         if not want_grad:
             return out
-        loss, pred, target, sig, gamma = out
-        return _DistillLoss.apply(self._grad_anchor(), loss, self, pred, target, sig, gamma)
-
-    def _grad_anchor(self):
-        a = getattr(self, "_anchor", None)
-        if a is None or a.device != self.device:
-            a = self._anchor = torch.zeros((), device=self.device, requires_grad=True)
-        return a
+        loss, *saved = out
+        return _EngineLoss.apply(self._grad_anchor(), loss, self, *saved)
 
     def _side_stream(self, dev):
         st = getattr(self, "_side", None)
         if st is None or st.device != torch.device(dev):
             st = self._side = torch.cuda.Stream(device=dev)
         return st
+
+    def _student_forward_on_side(self, z_in, t, w, embeds, mask):
+        """The student's training forward enqueued on the model's side stream, behind what the current stream holds; the
+        caller joins (`current.wait_stream(self._side_stream(dev))`) before it reads the prediction."""
+        dev = z_in.device
+        side = self._side_stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            return self.student_unet.forward_train(z_in, t, w, embeds, mask)
 
     def _student_backward(self, pred, target, sig, gamma, loss_scale=1.0, on_block_done=None):
         """d loss / d pred of get_loss (audio_consistency_model.py:250-266) -> engine backward."""
@@ -478,24 +651,8 @@ class AudioLCM(AudioDistilledModel):
                 (g,) = torch.autograd.grad(graph, leaf, torch.full_like(graph, float(loss_scale)))
             self.student_unet.backward(grad_output=g, on_block_done=on_block_done)
             return
-        B, C, H, W = pred.shape
-        d = torch.empty(B, H * W, 8, dtype=torch.bfloat16, device=pred.device)
-        with torch.cuda.device(pred.device):
-            N.check(N.lib().ctta_snr_mse_grad(N.ptr(pred), N.ptr(target.contiguous()), N.ptr(sig), float(gamma),
-                                              float(loss_scale), B, C, H * W, 8, N.ptr(d), N.stream_ptr()))
-        self.student_unet.backward(grad_output_nhwc=d, on_block_done=on_block_done)
-
-    def prepare_training(self, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, broadcast=True):
-        """Flat parameter buffers for the student family, rank-0 weights on every rank (DDP's wrap-time
-        broadcast) and the fused AdamW over the student (tools/train_utils.py:59-63)."""
-        from .optim import FusedAdamW
-        self.student_unet.enable_training = True
-        for m in (self.student_unet, self.student_target_unet, self.student_ema_unet):
-            flat = m.flatten_parameters_()
-            if broadcast:
-                dist_util.broadcast_(flat)
-                m.mark_weights_changed()
-        return FusedAdamW(self.student_unet, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.student_unet.backward(grad_output_nhwc=_snr_mse_grad(pred, target, sig, gamma, loss_scale),
+                                   on_block_done=on_block_done)
 
     def train_step(self, z_0, prompt, optimizer, lr_scheduler=None, gt_wav=None, skip_nan=True,
                    accumulation_steps=1, **fw):
@@ -506,30 +663,15 @@ class AudioLCM(AudioDistilledModel):
         Returns the (unscaled) loss as a Python float (the reference reads `loss.item()` every step too)."""
         assert self.training, "train_step needs model.train()"
         self._micro = getattr(self, "_micro", 0) + 1
-        boundary = self._micro % max(1, int(accumulation_steps)) == 0
-        if not boundary:
-            with torch.no_grad():
-                loss, pred, target, sig, gamma = self._forward_impl(
-                    z_0, gt_wav, prompt, False, True, fw.pop("time_inds", None), fw.pop("gaussian_noise", None),
-                    fw.pop("guidance_scale", None), True)
-                self._student_backward(pred, target, sig, gamma, 1.0 / accumulation_steps)
-            return float(loss.item())
+        accum = max(1, int(accumulation_steps))
         with torch.no_grad():
-            loss, pred, target, sig, gamma = self._forward_impl(
-                z_0, gt_wav, prompt, False, True, fw.pop("time_inds", None), fw.pop("gaussian_noise", None),
-                fw.pop("guidance_scale", None), True)
-            # gradient all-reduce (RCCL) overlapped with the backward pass, block by block
-            cdt = getattr(self, "allreduce_dtype", None)
-            buckets = dist_util.GradientBuckets(optimizer.grad, self.student_unet.block_ranges(), compress=cdt,
-                                                twin=optimizer.grad_twin(cdt) if hasattr(optimizer, "grad_twin") else None)
-            nan_any = dist_util.AnyRankFlag(torch.isnan(loss))     # all ranks skip together (or none)
-            self._student_backward(pred, target, sig, gamma, 1.0 / max(1, int(accumulation_steps)),
-                                   buckets.ready if buckets.enabled else None)
-            world = buckets.wait()
-            value = float(loss.item())
-            # train_utils.py:167-172: a NaN loss skips the update (not the zero_grad, not the EMA)
-            self._optimizer_tail(optimizer, lr_scheduler, 1.0 / world, not (skip_nan and nan_any.result()))
-        return value
+            loss, *saved = self._forward_impl(z_0, gt_wav, prompt, False, True, fw.pop("time_inds", None),
+                                              fw.pop("gaussian_noise", None), fw.pop("guidance_scale", None), True)
+            if self._micro % accum != 0:
+                self._student_backward(*saved, 1.0 / accum)
+                return float(loss.item())
+            return self._boundary_step(loss, lambda on_block_done: self._student_backward(*saved, 1.0 / accum, on_block_done),
+                                       optimizer, lr_scheduler, skip_nan)
 
     def _forward_impl(self, z_0, gt_wav, prompt, validation_mode, run_teacher, time_inds, gaussian_noise,
                       guidance_scale, want_grad):
@@ -578,14 +720,10 @@ class AudioLCM(AudioDistilledModel):
         # kernel's MFMA waves -- tools/pk_hazard.py.  The library is built without that instruction form and
         # tools/check_isa.py keeps it out; test_distillation_step_full_batch_is_deterministic... guards the overlap.)
         side_pred = None
-        if (want_grad and validation_mode == 0 and z_0.is_cuda and os.environ.get("CTTA_TWO_STREAM", "1") != "0"):
-            cur = torch.cuda.current_stream(dev)
-            side = self._side_stream(dev)
+        if want_grad and validation_mode == 0 and z_0.is_cuda and _env_on("CTTA_TWO_STREAM"):
             w_stu = guidance_scale if guidance_scale is not None else float(self.teacher_guidance_scale)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                side_pred = self.student_unet.forward_train(z_np1_scaled, t_np1, w_stu, embeds, mask)
-            side_pred.record_stream(cur)
+            side_pred = self._student_forward_on_side(z_np1_scaled, t_np1, w_stu, embeds, mask)
+            side_pred.record_stream(torch.cuda.current_stream(dev))
         if heun:
             v1 = self._query_teacher(z_np1_scaled, t_np1, embeds_cf, mask_cf, guidance_scale)
             zhat_n = sch.step(v1, t_np1, z_np1).prev_sample
@@ -606,11 +744,7 @@ class AudioLCM(AudioDistilledModel):
             if self.loss is not None and sigma is not None:   # the consistency loss proper (get_loss); plain MSEs stay MSE
                 with torch.no_grad():
                     return self._perceptual_loss(a, b, gt_wav, prompt, sigma, gamma)
-            inst = torch.empty(B, dtype=torch.float32, device=dev)
-            out = torch.empty(1, dtype=torch.float32, device=dev)
-            N.check(N.lib().ctta_snr_mse_loss(N.ptr(a.contiguous()), N.ptr(b.contiguous()), N.ptr(sigma), float(gamma),
-                                              N.ptr(inst), N.ptr(out), B, a[0].numel(), N.stream_ptr()))
-            return out[0]
+            return _snr_mse_loss(a, b, sigma, gamma)[0]
 
         if validation_mode != 0:   # :354-405
             from_np1 = self.student_target_unet(z_np1_scaled, t_np1, guidance=w, encoder_hidden_states=embeds,
@@ -685,14 +819,7 @@ class AudioLCM(AudioDistilledModel):
         unet = self.student_ema_unet if use_ema else self.student_target_unet
 
         def calc_zhat_0(z_n, t):
-            z_in = torch.cat([z_n] * 2) if use_cf else z_n
-            z_in = sch.scale_model_input(z_in, t)
-            zh = unet(z_in, t, guidance=guidance_scale_input, encoder_hidden_states=enc_stu,
-                      encoder_attention_mask=mask_stu).sample
-            if use_cf:
-                u, c = zh.chunk(2)
-                zh = (1 - guidance_scale_post) * u + guidance_scale_post * c
-            return zh
+            return _student_query(unet, sch, z_n, t, guidance_scale_input, guidance_scale_post, enc_stu, mask_stu)
 
         t1 = time()
         sch.set_timesteps(18, device=dev)
@@ -737,21 +864,6 @@ class AudioLCM(AudioDistilledModel):
         return zhat_0
 
 
-class _WeightedMSELoss(torch.autograd.Function):
-    """grad_fn of AudioGDM's loss: backward = d(weighted MSE)/d(pred) -> the student engine's backward pass."""
-
-    @staticmethod
-    def forward(ctx, anchor, loss, model, pred, target, weights):
-        ctx.model, ctx.saved = model, (pred, target, weights)
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        pred, target, weights = ctx.saved
-        ctx.model._student_backward(pred, target, weights, float(grad_out))
-        return (None,) * 6
-
-
 class AudioGDM(AudioDistilledModel):
     """Stage-1 guided distillation (models/audio_guided_model.py:16-244): the CFG teacher is
     distilled into the guidance-conditioned student at DDPM noise levels; loss = MSE to the teacher's prediction with
@@ -767,36 +879,16 @@ class AudioGDM(AudioDistilledModel):
                          ema_decay=ema_decay, teacher_guidance_scale=teacher_guidance_scale, **kwargs)
         self.noise_scheduler = DDPMScheduler.from_pretrained(self.scheduler_name, subfolder="scheduler")
 
-    def train(self, mode=True):
-        """audio_distilled_model.py:154-163: the frozen teacher / EMA / text encoder stay in eval mode."""
-        super().train(mode)
-        self.teacher_unet.eval()
-        self.student_ema_unet.eval()
-        if self.text_encoder is not None:
-            self.text_encoder.eval()
-        return self
+    def _frozen_modules(self):
+        return (self.teacher_unet, self.student_ema_unet, self.text_encoder)
 
-    def eval(self):
-        return self.train(False)
+    def _ema_shadows(self):
+        return [self.student_ema_unet], [self.ema_decay]
 
     def compute_snr(self, timesteps):
         """alpha^2 / sigma^2 with alpha = sqrt(alphas_cumprod[t]) (audio_distilled_model.py:165-191), host side."""
         ac = self.noise_scheduler.alphas_cumprod[torch.as_tensor(timesteps).reshape(-1).to("cpu", torch.int64)]
         return ((ac ** 0.5) / ((1.0 - ac) ** 0.5)) ** 2
-
-    def update_ema(self):
-        assert self.training, "EMA update should only be called during training"
-        do_ema_update(self.student_unet, [self.student_ema_unet], [self.ema_decay])
-
-    def _optimizer_tail(self, optimizer, lr_scheduler, grad_scale, do_step):
-        assert self.training, "EMA update should only be called during training"
-        optimizer_tail(self.student_unet, [self.student_ema_unet], [self.ema_decay], optimizer, lr_scheduler, grad_scale, do_step)
-
-    def _grad_anchor(self):
-        a = getattr(self, "_anchor", None)
-        if a is None or a.device != self.device:
-            a = self._anchor = torch.zeros((), device=self.device, requires_grad=True)
-        return a
 
     def _loss_weights(self, t_n, dev):
         if self.snr_gamma is None:
@@ -859,37 +951,19 @@ class AudioGDM(AudioDistilledModel):
         want_grad = (self.training and torch.is_grad_enabled()
                      and any(p.requires_grad for p in self.student_unet.parameters()))
         with torch.no_grad():
-            loss, pred, target, weights = self._forward_impl(z_0, prompt, want_grad, time_inds, gaussian_noise,
-                                                             guidance_scale)
+            loss, *saved = self._forward_impl(z_0, prompt, want_grad, time_inds, gaussian_noise, guidance_scale)
         if not want_grad:
             return loss
-        return _WeightedMSELoss.apply(self._grad_anchor(), loss, self, pred, target, weights)
-
-    def prepare_training(self, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, broadcast=True):
-        from .optim import FusedAdamW
-        self.student_unet.enable_training = True
-        for m in (self.student_unet, self.student_ema_unet):
-            flat = m.flatten_parameters_()
-            if broadcast:
-                dist_util.broadcast_(flat)
-                m.mark_weights_changed()
-        return FusedAdamW(self.student_unet, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        return _EngineLoss.apply(self._grad_anchor(), loss, self, *saved)
 
     def train_step(self, z_0, prompt, optimizer, lr_scheduler=None, skip_nan=True, **fw):
         """loss -> backward (+ overlapped RCCL gradient all-reduce) -> AdamW -> schedule -> zero_grad -> EMA."""
         assert self.training, "train_step needs model.train()"
         with torch.no_grad():
-            loss, pred, target, weights = self._forward_impl(z_0, prompt, True, fw.pop("time_inds", None),
-                                                             fw.pop("gaussian_noise", None), fw.pop("guidance_scale", None))
-            cdt = getattr(self, "allreduce_dtype", None)
-            buckets = dist_util.GradientBuckets(optimizer.grad, self.student_unet.block_ranges(), compress=cdt,
-                                                twin=optimizer.grad_twin(cdt) if hasattr(optimizer, "grad_twin") else None)
-            nan_any = dist_util.AnyRankFlag(torch.isnan(loss))
-            self._student_backward(pred, target, weights, 1.0, buckets.ready if buckets.enabled else None)
-            world = buckets.wait()
-            value = float(loss.item())
-            self._optimizer_tail(optimizer, lr_scheduler, 1.0 / world, not (skip_nan and nan_any.result()))
-        return value
+            loss, *saved = self._forward_impl(z_0, prompt, True, fw.pop("time_inds", None), fw.pop("gaussian_noise", None),
+                                              fw.pop("guidance_scale", None))
+            return self._boundary_step(loss, lambda on_block_done: self._student_backward(*saved, 1.0, on_block_done),
+                                       optimizer, lr_scheduler, skip_nan)
 
     @torch.no_grad()
     def inference(self, prompt, inference_scheduler, guidance_scale_input=3, guidance_scale_post=1, num_steps=20,
@@ -975,25 +1049,12 @@ def _teacher_loop_graphed(self, sch, z, enc, mask, guidance_scale):
 
     n_pairs = (nt - 1) // 2
     if n_pairs > 0:
-        # one eager pair on a side stream first: handles, kernel attributes and the allocator pool must exist
-        # before capture; then rewind the state and capture
         x0 = x.clone()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            pair()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        x.copy_(x0)
-        idx.zero_()
-        graph = torch.cuda.CUDAGraph()
-        # thread-local capture mode: with a process group alive, RCCL's watchdog thread may touch the HIP runtime
-        # during the capture; only this thread's calls belong to it
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            pair()
-        x.copy_(x0)
-        idx.zero_()
-        for _ in range(n_pairs):
-            graph.replay()
+
+        def rewind():
+            x.copy_(x0)
+            idx.zero_()
+        _replay_loop(pair, rewind, n_pairs, dev)
     half_first()                # last timestep: sigma_next = 0, a plain 1st-order (Euler) step
     return bufs["xhat"].clone()
 
@@ -1032,22 +1093,12 @@ def _teacher_loop_graphed_ddim(self, sch, z, enc, mask, guidance_scale):
         x.copy_(xnew)
         idx.add_(1)
 
-    # one eager step on a side stream first (handles, kernel attributes, allocator pool), then rewind and capture
     x0 = x.clone()
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        one()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    x.copy_(x0)
-    idx.zero_()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-        one()
-    x.copy_(x0)
-    idx.zero_()
-    for _ in range(nt):
-        graph.replay()
+
+    def rewind():
+        x.copy_(x0)
+        idx.zero_()
+    _replay_loop(one, rewind, nt, dev)
     return x.clone()
 
 
@@ -1069,7 +1120,6 @@ def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, 
     B = rows // 2 if use_cf else rows
     n = z_first[0].numel()
     K = len(later)
-    L_ = N.lib()
     if step_noise is None:          # today's draws, in today's order
         step_noise = [torch.randn_like(z_first[:B]) for _ in range(K)]
         step_noise = torch.stack(step_noise) if K else None
@@ -1081,7 +1131,6 @@ def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, 
     else:           # DDIMScheduler.add_noise's coefficient pair; the dummy row is (1, 0)
         cols = [sch.noise_coeffs(t, 1) for t in later] + [torch.tensor([[1.0], [0.0]])]
         tab = torch.cat(cols, dim=1).to(dev)                                                    # (2, K + 1)
-    fused_cfg = use_cf and heun and _post_cfg_fusable(w_post)
     w_dev = torch.full((B,), float(w_post), dtype=torch.float32, device=dev)
     zin = z_first.clone().contiguous()
     zh = torch.empty_like(zin)
@@ -1097,43 +1146,24 @@ def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, 
                    reuse_text=not first[0]).sample
         first[0] = False
         zh.copy_(out)
-        if fused_cfg:
-            cond, unc = out[B:], out[:B]
-        elif use_cf:
-            cond, unc = (1 - w_post) * out[:B] + w_post * out[B:], None
-        else:
-            cond, unc = out, None
         if heun:
-            N.check(L_.ctta_consistency_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
-                                                N.ptr(draw), N.ptr(c[0]), N.ptr(zin), 2 if use_cf else 1, B, n,
-                                                N.stream_ptr()))
+            _student_next_input(out, B, w_post, w_dev, draw, c[0], zin)
         else:
-            N.check(L_.ctta_lincomb2_rows(N.ptr(cond.contiguous()), N.ptr(draw), N.ptr(c[0]), N.ptr(c[1]), N.ptr(zin), B, n,
-                                          0.0, N.stream_ptr()))
+            cond = (1 - w_post) * out[:B] + w_post * out[B:] if use_cf else out
+            N.check(N.lib().ctta_lincomb2_rows(N.ptr(cond.contiguous()), N.ptr(draw), N.ptr(c[0]), N.ptr(c[1]), N.ptr(zin), B,
+                                               n, 0.0, N.stream_ptr()))
             if use_cf:
                 zin[B:].copy_(zin[:B])
         idx.add_(1)
 
-    # one eager step on a side stream first (handles, kernel attributes, allocator pool, the text K / V), then rewind
-    # and capture
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        one()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    zin.copy_(z_first)
-    idx.zero_()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-        one()
-    zin.copy_(z_first)
-    idx.zero_()
-    for _ in range(K + 1):
-        graph.replay()
+    def rewind():
+        zin.copy_(z_first)
+        idx.zero_()
+    _replay_loop(one, rewind, K + 1, dev)       # the warm-up step also fills the handle's text K / V
     unet._text_key = None       # the handle's text cache was last filled outside the module's own bookkeeping
-    if use_cf:
-        return (1 - w_post) * zh[:B] + w_post * zh[B:]
-    return zh.clone()
+    if not use_cf:
+        return zh.clone()
+    return _post_cfg_combine(zh, B, w_post, w_dev) if heun else (1 - w_post) * zh[:B] + w_post * zh[B:]
 
 
 AudioLCM._student_loop_graphed = _student_loop_graphed
@@ -1356,6 +1386,9 @@ class _DistillStepGraph:
         """Noising, the two CFG teacher queries and the Heun step between them (audio_consistency_model.py:268-311) on the
         input set S: writes the student's input S['z_in'] and the target network's input S['tgt_in'].  Nothing here
         depends on the student's weights: the pipelined step runs it for batch i + 1 beside the rest of batch i."""
+        # A second derivation of the Heun / DDIM step ON PURPOSE: `_forward_impl` goes through the scheduler's own methods and
+        # state, this goes through `_sigma_plan` / `_ddim_plan`, and tests/test_train_gpu.py holds the two against each other
+        # bit for bit -- a comparison that is only worth something while they stay independent.
         m, B = self.m, self.B
         sch = m.noise_scheduler
         L_ = N.lib()
@@ -1403,21 +1436,15 @@ class _DistillStepGraph:
     def _main_part(self, S, teacher_first):
         """Target network, the student's training forward (on its side stream) and the loss, on the input set S whose
         teacher phase is done (`teacher_first=False`) or runs first in this same sequence (the unpipelined step)."""
-        m, B, dev = self.m, self.B, self.dev
-        L_ = N.lib()
+        m, dev = self.m, self.dev
         w = S["w"]
         embeds, mask = S["P"]["embeds"], S["P"]["mask"]
-        two_stream = os.environ.get("CTTA_TWO_STREAM", "1") != "0"
+        two_stream = _env_on("CTTA_TWO_STREAM")
         box = {}
 
         def fork():
-            if not two_stream:
-                return
-            cur = torch.cuda.current_stream(dev)
-            side = m._side_stream(dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                box["pred"] = m.student_unet.forward_train(S["z_in"], S["t_np1"], w, embeds, mask)
+            if two_stream:
+                box["pred"] = m._student_forward_on_side(S["z_in"], S["t_np1"], w, embeds, mask)
         if teacher_first:
             self._fork_student = fork
             try:
@@ -1442,11 +1469,7 @@ class _DistillStepGraph:
             with torch.enable_grad():
                 graph = m._perceptual_loss(leaf, target, S["gt_wav"], prompt, s_loss, gamma)
             return graph.detach().reshape(1), pred, (leaf, graph), s_loss, gamma
-        inst = torch.empty(B, dtype=torch.float32, device=dev)
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-        N.check(L_.ctta_snr_mse_loss(N.ptr(pred.contiguous()), N.ptr(target), N.ptr(s_loss), float(gamma), N.ptr(inst),
-                                     N.ptr(out), B, pred[0].numel(), N.stream_ptr()))
-        return out, pred, target, s_loss, gamma
+        return _snr_mse_loss(pred, target, s_loss, gamma), pred, target, s_loss, gamma
 
     def _forward_part(self):
         return self._main_part(self.cur, teacher_first=not self.pipelined)
@@ -1459,7 +1482,6 @@ class _DistillStepGraph:
         m = self.m
         unet = m.student_unet
         pool = torch.cuda.graph_pool_handle()
-        kw = dict(pool=pool, stream=warm, capture_error_mode="thread_local")
         ranges = unet.block_ranges()
         min_e = self.bucket_min_elems
         state = {"fin": False}
@@ -1469,22 +1491,24 @@ class _DistillStepGraph:
                 blk, state["fin"] = unet.backward_next()
                 blocks.append(blk)
                 pending += (ranges[blk][1] - ranges[blk][0]) if blk in ranges else 0
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, **kw):
+
+        def head():
             out, pred, target, s_loss, gamma = self._forward_part()
-            Bn, C, H, W = pred.shape
-            d = torch.empty(Bn, H * W, 8, dtype=torch.bfloat16, device=pred.device)
-            N.check(N.lib().ctta_snr_mse_grad(N.ptr(pred), N.ptr(target), N.ptr(s_loss), float(gamma), 1.0 / self.accum,
-                                              Bn, C, H * W, 8, N.ptr(d), N.stream_ptr()))
+            d = _snr_mse_grad(pred, target, s_loss, gamma, 1.0 / self.accum)
+            self._keep = (pred, target, d)        # read by the later graphs: their pool blocks must stay allocated
             first = unet.backward_begin(d)
             blocks = [first]
             more_blocks(blocks, (ranges[first][1] - ranges[first][0]) if first in ranges else 0)
-        self._keep = (pred, target, d)        # read by the later graphs: their pool blocks must stay allocated
+            return out, blocks
+
+        def further():
+            blocks = []
+            more_blocks(blocks, 0)
+            return blocks
+        self.graph, (out, blocks) = _capture(head, stream=warm, pool=pool)
         self.segments = [(self.graph, tuple(blocks))]
         while not state["fin"]:
-            g, blocks = torch.cuda.CUDAGraph(), []
-            with torch.cuda.graph(g, **kw):
-                more_blocks(blocks, 0)
+            g, blocks = _capture(further, stream=warm, pool=pool)
             self.segments.append((g, tuple(blocks)))
         return out
 
@@ -1493,68 +1517,48 @@ class _DistillStepGraph:
         ACCUMULATE into the gradient buffer like any backward; the caller zeroes it (train_step does after its update)."""
         m = self.m
         self._refresh(z_0, time_inds, gaussian_noise, guidance_scale, gt_wav=gt_wav)
+
+        def eager_pass():
+            if self.pipelined:
+                self._teacher_part(self.nxt)
+                self._rotate()
+            self._body()
         with torch.no_grad():
-            warm = torch.cuda.Stream(device=self.dev)
-            warm.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(warm):
-                if self.pipelined:
-                    self._teacher_part(self.nxt)
-                    self._rotate()
-                self._body()
-            torch.cuda.current_stream(self.dev).wait_stream(warm)
-            torch.cuda.synchronize(self.dev)
+            warm = _warm_up(eager_pass, self.dev, sync=True)      # every capture below goes on this warmed stream
             for net in (m.student_unet, m.student_target_unet):   # their bf16 re-pack belongs to every replay
                 net._engine.version = None
             if self.pipelined:
-                self.teacher_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.teacher_graph, stream=warm, capture_error_mode="thread_local"):
-                    self._teacher_part(self.nxt)
+                self.teacher_graph, _ = _capture(lambda: self._teacher_part(self.nxt), stream=warm)
             if self.main_eager:
                 pass                                  # the main part stays eager launches (see __init__)
             elif self.segmented:
                 self.loss = self._capture_segments(warm)
             else:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=warm, capture_error_mode="thread_local"):
-                    self.loss = self._body()
+                self.graph, self.loss = _capture(self._body, stream=warm)
             if self.pipelined:
                 self._place_teacher_stream()
         self.opt.zero_grad()
         return self
 
     def _place_teacher_stream(self, candidates=10):
-        """Which stream the teacher graph is replayed on decides whether it overlaps anything: HIP maps its streams (torch's
-        pool streams, the hipGraphs' own branch streams, the handles' side streams) onto 4 hardware queues, and two streams
-        on one queue run back to back.  The mapping is not queryable, so it is MEASURED once per capture: (teacher graph on
-        the candidate) beside (main graph on the current stream), timed for a handful of pool streams; the fastest stays
-        (measured on MI355X: 86 ms per step on a free queue against 99 ms on the main graph's own queue)."""
+        """The stream the teacher graph is replayed on, by `_place_stream`: (teacher graph on the candidate) beside (main
+        graph on the current stream), once per capture (measured on MI355X: 86 ms per step on a free queue against 99 ms
+        on the main graph's own queue)."""
         dev = self.dev
         cur = torch.cuda.current_stream(dev)
-        self.placement_ms = []
-        best = (None, float("inf"))
         # high-priority pool streams sit on hardware queues of their own (no normal-priority stream -- the main graph's launch
         # stream, its branch streams -- can share them); the teacher has a whole step of slack, so its priority only matters
         # for the placement
         cands = [self._tstream] + [torch.cuda.Stream(device=dev, priority=-1) for _ in range(2)] + \
                 [torch.cuda.Stream(device=dev) for _ in range(max(0, candidates - 3))]
-        for s_ in cands:
-            ms = float("inf")
-            for _ in range(2):          # the second pass is the measurement (the first pays first-use costs of the stream)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize(dev)
-                e0.record(cur)
-                s_.wait_stream(cur)
-                with torch.cuda.stream(s_):
-                    self.teacher_graph.replay()
-                self.replay()
-                cur.wait_stream(s_)
-                e1.record(cur)
-                torch.cuda.synchronize(dev)
-                ms = e0.elapsed_time(e1)
-            self.placement_ms.append(round(ms, 2))
-            if ms < best[1]:
-                best = (s_, ms)
-        self._tstream = best[0]
+
+        def run_on(s_):
+            s_.wait_stream(cur)
+            with torch.cuda.stream(s_):
+                self.teacher_graph.replay()
+            self.replay()
+            cur.wait_stream(s_)
+        self._tstream, self.placement_ms = _place_stream(cands, run_on, dev)
 
     def replay(self, on_block_done=None):
         """The device work of one micro-step on the CURRENT input set.  Segmented: `on_block_done(block id)` runs between
@@ -1639,9 +1643,7 @@ class _DistillStepGraph:
         if self._micro % self.accum != 0:      # DDP's no_sync: gradients only accumulate locally
             self.replay()
             return float(self.loss.item())
-        cdt = getattr(m, "allreduce_dtype", None)
-        buckets = dist_util.GradientBuckets(self.opt.grad, m.student_unet.block_ranges(), min_elems=self.bucket_min_elems,
-                                            compress=cdt, twin=self.opt.grad_twin(cdt) if hasattr(self.opt, "grad_twin") else None)
+        buckets = m._gradient_buckets(self.opt, min_elems=self.bucket_min_elems)
         if buckets.enabled and not self.segmented and not self.main_eager:
             raise N.CttaError("a monolithic step graph cannot interleave the gradient all-reduce with the backward pass: "
                               "capture with segmented=True under a process group")
@@ -1748,14 +1750,7 @@ class ConsistencyTTA(nn.Module):
         z_N = noise * sch.init_noise_sigma
 
         def calc(z_n, t):
-            z_in = torch.cat([z_n] * 2) if use_cf else z_n
-            z_in = sch.scale_model_input(z_in, t)
-            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=encoder_states,
-                           encoder_attention_mask=encoder_mask).sample
-            if use_cf:
-                u, c = zh.chunk(2)
-                zh = (1 - cfg_scale_post) * u + cfg_scale_post * c
-            return zh
+            return _student_query(self.unet, sch, z_n, t, cfg_scale_input, cfg_scale_post, encoder_states, encoder_mask)
 
         zhat_0 = calc(z_N, float(sch._timesteps_host[0]))
         sch.set_timesteps(num_steps, device=noise.device)
@@ -1775,16 +1770,14 @@ class ConsistencyTTA(nn.Module):
         fp32 operations per element as the eager sequence, so the latent is bit-identical to `generate_latent` with
         `step_noise=noise[1:]`."""
         sch = self.scheduler
-        L_ = N.lib()
         use_cf = cfg_scale_post > 1.
         B = noise.shape[1]
-        n = noise[0, 0].numel()
         dev = noise.device
+        w_post = None
         if use_cf:
             encoder_states = torch.cat([uncond_states, encoder_states])
             encoder_mask = torch.cat([uncond_mask, encoder_mask])
             w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev)
-            fused_cfg = _post_cfg_fusable(cfg_scale_post)
         sch.set_timesteps(18, device=dev)
         z_N = noise[0] * sch.init_noise_sigma
         z_in = sch.scale_model_input(torch.cat([z_N] * 2) if use_cf else z_N, float(sch._timesteps_host[0]))
@@ -1800,20 +1793,8 @@ class ConsistencyTTA(nn.Module):
             t = later[k]
             sig = sch._sigma_dev(sch.index_for_timestep(t), B, dev)
             z_in = torch.empty_like(zh)
-            if use_cf and not fused_cfg:
-                cond, unc = (1 - cfg_scale_post) * zh[:B] + cfg_scale_post * zh[B:], None
-            else:
-                cond, unc = (zh[B:], zh[:B]) if use_cf else (zh, None)
-            N.check(L_.ctta_consistency_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_post) if unc is not None else N.c_void_p(0),
-                                                N.ptr(noise[k + 1]), N.ptr(sig), N.ptr(z_in), 2 if use_cf else 1, B, n,
-                                                N.stream_ptr()))
-        if not use_cf:
-            return zh
-        if not fused_cfg:
-            return (1 - cfg_scale_post) * zh[:B] + cfg_scale_post * zh[B:]
-        out = torch.empty_like(zh[:B])
-        N.check(L_.ctta_cfg_combine(N.ptr(zh[:B]), N.ptr(zh[B:]), N.ptr(w_post), N.ptr(out), B, n, N.stream_ptr()))
-        return out
+            _student_next_input(zh, B, cfg_scale_post, w_post, noise[k + 1], sig, z_in)
+        return _post_cfg_combine(zh, B, cfg_scale_post, w_post) if use_cf else zh
 
     def _serving_inputs(self, batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post, uncond_states,
                         uncond_mask, from_tokens):
@@ -1920,14 +1901,8 @@ class ConsistencyTTA(nn.Module):
             N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
             return lat, mel, pcm
 
-        side = torch.cuda.Stream(device=dev)        # eager warm-up: engine handles, kernel attributes, allocator pool
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            run()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            out = run()
+        _warm_up(run, dev)
+        graph, out = _capture(run)
 
         def replay(*args):
             load(*args)
@@ -1950,7 +1925,7 @@ class ConsistencyTTA(nn.Module):
         int16 waveforms of the batch fed TWO calls earlier` (the buffer is overwritten by the next call; the first two calls
         return warm-up garbage -- feed two extra batches, e.g. the last one again, to drain).  Results are bit-identical to
         `capture_graph` / the eager path.  Which streams the U-Net and decoder graphs run on is measured at capture: HIP maps
-        streams onto 4 hardware queues and two graphs on one queue do not overlap (see `_DistillStepGraph._place_teacher_stream`).
+        streams onto 4 hardware queues and two graphs on one queue do not overlap (see `_place_stream`).
         `num_steps`, `cfg_scale_post`, `uncond_states`, `uncond_mask`, `from_tokens`: as in `capture_graph`.  With
         `from_tokens=True` FLAN-T5 is a FOURTH graph on a fourth stream, placed by the same measurement, one batch ahead of
         the U-Net: `f(input_ids, attention_mask, noise)` returns the batch fed THREE calls earlier (`f.depth == 3`); a
@@ -1961,17 +1936,8 @@ class ConsistencyTTA(nn.Module):
                                         uncond_states, uncond_mask, from_tokens)
         scratch = torch.empty(4, dtype=torch.float32, device=dev)
 
-        def graphed(fn):
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                fn()                                  # eager warm-up: engine handles, kernel attributes, allocator pool
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr, stream=side, capture_error_mode="thread_local"):
-                out = fn()
-            return gr, out
+        def graphed(fn):      # every stage on the stream that warmed it up
+            return _capture(fn, stream=_warm_up(fn, dev, sync=True))
 
         if from_tokens:
             g_t, (enc, mask) = graphed(lambda: self._encode_static(st))
@@ -2011,30 +1977,14 @@ class ConsistencyTTA(nn.Module):
             for k, _ in side_graphs:
                 cur.wait_stream(streams[k])
 
-        def timed():
-            ms = 0.0
-            for _ in range(2):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize(dev)
-                e0.record()
-                hand_over()
-                launch()
-                e1.record()
-                torch.cuda.synchronize(dev)
-                ms = e0.elapsed_time(e1)
-            return ms
         placement = {}
         for k, _ in side_graphs:                       # decoder first, then the U-Net beside both, then the text encoder
-            best = (streams[k], float("inf"))
-            tried = []
-            for s_ in [streams[k]] + [torch.cuda.Stream(device=dev) for _ in range(max(0, candidates - 1))]:
+            def run_on(s_, k=k):                       # one call of the pipeline with this stage's graph on the candidate
                 streams[k] = s_
-                ms = timed()
-                tried.append(round(ms, 2))
-                if ms < best[1]:
-                    best = (s_, ms)
-            streams[k] = best[0]
-            placement[k] = tried
+                hand_over()
+                launch()
+            cands = [streams[k]] + [torch.cuda.Stream(device=dev) for _ in range(max(0, candidates - 1))]
+            streams[k], placement[k] = _place_stream(cands, run_on, dev)
 
         def replay(*args):
             hand_over()                                # reads the previous call's inputs and results, before ...

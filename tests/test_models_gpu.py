@@ -13,6 +13,9 @@ from consistencytta_amd.models import AudioLCM  # noqa: E402
 from gpu_util import DEV, rel_err, rel_l2  # noqa: E402
 
 REL_L2 = 2.5e-2
+# relative L2 difference between the gradients of two `forward().backward()` runs of the `_gdm()` case: the largest of the
+# ten pairs among five runs on an MI355X (6.3e-9 ... 1.28e-8, LABNOTES.md)
+GDM_GRAD_REPEAT_REL_L2 = 1.28e-8
 
 
 def _model():
@@ -268,6 +271,51 @@ def test_stage1_guided_distillation_loss_backward_and_inference(golden):
     l2 = rel_l2(z, torch.from_numpy(g["gdm_inference_4steps"]))
     print("stage-1 4-step DDIM inference rel_l2 %.3e" % l2)
     assert l2 <= 2 * REL_L2
+
+
+def test_stage1_train_step_is_forward_backward_adamw_and_ema(golden):
+    """AudioGDM.train_step pinned against the pieces it is made of, on the recorded draws of `gdm_tiny`: model 1 runs
+    `forward(...).backward()`; model 2, from identical weights, runs `train_step`.  Same loss bit for bit; one AdamW step
+    whose first moment is (1 - beta1) x model 1's gradient; the gradient buffer zeroed; the EMA shadow moved by
+    (1 - ema_decay) * (p_after - shadow_before), bit for bit (the kernel's own unfused fp32 arithmetic, as
+    test_update_ema_matches_reference_and_resyncs_engines holds it against the reference).
+    Gradient bound: two `forward().backward()` runs of this very case differ by GDM_GRAD_REPEAT_REL_L2 in relative L2
+    (the atomics of the normalisation-layer reductions add in arrival order; LABNOTES.md); twice that is allowed, and never
+    more than 1e-6.  The moment is compared in the form the kernel computes it, fl32((1 - beta1) * g) with 1 - beta1 in
+    fp32 -- one fp32 multiply, which torch repeats bit for bit on model 1's gradient: dividing exp_avg back by (1 - beta1)
+    would add the rounding of that multiply and of the division (6.3e-8 measured, the same on every run) to a comparison
+    whose bound is 2.6e-8."""
+    g = golden("gdm_tiny")
+    kw = dict(time_inds=torch.from_numpy(g["gdm_time_inds"]), gaussian_noise=torch.from_numpy(g["gdm_noise"]).to(DEV),
+              guidance_scale=torch.from_numpy(g["gdm_guidance"]))
+    m1, P, z0 = _gdm()
+    m1.train()
+    opt1 = m1.prepare_training(lr=1e-4, weight_decay=1e-2, broadcast=False)
+    loss1 = m1(z0, P, **kw)
+    loss1.backward()
+    torch.cuda.synchronize()
+    grad1 = opt1.grad[:opt1.n].clone()
+    assert float(grad1.abs().max()) > 0 and opt1.step_count == 0
+
+    m2, P2, _ = _gdm()
+    m2.train()
+    opt2 = m2.prepare_training(lr=1e-4, weight_decay=1e-2, broadcast=False)
+    assert torch.equal(opt2.flat, opt1.flat)
+    ema_before = m2.student_ema_unet._flat.detach().clone()
+    val = m2.train_step(z0, P2, opt2, None, **kw)
+    torch.cuda.synchronize()
+    assert val == float(loss1.detach())                                   # bit for bit
+    assert opt2.step_count == 1 and float(opt2.grad.abs().max()) == 0.0
+    beta1 = np.float32(opt2.param_groups[0]["betas"][0])
+    want = grad1 * float(np.float32(1.0) - beta1)                         # exp_avg after one step from zero moments
+    rel = float((opt2.exp_avg - want).norm() / want.norm())
+    bound = min(2 * GDM_GRAD_REPEAT_REL_L2, 1e-6)
+    print("stage-1 train_step: loss %.8f, gradient vs forward().backward() rel_l2 %.3e (bound %.1e)" % (val, rel, bound))
+    assert rel <= bound
+    assert not torch.equal(opt2.flat, opt1.flat)
+    ema_after = m2.student_ema_unet._flat
+    assert not torch.equal(ema_after, ema_before)
+    assert torch.equal(ema_after, ema_before + (1 - m2.ema_decay) * (opt2.flat - ema_before))
 
 
 def test_whole_pipeline_hipgraph_matches_eager():
