@@ -188,6 +188,8 @@ SIGNATURES = {
     "ctta_vae_decode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "ctta_vae_decode_with_grad": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "ctta_vae_decode_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "ctta_vae_decode_backward_params": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "ctta_vae_load_weights": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "ctta_vae_arena_bytes": (c_size_t, [c_void_p]),
     "ctta_vae_num_taps": (c_int, [c_void_p]),
     "ctta_vae_tap_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
@@ -320,6 +322,13 @@ SIGNATURES = {
     "ctta_lrelu_bwd": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "ctta_conv_cout1_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_float, c_void_p, c_void_p]),
+    "ctta_conv_cout1_wgrad_scratch_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "ctta_conv_cout1_wgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_int, c_void_p, c_void_p]),
+    "ctta_post_quant_wgrad_scratch_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ctta_post_quant_wgrad": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p]),
+    "ctta_upsample2_nearest": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ctta_pool2_sum": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ctta_softmax_bias_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
     "ctta_softmax_bwd_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),

@@ -126,14 +126,15 @@ def load_state(input_dir, models, optimizer=None, lr_scheduler=None, process_ind
 # ------------------------------------------------------------------------------------------------ inference.py:112-158
 def build_model_from_run(model_path, original_args_path, vae=None, stage=2, device=None, **overrides):
     """What inference.py / demo.py do between `parse_args` and the generation loop: read the training arguments
-    from summary.jsonl, construct AudioGDM (stage 1) or AudioLCM (stage 2) from them, load `pytorch_model_2.bin`
-    through `load_pretrained` (legacy key names included) and switch to eval mode.  `overrides` (e.g. `unet_config=`,
-    `text_encoder=`, `tokenizer=`) are passed to the constructor: offline boxes cannot fetch FLAN-T5."""
-    from .models import AudioGDM, AudioLCM
+    from summary.jsonl, construct AudioGDM (stage 1), AudioLCM (stage 2) or AudioLCM_FTVAE (stage 2 with
+    `finetune_vae`) from them, load `pytorch_model_2.bin` through `load_pretrained` (legacy key names included) and
+    switch to eval mode.  `overrides` (e.g. `unet_config=`, `text_encoder=`, `tokenizer=`) are passed to the
+    constructor: offline boxes cannot fetch FLAN-T5."""
+    from .models import AudioGDM, AudioLCM, AudioLCM_FTVAE
     train_args = read_original_args(original_args_path)
     assert stage == train_args.stage, "Stage mismatch between training and eval."
-    assert not train_args.finetune_vae, "AudioLCM_FTVAE (VAE fine-tuning) is outside the built path"
-    cls = AudioGDM if stage == 1 else AudioLCM
+    # inference.py:127: a run that fine-tuned the VAE decoder comes back as AudioLCM_FTVAE (its EMA decoder included)
+    cls = AudioGDM if stage == 1 else AudioLCM_FTVAE if train_args.finetune_vae else AudioLCM
     kw = dict(text_encoder_name=train_args.text_encoder_name, scheduler_name=train_args.scheduler_name,
               unet_model_name=train_args.unet_model_name, unet_model_config_path=train_args.unet_model_config,
               snr_gamma=train_args.snr_gamma, freeze_text_encoder=train_args.freeze_text_encoder,

@@ -1206,6 +1206,28 @@ extern "C" ctta_status ctta_zero_insert2(const void* dy, void* dz, int batch, in
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }
+// nearest x2 upsample, materialised: out[b][y][x] = in[b][y / 2][x / 2] (NHWC bf16, 8 channels per lane).  The upsampling
+// convolutions' weight gradient reads this copy through the implicit kernel instead of nine shifted im2col^T copies.
+__global__ void upsample2_nearest_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, int B, int h, int w, int vc) {
+  const long long total = (long long)B * (2 * h) * (2 * w) * vc;
+  for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int v = (int)(idx % vc);
+    long long p = idx / vc;
+    const int x = (int)(p % (2 * w)); p /= 2 * w;
+    const int y = (int)(p % (2 * h));
+    const long long b = p / (2 * h);
+    out[idx] = in[((b * h + (y >> 1)) * w + (x >> 1)) * vc + v];
+  }
+}
+extern "C" ctta_status ctta_upsample2_nearest(const void* x, void* out, int batch, int h, int w, int c, void* stream) {
+  CTTA_REQUIRE(x && out && batch >= 1 && h >= 1 && w >= 1 && c >= 8 && c % 8 == 0, "upsample2_nearest: bad arguments");
+  const long long total = (long long)batch * 4 * h * w * (c / 8);
+  hipLaunchKernelGGL(upsample2_nearest_kernel, dim3(grid1d(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, (const uint4*)x,
+                     (uint4*)out, batch, h, w, c / 8);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
 // nearest x2 upsample backward: dx[b][h][w] (+)= sum of the 2x2 block of dup
 __global__ void pool2_sum_kernel(const bf16_t* __restrict__ du, bf16_t* __restrict__ dx, int B, int h, int w, int C,
                                  int acc) {
@@ -1525,6 +1547,189 @@ extern "C" ctta_status ctta_conv_cout1_dgrad(const float* gy, const float* y_tan
   const long long total = (long long)batch * h * wd * (c / 8);
   hipLaunchKernelGGL(conv_cout1_dgrad_kernel, dim3(grid1d(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, gy,
                      y_tanh, w, batch, h, wd, kh, kw, pad_h, pad_w, c, (const bf16_t*)act, slope, (bf16_t*)dx);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+// Parameter gradients of the two small layers at the ends of the VAE decoder (fine-tuning the decoder): sums over every
+// pixel into a few hundred numbers.  Both kernels write per-workgroup partial rows, already in the gradient tensors' own
+// element order, and fold_partials_kernel adds the rows up in workgroup order: no float atomics, the same bits every run.
+//   out[j] (+)= sum_blk partials[blk][j]       j < n_w -> dw[j],   n_w <= j < n_w + n_b -> db[j - n_w]
+__global__ void fold_partials_kernel(const float* __restrict__ partials, int nblk, int ld, int n_w, int n_b,
+                                     float* __restrict__ dw, float* __restrict__ db, int accumulate) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_w + n_b) return;
+  float t = 0.f;
+  for (int b = 0; b < nblk; ++b) t += partials[(size_t)b * ld + j];
+  if (j >= n_w && !db) return;
+  float* dst = j < n_w ? dw + j : db + (j - n_w);
+  *dst = accumulate ? *dst + t : t;
+}
+
+// Weight and bias gradient of a single-output-channel convolution (the decoder's conv_out), the twin of
+// conv_cout1_dgrad_kernel:   dW[c][tap] = sum_m gy[m] * a[pixel(m, tap)][c],   db = sum_m gy[m]
+// (gy fp32 (B, H, W), a NHWC bf16, dW in the state dict's (1, C, kh, kw) order).  Walked over the INPUT pixels: a thread
+// owns 8 channels (v = tid % (C / 8)) and every (256 / (C / 8))-th pixel of its workgroup's contiguous range, reads its
+// vector of a once and multiplies it by the up to nine output positions the pixel feeds.
+constexpr int COUT1_MAX_TAPS = 9;
+static int cout1_wgrad_blocks(long long pixels, int c) {
+  const int npg = 256 / (c / 8);
+  const long long want = (pixels + (long long)npg * 16 - 1) / ((long long)npg * 16);
+  return (int)(want < 1 ? 1 : (want > 512 ? 512 : want));
+}
+__global__ __launch_bounds__(256) void conv_cout1_wgrad_kernel(const float* __restrict__ gy, const bf16_t* __restrict__ a, int B,
+                                                               int H, int W, int kh, int kw, int pad_h, int pad_w, int C,
+                                                               long long pix_per_blk, float* __restrict__ partials, int ld) {
+  __shared__ float red[256 * 8];
+  const int vc = C / 8, npg = 256 / vc, taps = kh * kw;
+  const int tid = threadIdx.x, v = tid % vc, pg = tid / vc;
+  const long long total = (long long)B * H * W;
+  const long long p_lo = blockIdx.x * pix_per_blk, p_hi = min(p_lo + pix_per_blk, total);
+  float acc[COUT1_MAX_TAPS][8];
+#pragma unroll
+  for (int t = 0; t < COUT1_MAX_TAPS; ++t)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[t][e] = 0.f;
+  float gsum = 0.f;
+  if (pg < npg) {
+    for (long long p = p_lo + pg; p < p_hi; p += npg) {
+      const int x = (int)(p % W);
+      const int y = (int)((p / W) % H);
+      const long long img = p / ((long long)W * H) * H;       // first row of the sample
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(a + (size_t)p * C + v * 8), f);
+      if (v == 0) gsum += gy[p];
+#pragma unroll
+      for (int t = 0; t < COUT1_MAX_TAPS; ++t) {
+        if (t >= taps) continue;
+        // pixel (y, x) is tap (ta, tq) of output position (y - ta + pad_h, x - tq + pad_w)
+        const int yy = y - t / kw + pad_h, xx = x - t % kw + pad_w;
+        if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+        const float g = gy[(size_t)(img + yy) * W + xx];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[t][e] += g * f[e];
+      }
+    }
+  }
+  // the workgroup's pixel phases, folded in phase order, one tap at a time
+  float* row = partials + (size_t)blockIdx.x * ld;
+#pragma unroll
+  for (int t = 0; t < COUT1_MAX_TAPS; ++t) {
+    if (t >= taps) continue;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[tid * 8 + e] = acc[t][e];
+    __syncthreads();
+    for (int c = tid; c < C; c += 256) {
+      float s = 0.f;
+      for (int g = 0; g < npg; ++g) s += red[(g * vc + c / 8) * 8 + (c & 7)];
+      row[(size_t)c * taps + t] = s;
+    }
+  }
+  __syncthreads();
+  if (v == 0 && pg < npg) red[pg] = gsum;
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.f;
+    for (int g = 0; g < npg; ++g) s += red[g];
+    row[(size_t)C * taps] = s;
+  }
+}
+extern "C" size_t ctta_conv_cout1_wgrad_scratch_floats(int batch, int h, int wd, int kh, int kw, int c) {
+  if (batch < 1 || h < 1 || wd < 1 || kh < 1 || kw < 1 || c < 8 || c % 8 != 0 || c > 2048) return 0;
+  return (size_t)cout1_wgrad_blocks((long long)batch * h * wd, c) * ((size_t)c * kh * kw + 1);
+}
+extern "C" ctta_status ctta_conv_cout1_wgrad(const float* gy, const void* a, int batch, int h, int wd, int kh, int kw, int pad_h,
+                                             int pad_w, int c, float* dw, float* db, int accumulate, float* scratch,
+                                             void* stream) {
+  CTTA_REQUIRE(gy && a && dw && scratch && batch >= 1 && h >= 1 && wd >= 1 && kh >= 1 && kw >= 1 && kh * kw <= COUT1_MAX_TAPS &&
+                   c >= 8 && c % 8 == 0 && c <= 2048,
+               "conv_cout1_wgrad: bad arguments (c a multiple of 8 up to 2048, at most %d taps)", COUT1_MAX_TAPS);
+  const long long total = (long long)batch * h * wd;
+  const int nblk = cout1_wgrad_blocks(total, c), ld = c * kh * kw + 1;
+  const long long ppb = (total + nblk - 1) / nblk;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(conv_cout1_wgrad_kernel, dim3((unsigned)nblk), dim3(256), 0, s, gy, (const bf16_t*)a, batch, h, wd, kh, kw,
+                     pad_h, pad_w, c, ppb, scratch, ld);
+  CTTA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, scratch, nblk, ld, ld - 1, 1, dw, db,
+                     accumulate);
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+// post_quant_conv's parameter gradients, the backward twin of engine_vae.hip's post_quant_kernel (a 1x1 convolution of
+// z / scale):   dW[o][e] = sum_pix dzin[pix][o] * (z[b][e][hw] * inv_scale),   db[o] = sum_pix dzin[pix][o]
+// dzin NHWC bf16 with ld elements per pixel, z (B, zin, HW) fp32.  A workgroup stages tiles of 128 pixels in LDS; thread j owns
+// output element j (weights first, then the biases) and adds its tiles up in tile order.
+constexpr int PQ_TILE = 128, PQ_MAX_IN = 16, PQ_MAX_OUT = 32;
+__global__ __launch_bounds__(256) void post_quant_wgrad_kernel(const bf16_t* __restrict__ dzin, int ld, const float* __restrict__ z,
+                                                               float inv_scale, int B, int zin, int zout, int HW,
+                                                               float* __restrict__ partials, int pld) {
+  __shared__ float ds[PQ_TILE * PQ_MAX_OUT];
+  __shared__ float zs[PQ_TILE * PQ_MAX_IN];
+  const long long total = (long long)B * HW;
+  const int ntiles = (int)((total + PQ_TILE - 1) / PQ_TILE);
+  const int tid = threadIdx.x, nout = zout * zin + zout;
+  float acc[(PQ_MAX_OUT * (PQ_MAX_IN + 1) + 255) / 256];
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(acc) / sizeof(float)); ++i) acc[i] = 0.f;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long long p0 = (long long)tile * PQ_TILE;
+    const int np = (int)min((long long)PQ_TILE, total - p0);
+    __syncthreads();
+    for (int i = tid; i < np * zout; i += 256) {
+      const int px = i / zout, o = i - px * zout;
+      ds[px * zout + o] = bf2f(dzin[(size_t)(p0 + px) * ld + o]);
+    }
+    for (int i = tid; i < np * zin; i += 256) {
+      const int e = i / np, px = i - e * np;                   // hw contiguous in z
+      const long long pix = p0 + px;
+      const long long bb = pix / HW;
+      zs[px * zin + e] = z[((size_t)bb * zin + e) * HW + (pix - bb * HW)] * inv_scale;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(acc) / sizeof(float)); ++i) {
+      const int j = tid + i * 256;
+      if (j >= nout) continue;
+      float s = 0.f;
+      if (j < zout * zin) {
+        const int o = j / zin, e = j - o * zin;
+        for (int px = 0; px < np; ++px) s += ds[px * zout + o] * zs[px * zin + e];
+      } else {
+        const int o = j - zout * zin;
+        for (int px = 0; px < np; ++px) s += ds[px * zout + o];
+      }
+      acc[i] += s;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(acc) / sizeof(float)); ++i) {
+    const int j = tid + i * 256;
+    if (j < nout) partials[(size_t)blockIdx.x * pld + j] = acc[i];
+  }
+}
+static int post_quant_wgrad_blocks(long long pixels) {
+  const long long t = (pixels + PQ_TILE - 1) / PQ_TILE;
+  return (int)(t < 1 ? 1 : (t > 256 ? 256 : t));
+}
+extern "C" size_t ctta_post_quant_wgrad_scratch_floats(int batch, int hw, int zin, int zout) {
+  if (batch < 1 || hw < 1 || zin < 1 || zout < 1 || zin > PQ_MAX_IN || zout > PQ_MAX_OUT) return 0;
+  return (size_t)post_quant_wgrad_blocks((long long)batch * hw) * ((size_t)zout * zin + zout);
+}
+extern "C" ctta_status ctta_post_quant_wgrad(const void* dzin, int ld, const float* z, float inv_scale, int batch, int zin, int zout,
+                                             int hw, float* dw, float* db, int accumulate, float* scratch, void* stream) {
+  CTTA_REQUIRE(dzin && z && dw && scratch && batch >= 1 && hw >= 1 && zin >= 1 && zin <= PQ_MAX_IN && zout >= 1 &&
+                   zout <= PQ_MAX_OUT && ld >= zout,
+               "post_quant_wgrad: bad arguments (embed_dim <= %d, z_channels <= %d)", PQ_MAX_IN, PQ_MAX_OUT);
+  const int nblk = post_quant_wgrad_blocks((long long)batch * hw), pld = zout * zin + zout;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(post_quant_wgrad_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const bf16_t*)dzin, ld, z, inv_scale, batch,
+                     zin, zout, hw, scratch, pld);
+  CTTA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)((pld + 255) / 256)), dim3(256), 0, s, scratch, nblk, pld, zout * zin, zout,
+                     dw, db, accumulate);
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }

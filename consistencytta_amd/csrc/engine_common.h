@@ -87,6 +87,15 @@ static inline int64_t tensor_numel(const ctta_tensor* t) {
   return n;
 }
 
+// The caller's fp32 gradient tensors of a backward pass (same names / shapes as the state dict; U-Net and VAE decoder).
+struct GradTable {
+  std::unordered_map<std::string, float*> map;
+  void build(const ctta_tensor* g, int n) {
+    map.clear();
+    for (int i = 0; i < n; ++i) map[g[i].name] = const_cast<float*>(g[i].data);   // ctta_tensor is shared with the (read-only) weight tables
+  }
+};
+
 // A packed bf16 GEMM operand [n_rows][k_pad] plus its fp32 bias (owned copies).
 struct PackedW {
   bf16_t* w = nullptr;

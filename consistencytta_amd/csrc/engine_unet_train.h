@@ -12,14 +12,6 @@
 // Gradients are ACCUMULATED into the caller's fp32 tensors (same names / shapes as the state dict),
 // i.e. `.grad` semantics; the caller zeroes them.  Activation gradients travel in bf16.
 
-struct GradTable {
-  std::unordered_map<std::string, float*> map;
-  void build(const ctta_tensor* g, int n) {
-    map.clear();
-    for (int i = 0; i < n; ++i) map[g[i].name] = const_cast<float*>(g[i].data);   // ctta_tensor is shared with the (read-only) weight tables
-  }
-};
-
 struct BCtx : UCtx {
   const GradTable* grads = nullptr;
   float* dtemb_all = nullptr;   // [B][temb_total] fp32, filled from the conv1 indicator rows

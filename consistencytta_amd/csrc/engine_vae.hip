@@ -68,7 +68,11 @@ struct VaeRes {
   bool has_sc = false;
   // enable_grad: data-gradient operands and what the differentiable forward keeps for the backward
   ConvLayer d1, d2, dsc;
-  struct Saved { const bf16_t* x = nullptr; bf16_t* t1 = nullptr; float *st1 = nullptr, *st2 = nullptr; int H = 0, W = 0; } sv;
+  PackMap m1, m2, msc;   // enable_grad == 2: where the weight gradients go
+  struct Saved {
+    const bf16_t* x = nullptr; bf16_t* t1 = nullptr; float *st1 = nullptr, *st2 = nullptr; int H = 0, W = 0;
+    const bf16_t *a = nullptr, *a2 = nullptr;   // enable_grad == 2: the two convolutions' inputs (the weight gradients' X)
+  } sv;
 };
 
 struct VaeAttn {   // AttnBlock (modules.py:178-230): single head over H*W tokens, d = C
@@ -76,11 +80,13 @@ struct VaeAttn {   // AttnBlock (modules.py:178-230): single head over H*W token
   ConvLayer q, k, v, proj;
   int C = 0;
   ConvLayer dq, dk, dv, dproj;
+  PackMap mq, mk, mv, mproj;
   struct Saved {
     const bf16_t* x = nullptr;
     bf16_t *q = nullptr, *k = nullptr, *vt = nullptr, *p = nullptr;
     float* st = nullptr;
     int H = 0, W = 0;
+    const bf16_t *g = nullptr, *o = nullptr;    // enable_grad == 2: the normalised input (X of q / k / v) and the attention output (X of proj_out)
   } sv;
 };
 
@@ -99,13 +105,24 @@ struct ctta_vae : EngineBase {
   ConvLayer d_conv_in;
   std::vector<ConvLayer> d_upsample;
   float* out_w = nullptr;                  // conv_out weight as fp32 [tap][C]
-  struct Saved { const bf16_t* h_last = nullptr; float* st_out = nullptr; int B = 0; } sv;
+  // enable_grad == 2 (fine-tuning the decoder, AudioLCM_FTVAE): parameter gradients as well
+  PackMap m_conv_in;
+  std::vector<PackMap> m_upsample;
+  struct Saved {
+    const bf16_t* h_last = nullptr; float* st_out = nullptr; int B = 0;
+    bool params = false;                     // the pending forward kept what the parameter gradients read
+    const float* z = nullptr;                // copy of the latent (post_quant_conv's X)
+    const bf16_t *zin = nullptr, *a_out = nullptr;   // conv_in's and conv_out's inputs
+    const bf16_t* up_in[CTTA_MAX_LEVELS] = {};       // the upsampling convolutions' inputs (before the x2)
+  } sv;
 };
 
 struct VCtx : RunCtx {
   int B;
   size_t gn_need = 0;
   bool grad = false;   // differentiable forward: keep what vae_backward_impl reads
+  bool pgrad = false;  // forward: also keep the convolutions' inputs; backward: also form the parameter gradients
+  const GradTable* grads = nullptr;   // backward with pgrad: the caller's gradient tensors
 };
 
 static const int kVaeGroups = 32;    // Normalize(): GroupNorm(32, eps=1e-6)  modules.py:38-41
@@ -119,14 +136,15 @@ static ctta_status vgn(VCtx& c, const GNLayer& g, const bf16_t* x, bf16_t* y, in
 // (mean, rstd) per (sample, group) kept for the backward
 static float* stats_buf(VCtx& c) { return c.grad ? c.arena->get<float>((size_t)c.B * kVaeGroups * 2) : nullptr; }
 
-static ctta_status make_vae_res(WeightStore& ws, const std::string& p, int cin, int cout, VaeRes* R, bool grad = false) {
+static ctta_status make_vae_res(WeightStore& ws, const std::string& p, int cin, int cout, VaeRes* R, bool grad = false,
+                                bool pgrad = false) {
   R->cin = cin; R->cout = cout;
   CTTA_TRY(make_gn(ws, p + "norm1.", cin, &R->n1));
-  CTTA_TRY(make_conv(ws, p + "conv1.", cout, cin, cin, 3, 3, 1, 1, &R->c1));
+  CTTA_TRY(make_conv(ws, p + "conv1.", cout, cin, cin, 3, 3, 1, 1, &R->c1, true, pgrad ? &R->m1 : nullptr));
   CTTA_TRY(make_gn(ws, p + "norm2.", cout, &R->n2));
-  CTTA_TRY(make_conv(ws, p + "conv2.", cout, cout, cout, 3, 3, 1, 1, &R->c2));
+  CTTA_TRY(make_conv(ws, p + "conv2.", cout, cout, cout, 3, 3, 1, 1, &R->c2, true, pgrad ? &R->m2 : nullptr));
   R->has_sc = cin != cout;
-  if (R->has_sc) CTTA_TRY(make_conv(ws, p + "nin_shortcut.", cout, cin, cin, 1, 1, 1, 0, &R->sc));
+  if (R->has_sc) CTTA_TRY(make_conv(ws, p + "nin_shortcut.", cout, cin, cin, 1, 1, 1, 0, &R->sc, true, pgrad ? &R->msc : nullptr));
   if (grad) {
     CTTA_TRY(make_conv_dgrad_from(ws, R->c1, cout, cin, &R->d1));
     CTTA_TRY(make_conv_dgrad_from(ws, R->c2, cout, cout, &R->d2));
@@ -147,12 +165,18 @@ static ctta_status run_vae_res(VCtx& c, VaeRes& R, const bf16_t* x, int H, int W
     st2 = stats_buf(c); ALLOC_OR_FAIL(st2);
     R.sv.x = x; R.sv.t1 = t1; R.sv.st1 = st1; R.sv.st2 = st2; R.sv.H = H; R.sv.W = W;
   }
+  bf16_t *a = nullptr, *a2 = nullptr;
+  if (c.pgrad) {  // the normalised activations are the convolutions' inputs: the weight gradients read them
+    a = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(a);
+    a2 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(a2);
+    R.sv.a = a; R.sv.a2 = a2;
+  }
   const size_t mk = A.mark();
-  bf16_t* a = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(a);
+  if (!a) { a = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(a); }
   CTTA_TRY(vgn(c, R.n1, x, a, H * W, true, st1));
   if (!t1) { t1 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(t1); }
   CTTA_TRY(run_conv2d(c, R.c1, a, c.B, H, W, false, t1, nullptr, 0, nullptr, 0));
-  bf16_t* a2 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(a2);
+  if (!a2) { a2 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(a2); }
   CTTA_TRY(vgn(c, R.n2, t1, a2, H * W, true, st2));
   const bf16_t* res = x;
   if (R.has_sc) {
@@ -169,13 +193,13 @@ static ctta_status run_vae_res(VCtx& c, VaeRes& R, const bf16_t* x, int H, int W
 // AttnBlock: single head over N = H*W tokens, d = C.  Scores are materialised in fp32
 // (B x N x N; 2 GiB at B=32, N=4096 -- 288 GB of HBM makes this the simple choice), softmaxed
 // to bf16, and multiplied by V^T; all three products run on conv_gemm.
-static ctta_status make_vae_attn(WeightStore& ws, const std::string& p, int C, VaeAttn* T, bool grad = false) {
+static ctta_status make_vae_attn(WeightStore& ws, const std::string& p, int C, VaeAttn* T, bool grad = false, bool pgrad = false) {
   T->C = C;
   CTTA_TRY(make_gn(ws, p + "norm.", C, &T->norm));
-  CTTA_TRY(make_conv(ws, p + "q.", C, C, C, 1, 1, 1, 0, &T->q));
-  CTTA_TRY(make_conv(ws, p + "k.", C, C, C, 1, 1, 1, 0, &T->k));
-  CTTA_TRY(make_conv(ws, p + "v.", C, C, C, 1, 1, 1, 0, &T->v));
-  CTTA_TRY(make_conv(ws, p + "proj_out.", C, C, C, 1, 1, 1, 0, &T->proj));
+  CTTA_TRY(make_conv(ws, p + "q.", C, C, C, 1, 1, 1, 0, &T->q, true, pgrad ? &T->mq : nullptr));
+  CTTA_TRY(make_conv(ws, p + "k.", C, C, C, 1, 1, 1, 0, &T->k, true, pgrad ? &T->mk : nullptr));
+  CTTA_TRY(make_conv(ws, p + "v.", C, C, C, 1, 1, 1, 0, &T->v, true, pgrad ? &T->mv : nullptr));
+  CTTA_TRY(make_conv(ws, p + "proj_out.", C, C, C, 1, 1, 1, 0, &T->proj, true, pgrad ? &T->mproj : nullptr));
   if (grad) {
     CTTA_TRY(make_conv_dgrad_from(ws, T->q, C, C, &T->dq));
     CTTA_TRY(make_conv_dgrad_from(ws, T->k, C, C, &T->dk));
@@ -201,8 +225,14 @@ static ctta_status run_vae_attn(VCtx& c, VaeAttn* V, const bf16_t* x, int H, int
     st = stats_buf(c); ALLOC_OR_FAIL(st);
     V->sv.x = x; V->sv.q = q; V->sv.k = k; V->sv.vt = vt; V->sv.p = p; V->sv.st = st; V->sv.H = H; V->sv.W = W;
   }
+  bf16_t *g = nullptr, *o = nullptr;
+  if (c.pgrad) {
+    g = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(g);
+    o = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(o);
+    V->sv.g = g; V->sv.o = o;
+  }
   const size_t mk = A.mark();
-  bf16_t* g = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(g);
+  if (!g) { g = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(g); }
   CTTA_TRY(vgn(c, V->norm, x, g, N, false, st));
   if (!q) { q = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(q); }
   if (!k) { k = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(k); }
@@ -230,7 +260,7 @@ static ctta_status run_vae_attn(VCtx& c, VaeAttn* V, const bf16_t* x, int H, int
   float* s = A.get<float>((size_t)gb * N * N); ALLOC_OR_FAIL(s);
   if (!p) { p = A.get<bf16_t>((size_t)gb * N * N); ALLOC_OR_FAIL(p); }
   const bool p_full = c.grad;   // the differentiable forward keeps every sample's probabilities
-  bf16_t* o = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(o);
+  if (!o) { o = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(o); }
   for (int b0 = 0; b0 < B; b0 += gb) {
     const int nb = B - b0 < gb ? B - b0 : gb;
     bf16_t* pc = p_full ? p + (size_t)b0 * N * N : p;
@@ -271,12 +301,20 @@ static ctta_status vae_forward_impl(ctta_vae* V, bool dry, const float* z, int B
   V->bind(c, stream, dry, cfg.debug_taps != 0, 32);
   c.B = B;
   c.grad = grad;
+  c.pgrad = grad && cfg.enable_grad == 2;
   V->sv.B = grad ? B : 0;
+  V->sv.params = c.pgrad;
   Arena& A = V->arena;
   A.reset();
   int H = cfg.latent_h, W = cfg.latent_w;
   const int cpad = 32;
   bf16_t* zin = A.get<bf16_t>((size_t)B * H * W * cpad); ALLOC_OR_FAIL(zin);
+  if (c.pgrad) {   // post_quant_conv's weight gradient reads the latent after the caller's tensor may be gone
+    const size_t nz = (size_t)B * cfg.embed_dim * H * W;
+    float* zc = A.get<float>(nz); ALLOC_OR_FAIL(zc);
+    if (!dry) CTTA_CHECK_HIP(hipMemcpyAsync(zc, z, nz * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    V->sv.z = zc; V->sv.zin = zin;
+  }
   if (!dry) {
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(post_quant_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, z, V->pq_w,
@@ -300,6 +338,7 @@ static ctta_status vae_forward_impl(ctta_vae* V, bool dry, const float* z, int B
       add_tap(c, "up." + std::to_string(lvl) + ".block." + std::to_string(b), h, B, ch, H, W, ch);
     }
     if (lvl != 0) {
+      V->sv.up_in[lvl] = h;
       bf16_t* u = A.get<bf16_t>((size_t)B * 4 * H * W * ch); ALLOC_OR_FAIL(u);
       CTTA_TRY(run_conv2d(c, V->upsample[lvl], h, B, H, W, true, u, nullptr, 0, nullptr, 0));
       h = u; H *= 2; W *= 2;
@@ -309,6 +348,7 @@ static ctta_status vae_forward_impl(ctta_vae* V, bool dry, const float* z, int B
   if (grad) { V->sv.h_last = h; V->sv.st_out = stats_buf(c); ALLOC_OR_FAIL(V->sv.st_out); }
   bf16_t* a = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(a);
   CTTA_TRY(vgn(c, V->norm_out, h, a, H * W, true, grad ? V->sv.st_out : nullptr));
+  V->sv.a_out = a;
   {  // conv_out (Cout = out_ch = 1): MFMA kernel with element-wise fp32 stores; NCHW with C=1 == [m]
     ctta_conv_desc d;
     desc_init(&d);
@@ -355,13 +395,98 @@ static ctta_status vconv_dgrad(VCtx& c, const ConvLayer& D, const bf16_t* dy, in
   return CTTA_OK;
 }
 
+static ctta_status vgrad_ptr(VCtx& c, const std::string& key, float** out) {
+  *out = nullptr;
+  if (c.dry) return CTTA_OK;
+  auto it = c.grads->map.find(key);
+  if (it == c.grads->map.end() || !it->second) {
+    ctta_set_error("vae_decode_backward_params: no gradient tensor for '%s'", key.c_str());
+    return CTTA_ERR_MISSING_KEY;
+  }
+  *out = it->second;
+  return CTTA_OK;
+}
+
 static ctta_status vgn_bwd(VCtx& c, const GNLayer& g, const bf16_t* x, const bf16_t* dy, bf16_t* dx, int hw,
                            const float* stats, bool silu, bool accumulate_dx) {
   const size_t need = ctta_groupnorm_bwd_scratch_floats(c.B, hw, g.c, kVaeGroups);
   if (need > c.gn_need) c.gn_need = need;
   if (!c.dry && need > c.gn_scratch_floats) { ctta_set_error("groupnorm backward scratch too small"); return CTTA_ERR_INVALID; }
+  float *dgamma = nullptr, *dbeta = nullptr;
+  if (c.pgrad) {
+    CTTA_TRY(vgrad_ptr(c, g.key + "weight", &dgamma));
+    CTTA_TRY(vgrad_ptr(c, g.key + "bias", &dbeta));
+  }
   RUN(c, ctta_groupnorm_bwd(x, dy, dx, c.B, hw, g.c, kVaeGroups, stats, g.gamma, g.beta, silu ? 1 : 0,
-                            accumulate_dx ? 1 : 0, nullptr, nullptr, 0, c.gn_scratch, c.stream));
+                            accumulate_dx ? 1 : 0, dgamma, dbeta, dgamma ? 1 : 0, c.gn_scratch, c.stream));
+  return CTTA_OK;
+}
+
+// dW / db of one convolution, ACCUMULATED into the caller's tensors (`.grad` semantics, as ctta_unet_backward).  x: the
+// layer's input, NHWC with L.cin_pad channels (ups: at half the output extent); dy [B * H * W][cout] at the OUTPUT extent.
+//   1x1                      : both operands read where they lie (ctta_wgrad_tn);
+//   3x3, widths 2 .. 64      : the implicit kernel with dY in place (ctta_wgrad_implicit_inplace; width 64 is the last
+//                              level's 1024 x 64, where most of the backward's pixels are);
+//   the x2 upsampling convs  : the same kernel over a materialised x2 copy of the input (ctta_upsample2_nearest);
+//   anything else            : im2col^T (which knows `upsample`) + conv_gemm + row sums.
+// Split-M slabs in the arena, folded by ctta_wgrad_scatter_rows_bias in slab order: no atomics.  The implicit launches aim
+// at 512 workgroups (two per CU) with up to 128 position splits: at 1024 x 64 and batch 4 a 128 -> 128 layer has four 64 x 64
+// tiles, and 0.53 / 0.17 / 0.14 ms were measured at 16 / 64 / 128 splits against 0.51 ms for the copies route
+// (profiles/vae_wgrad.txt; past two workgroups per CU the time rises again).
+static ctta_status vconv_wgrad(VCtx& c, const ConvLayer& L, const PackMap& m, const bf16_t* x, int H, int W, bool ups,
+                               const bf16_t* dy) {
+  Arena& A = *c.arena;
+  const size_t mk = A.mark();
+  const int C = L.cin_pad, N = L.cout, taps = L.kh * L.kw, K = taps * C;
+  const int64_t M = (int64_t)c.B * H * W;
+  CTTA_REQUIRE(M < (1LL << 31) - 4096 && N % 8 == 0 && C % 8 == 0 && m.n <= N && m.k_ident > 0 && m.k_ident <= K && (taps == 1 || taps == 9),
+               "vae weight gradient: unsupported layer '%s'", m.wkey.c_str());
+  float *gw, *gb;
+  CTTA_TRY(vgrad_ptr(c, m.wkey, &gw));
+  CTTA_TRY(vgrad_ptr(c, m.bkey, &gb));
+  const int ld = round_up(K + 1, 4);
+  const bool implicit = taps == 9 && ctta_wgrad_implicit_supported(9, C, H, W, C, N) != 0;
+  int S = 1;
+  if (taps == 1) {          // 128 x 128 tiles, 256 workgroups
+    const int64_t tiles = (int64_t)((N + 127) / 128) * ((C + 127) / 128);
+    while (tiles * S < 256 && S < 32 && M / (2 * S) >= 128) S *= 2;
+  } else if (implicit) {    // 64 x 64 (x 9 taps) tiles
+    const int64_t tiles = (int64_t)((N + 63) / 64) * ((C + 63) / 64);
+    while (tiles * S < 512 && S < 128 && M / (2 * S) >= 256) S *= 2;
+  } else {
+    const int64_t tiles = (int64_t)((K + 127) / 128) * ((N + 127) / 128);
+    while (tiles * S < 256 && S < 16 && M / (2 * S) >= 256) S *= 2;
+  }
+  const int mp = (int)round_up64(M, 64 * S);
+  float* slabs = A.get<float>((size_t)S * N * ld); ALLOC_OR_FAIL(slabs);
+  if (taps == 1) {
+    RUN(c, ctta_wgrad_tn(dy, N, N, x, C, C, (int)M, mp, S, K, slabs, (int64_t)N * ld, ld, c.stream));
+  } else if (implicit) {
+    if (ups) {
+      bf16_t* xu = A.get<bf16_t>((size_t)M * C); ALLOC_OR_FAIL(xu);
+      RUN(c, ctta_upsample2_nearest(x, xu, c.B, H / 2, W / 2, C, c.stream));
+      x = xu;
+    }
+    RUN(c, ctta_wgrad_implicit_inplace(dy, N, N, mp, x, C, C, c.B, H, W, 9, (int)M, S, K, 0, slabs, (int64_t)N * ld, ld, c.stream));
+  } else {
+    const int seg = mp / S;
+    bf16_t* q = A.get<bf16_t>((size_t)(K + 1) * mp); ALLOC_OR_FAIL(q);
+    bf16_t* pt = A.get<bf16_t>((size_t)N * mp); ALLOC_OR_FAIL(pt);
+    RUN(c, ctta_transpose_bf16(dy, 0, (int)M, N, N, 0, pt, 0, mp, 1, c.stream));
+    RUN(c, ctta_im2col_t(x, C, c.B, H, W, ups ? 1 : 0, H, W, L.kh, L.kw, 1, L.pad, L.pad, 1, q, mp, 0, c.stream));
+    ctta_conv_desc d;
+    desc_init(&d);
+    d.x0 = pt; d.c0 = seg; d.x_stride = mp;
+    d.batch = 1; d.hi = N; d.wi = 1; d.ho = N; d.wo = 1;
+    d.w = q; d.k_pad = mp; d.n = K;
+    d.out = slabs; d.ldc = ld; d.out_f32 = 1;
+    d.groups = S; d.x_group_stride = seg; d.w_group_stride = seg; d.out_group_stride = (int64_t)N * ld;
+    RUN(c, ctta_conv_gemm(&d, c.stream));
+    RUN(c, ctta_wgrad_rowsum(pt, N, mp, (int)M, S, H * W, 0, slabs, (int64_t)N * ld, ld, K, c.stream));
+  }
+  RUN(c, ctta_wgrad_scatter_rows_bias(slabs, S, (int64_t)N * ld, ld, m.k_ident, m.n, m.ro, nullptr, gw, K, m.n_bias, m.bidx, gb, 1,
+                                      c.stream));
+  A.release(mk);
   return CTTA_OK;
 }
 
@@ -381,6 +506,11 @@ static ctta_status bwd_vae_res(VCtx& c, const VaeRes& R, const bf16_t* dout, bf1
   if (R.has_sc) CTTA_TRY(vconv_dgrad(c, R.dsc, dout, H, W, dx, false));
   else RUN(c, ctta_add_slices(dout, R.cout, nullptr, 0, dx, R.cin, (int64_t)M, R.cin, c.stream));
   CTTA_TRY(vgn_bwd(c, R.n1, R.sv.x, da, dx, H * W, R.sv.st1, true, true));
+  if (c.pgrad) {
+    CTTA_TRY(vconv_wgrad(c, R.c2, R.m2, R.sv.a2, H, W, false, dout));
+    CTTA_TRY(vconv_wgrad(c, R.c1, R.m1, R.sv.a, H, W, false, dt1));
+    if (R.has_sc) CTTA_TRY(vconv_wgrad(c, R.sc, R.msc, R.sv.x, H, W, false, dout));
+  }
   A.release(mk);
   *dx_p = dx;
   return CTTA_OK;
@@ -439,28 +569,45 @@ static ctta_status bwd_vae_attn(VCtx& c, const VaeAttn& T, const bf16_t* dout, b
   CTTA_TRY(vconv_dgrad(c, T.dv, dv, H, W, dg, true));
   RUN(c, ctta_add_slices(dout, C, nullptr, 0, dx, C, (int64_t)M, C, c.stream));
   CTTA_TRY(vgn_bwd(c, T.norm, T.sv.x, dg, dx, N, T.sv.st, false, true));
+  if (c.pgrad) {   // four linear weight gradients: X = the attention output (proj_out) or the normalised input (q, k, v)
+    CTTA_TRY(vconv_wgrad(c, T.proj, T.mproj, T.sv.o, H, W, false, dout));
+    CTTA_TRY(vconv_wgrad(c, T.q, T.mq, T.sv.g, H, W, false, dq));
+    CTTA_TRY(vconv_wgrad(c, T.k, T.mk, T.sv.g, H, W, false, dk));
+    CTTA_TRY(vconv_wgrad(c, T.v, T.mv, T.sv.g, H, W, false, dv));
+  }
   A.release(mk);
   *dx_p = dx;
   return CTTA_OK;
 }
 
 static ctta_status vae_backward_impl(ctta_vae* V, bool dry, const float* gmel, int B, float* gz, hipStream_t stream,
-                                     size_t* gn_need) {
+                                     size_t* gn_need, const GradTable* grads = nullptr, bool pgrad = false) {
   const ctta_vae_config& cfg = V->cfg;
   VCtx c;
   V->bind(c, stream, dry, false, 32);
   c.B = B;
+  c.pgrad = pgrad; c.grads = grads;
   Arena& A = V->arena;   // continues above the differentiable forward's saved tensors
   const int up = 1 << (cfg.n_levels - 1);
   int H = cfg.latent_h * up, W = cfg.latent_w * up, ch = V->c_last;
   bf16_t* da = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(da);
   RUN(c, ctta_conv_cout1_dgrad(gmel, nullptr, V->out_w, B, H, W, 3, 3, 1, 1, ch, nullptr, 0.f, da, stream));
+  if (pgrad) {
+    float *gw, *gb;
+    CTTA_TRY(vgrad_ptr(c, "decoder.conv_out.weight", &gw));
+    CTTA_TRY(vgrad_ptr(c, "decoder.conv_out.bias", &gb));
+    const size_t mk = A.mark();
+    float* part = A.get<float>(ctta_conv_cout1_wgrad_scratch_floats(B, H, W, 3, 3, ch)); ALLOC_OR_FAIL(part);
+    RUN(c, ctta_conv_cout1_wgrad(gmel, V->sv.a_out, B, H, W, 3, 3, 1, 1, ch, gw, gb, 1, part, stream));
+    A.release(mk);
+  }
   bf16_t* dh = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(dh);
   CTTA_TRY(vgn_bwd(c, V->norm_out, V->sv.h_last, da, dh, H * W, V->sv.st_out, true, false));
   for (int lvl = 0; lvl < cfg.n_levels; ++lvl) {
     if (lvl != 0) {   // u = conv(nearest x2 (h)): data gradient at the fine resolution, then the 2x2 sum
       bf16_t* du = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(du);
       CTTA_TRY(vconv_dgrad(c, V->d_upsample[lvl], dh, H, W, du, false));
+      if (pgrad) CTTA_TRY(vconv_wgrad(c, V->upsample[lvl], V->m_upsample[lvl], V->sv.up_in[lvl], H, W, true, dh));
       H /= 2; W /= 2;
       bf16_t* dl = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(dl);
       RUN(c, ctta_pool2_sum(du, dl, B, H, W, ch, 0, stream));
@@ -477,7 +624,16 @@ static ctta_status vae_backward_impl(ctta_vae* V, bool dry, const float* gmel, i
   const int zc = V->d_conv_in.cout;
   bf16_t* dzin = A.get<bf16_t>((size_t)B * H * W * zc); ALLOC_OR_FAIL(dzin);
   CTTA_TRY(vconv_dgrad(c, V->d_conv_in, dh, H, W, dzin, false));
-  if (!dry) {
+  if (pgrad) {
+    CTTA_TRY(vconv_wgrad(c, V->conv_in, V->m_conv_in, V->sv.zin, H, W, false, dh));
+    float *gw, *gb;
+    CTTA_TRY(vgrad_ptr(c, "post_quant_conv.weight", &gw));
+    CTTA_TRY(vgrad_ptr(c, "post_quant_conv.bias", &gb));
+    float* part = A.get<float>(ctta_post_quant_wgrad_scratch_floats(B, H * W, cfg.embed_dim, cfg.z_channels)); ALLOC_OR_FAIL(part);
+    RUN(c, ctta_post_quant_wgrad(dzin, zc, V->sv.z, 1.0f / cfg.scale_factor, B, cfg.embed_dim, cfg.z_channels, H * W, gw, gb, 1, part,
+                                 stream));
+  }
+  if (!dry && gz) {
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(post_quant_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, dzin, zc,
                        V->pq_w, 1.0f / cfg.scale_factor, B, cfg.embed_dim, cfg.z_channels, H * W, gz);
@@ -496,26 +652,27 @@ static ctta_status vae_build(ctta_vae* V) {
   CTTA_TRY(ws.add_vector("post_quant_conv.weight", cfg.z_channels * cfg.embed_dim, &V->pq_w));
   CTTA_TRY(ws.add_vector("post_quant_conv.bias", cfg.z_channels, &V->pq_b));
   const std::string p = "decoder.";
-  const bool grad = cfg.enable_grad != 0;
-  CTTA_TRY(make_conv(ws, p + "conv_in.", block_in, cfg.z_channels, 32, 3, 3, 1, 1, &V->conv_in));
+  const bool grad = cfg.enable_grad != 0, pgrad = cfg.enable_grad == 2;
+  CTTA_TRY(make_conv(ws, p + "conv_in.", block_in, cfg.z_channels, 32, 3, 3, 1, 1, &V->conv_in, true, pgrad ? &V->m_conv_in : nullptr));
   if (grad) CTTA_TRY(make_conv_dgrad_from(ws, V->conv_in, block_in, cfg.z_channels, &V->d_conv_in));
-  CTTA_TRY(make_vae_res(ws, p + "mid.block_1.", block_in, block_in, &V->mid1, grad));
-  CTTA_TRY(make_vae_attn(ws, p + "mid.attn_1.", block_in, &V->attn, grad));
-  CTTA_TRY(make_vae_res(ws, p + "mid.block_2.", block_in, block_in, &V->mid2, grad));
+  CTTA_TRY(make_vae_res(ws, p + "mid.block_1.", block_in, block_in, &V->mid1, grad, pgrad));
+  CTTA_TRY(make_vae_attn(ws, p + "mid.attn_1.", block_in, &V->attn, grad, pgrad));
+  CTTA_TRY(make_vae_res(ws, p + "mid.block_2.", block_in, block_in, &V->mid2, grad, pgrad));
   V->up.resize(nres);
   V->upsample.resize(nres);
   V->d_upsample.resize(nres);
+  V->m_upsample.resize(nres);
   for (int lvl = nres - 1; lvl >= 0; --lvl) {
     const int block_out = cfg.ch * cfg.ch_mult[lvl];
     V->up[lvl].resize(cfg.num_res_blocks + 1);
     for (int b = 0; b <= cfg.num_res_blocks; ++b) {
       CTTA_TRY(make_vae_res(ws, p + "up." + std::to_string(lvl) + ".block." + std::to_string(b) + ".", block_in,
-                            block_out, &V->up[lvl][b], grad));
+                            block_out, &V->up[lvl][b], grad, pgrad));
       block_in = block_out;
     }
     if (lvl != 0) {
       CTTA_TRY(make_conv(ws, p + "up." + std::to_string(lvl) + ".upsample.conv.", block_in, block_in, block_in, 3, 3, 1,
-                         1, &V->upsample[lvl]));
+                         1, &V->upsample[lvl], true, pgrad ? &V->m_upsample[lvl] : nullptr));
       if (grad) CTTA_TRY(make_conv_dgrad_from(ws, V->upsample[lvl], block_in, block_in, &V->d_upsample[lvl]));
     }
   }
@@ -535,6 +692,7 @@ extern "C" ctta_status ctta_vae_create(const ctta_vae_config* cfg, const ctta_te
   CTTA_REQUIRE(cfg->ch % 32 == 0, "vae_create: ch=%d must be a multiple of 32 (GroupNorm(32))", cfg->ch);
   CTTA_REQUIRE(cfg->scale_factor != 0.f, "vae_create: scale_factor is zero");
   CTTA_REQUIRE(!cfg->enable_grad || cfg->z_channels % 8 == 0, "vae_create: enable_grad needs z_channels %% 8 == 0");
+  CTTA_REQUIRE(cfg->enable_grad >= 0 && cfg->enable_grad <= 2, "vae_create: enable_grad=%d (0, 1 or 2)", cfg->enable_grad);
   hipStream_t s = (hipStream_t)stream;
   ctta_vae* V = new ctta_vae();
   V->cfg = *cfg;
@@ -549,7 +707,7 @@ extern "C" ctta_status ctta_vae_create(const ctta_vae_config* cfg, const ctta_te
     st = vae_forward_impl(V, true, nullptr, cfg->max_batch, nullptr, s, &gn_need);
     if (st == CTTA_OK && cfg->enable_grad) {   // the differentiable forward keeps more, and the backward runs on top
       st = vae_forward_impl(V, true, nullptr, cfg->max_batch, nullptr, s, &gn_need, true);
-      if (st == CTTA_OK) st = vae_backward_impl(V, true, nullptr, cfg->max_batch, nullptr, s, &gn_need);
+      if (st == CTTA_OK) st = vae_backward_impl(V, true, nullptr, cfg->max_batch, nullptr, s, &gn_need, nullptr, cfg->enable_grad == 2);
     }
   }
   if (st == CTTA_OK)
@@ -589,6 +747,29 @@ extern "C" ctta_status ctta_vae_decode_backward(ctta_vae* V, const float* grad_m
   const ctta_status st = vae_backward_impl(V, false, grad_mel, batch, grad_z, (hipStream_t)stream, nullptr);
   V->sv.B = 0;   // the saved tensors are consumed (the backward's temporaries overwrote the arena above them)
   return st;
+}
+
+// The same backward on a handle created with enable_grad = 2, also ACCUMULATING d loss / d parameter into the caller's fp32
+// tensors (state-dict names and shapes: every decoder.* and post_quant_conv.* key).  grad_z may be NULL.
+extern "C" ctta_status ctta_vae_decode_backward_params(ctta_vae* V, const float* grad_mel, int batch, float* grad_z,
+                                                       const ctta_tensor* grads, int n_grads, void* stream) {
+  CTTA_REQUIRE(V && grad_mel && grads && n_grads >= 1, "vae_decode_backward_params: null pointer");
+  CTTA_REQUIRE(V->cfg.enable_grad == 2, "vae_decode_backward_params: the handle was created without enable_grad = 2");
+  CTTA_REQUIRE(V->sv.B == batch && V->sv.params,
+               "vae_decode_backward_params: no differentiable forward of batch %d is pending on this handle", batch);
+  GradTable gt;
+  gt.build(grads, n_grads);
+  WsBind bind(V->splitws);
+  const ctta_status st = vae_backward_impl(V, false, grad_mel, batch, grad_z, (hipStream_t)stream, nullptr, &gt, true);
+  V->sv.B = 0;
+  return st;
+}
+// A new state dict into an existing handle: the forward packs, the data-gradient packs and conv_out's fp32 taps are
+// repacked in place (after an optimizer step on the decoder), as ctta_unet_load_weights does for the U-Net.
+extern "C" ctta_status ctta_vae_load_weights(ctta_vae* V, const ctta_tensor* weights, int n_weights, void* stream) {
+  CTTA_REQUIRE(V && weights, "vae_load_weights: null pointer");
+  V->sv.B = 0;   // a pending differentiable forward belonged to the old weights
+  return V->load_weights(weights, n_weights, (hipStream_t)stream);
 }
 
 extern "C" size_t ctta_vae_arena_bytes(const ctta_vae* V) { return V ? V->arena_bytes() : 0; }

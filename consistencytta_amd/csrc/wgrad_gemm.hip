@@ -88,6 +88,8 @@ struct WgTile {
 // NAT (round 4): dY is read where it lies -- natural 64-position x 64-channel tiles, the B operand through the same transposing
 // LDS read as X -- and the bias / per-sample column sums are added up by the workgroups of channel tile 0 from the vectors
 // they stage (no dY^T copy, no row-sum launch).
+// (wgrad_implicit_w64_kernel below is this kernel's T = 9 body at image width 64: fetch, park, fold_sums, the MFMA loop and
+// the epilogue exist twice -- a fix to one of them belongs in both.)
 template <int T, bool NAT>
 __global__ __launch_bounds__(256, 2) void wgrad_implicit_kernel(const WgradParams p) {
   using K = WgTile<T>;
@@ -309,6 +311,205 @@ __global__ __launch_bounds__(256, 2) void wgrad_implicit_kernel(const WgradParam
   }
 }
 
+// The 3x3 product at image width 64 (the VAE decoder's last level, 1024 x 64: the student U-Net never has W > 16).  A
+// 64-position chunk is ONE image row, its patch the three rows around it with their border: 3 x 66 = 198 pixels, 198 RSX +
+// 64 RSN + the column-sum phases = 50 KB per workgroup (two per CU), seven patch vectors per thread instead of five.  The
+// MFMA loop, the k-slot order and the epilogue are wgrad_implicit_kernel<9, NAT>'s; it is a kernel of its own so that the
+// U-Net's instantiations keep their registers, their wait counts and their bits -- and a copy: a fix to fetch, park,
+// fold_sums or the epilogue of either kernel belongs in both.
+struct WgTile64 {
+  static constexpr int W = 64, WP = W + 2, NPIX = 3 * WP;
+  static constexpr int XV = (NPIX * (WgTile<9>::TC / 8) + 255) / 256;
+};
+template <bool NAT>
+__global__ __launch_bounds__(256, 2) void wgrad_implicit_w64_kernel(const WgradParams p) {
+  using K = WgTile<9>;
+  constexpr int T = 9, TC = K::TC, RSX = K::RSX, RSB = NAT ? K::RSN : K::RSB;
+  constexpr int W = WgTile64::W, Wp = WgTile64::WP, npix = WgTile64::NPIX, XV = WgTile64::XV;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* xs = smem;                                   // [198 pixels][RSX]
+  unsigned char* bs = smem + (size_t)npix * RSX;              // [64 n][RSB]   (NAT: [64 positions][RSN])
+  float* red = reinterpret_cast<float*>(bs + 64 * RSB);       // NAT: [32 row phases][64 channels] for the column sums
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lq = lane & 15, kg = lane >> 4;
+  const int c0 = blockIdx.x * TC, n0 = blockIdx.y * 64, split = blockIdx.z;
+  const int m_lo = split * p.seg, m_hi = min(m_lo + p.seg, p.mp);
+
+  // position k of the chunk is column k of the row: tap (0, 0) is pixel k of the bordered patch
+  int abase[2][2], nbase[2][2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int k = 32 * ks + 16 * r + 4 * kg + (lq >> 2);
+      abase[ks][r] = k * RSX + (wave * 16 + (lq & 3) * 4) * 2;
+      nbase[ks][r] = k * RSB + (lq & 3) * 8;
+    }
+  const int bbase = lq * RSB + kg * 8;
+  const bool do_sums = NAT && p.bias_col >= 0 && blockIdx.x == 0;
+  float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float tot = 0.f;
+  int acc_sample = -1;
+  if (do_sums && !p.direct.grad_w && tid < 64 && n0 + tid < p.N)
+    for (int b = 0; b < p.sample_cols; ++b) p.slabs[(size_t)split * p.slab_stride + (size_t)(n0 + tid) * p.ld + p.bias_col + 1 + b] = 0.f;
+
+  f32x4_t acc[T][4];
+#pragma unroll
+  for (int a = 0; a < T; ++a)
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[a][nb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+  uint4 xr[XV], br[2];
+  bool xok[XV], bok[2];
+#pragma unroll
+  for (int i = 0; i < XV; ++i) xok[i] = true;
+  bok[0] = bok[1] = true;
+  auto fetch = [&](int m0) {     // branch-free: clamped addresses, zeros selected when the vectors are parked
+    const int m0c = m0 < p.M ? m0 : 0;
+    const int img = m0c / p.HW, oh = (m0c - img * p.HW) / W;
+#pragma unroll
+    for (int i = 0; i < XV; ++i) {
+      const int q = tid + i * 256;
+      const int pix = q / (TC / 8), ch = q - pix * (TC / 8);
+      const int pr = pix / Wp, pc = pix - pr * Wp;
+      const int ih = oh - 1 + pr, iw = pc - 1;
+      const bool ok = pix < npix && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)W && c0 + ch * 8 < p.C && m0 < p.M;
+      const int ihc = ih < 0 ? 0 : (ih >= p.H ? p.H - 1 : ih), iwc = iw < 0 ? 0 : (iw >= W ? W - 1 : iw);
+      const int cc = c0 + ch * 8 < p.C ? c0 + ch * 8 : 0;
+      xr[i] = *reinterpret_cast<const uint4*>(p.x + ((size_t)(img * p.H + ihc) * W + iwc) * p.xld + cc);
+      xok[i] = ok;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int q = tid + i * 256;
+      const int row = q >> 3, ch = q & 7;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if constexpr (NAT) {
+        const bool ok = m0 + row < p.M && n0 + ch * 8 < p.N;
+        const int rc = m0 + row < p.M ? m0 + row : p.M - 1, nc = n0 + ch * 8 < p.N ? n0 + ch * 8 : 0;
+        v = *reinterpret_cast<const uint4*>(p.dy + (size_t)rc * p.ldy + nc);
+        bok[i] = ok;
+      } else {
+        if (n0 + row < p.N) v = *reinterpret_cast<const uint4*>(p.dyt + (size_t)(n0 + row) * p.mp + m0 + ch * 8);   // the pad of dY^T is zero
+      }
+      br[i] = v;
+    }
+  };
+  auto fold_sums = [&](int sample) {     // every thread of a do_sums workgroup (uniform): 32 row phases in a fixed order
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[(tid >> 3) * 64 + (tid & 7) * 8 + e] = bsum[e]; bsum[e] = 0.f; }
+    __syncthreads();
+    if (tid < 64) {
+      float t = 0.f;
+      for (int r = 0; r < 32; ++r) t += red[r * 64 + tid];
+      tot += t;
+      if (!p.direct.grad_w && sample >= 0 && sample < p.sample_cols && n0 + tid < p.N)
+        p.slabs[(size_t)split * p.slab_stride + (size_t)(n0 + tid) * p.ld + p.bias_col + 1 + sample] = t;
+    }
+  };
+  auto park = [&]() {
+#pragma unroll
+    for (int i = 0; i < XV; ++i) {
+      const int q = tid + i * 256;
+      const int pix = q / (TC / 8), ch = q - pix * (TC / 8);
+      if (pix < npix) *reinterpret_cast<uint4*>(xs + (size_t)pix * RSX + ch * 16) = xok[i] ? xr[i] : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int q = tid + i * 256;
+      if (!bok[i]) br[i] = make_uint4(0, 0, 0, 0);
+      *reinterpret_cast<uint4*>(bs + (size_t)(q >> 3) * RSB + (q & 7) * 16) = br[i];
+      if (do_sums) {
+        float f[8];
+        unpack8(br[i], f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bsum[e] += f[e];
+      }
+    }
+  };
+
+  if (m_lo < m_hi) fetch(m_lo);
+  for (int m0 = m_lo; m0 < m_hi; m0 += 64) {
+    if (do_sums && p.sample_cols > 0 && m0 < p.M) {     // a row lies inside one sample
+      const int b = m0 / p.HW;
+      if (acc_sample >= 0 && b != acc_sample) fold_sums(acc_sample);
+      acc_sample = b;
+    }
+    __syncthreads();                       // the previous row's fragments have been read
+    park();
+    __syncthreads();
+    if (m0 + 64 < m_hi) fetch(m0 + 64);    // in flight behind this row's MFMAs
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8_t bf[4];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        if constexpr (NAT) {
+          const s16x4_t b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bs + nbase[ks][0] + nb * 32));
+          const s16x4_t b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bs + nbase[ks][1] + nb * 32));
+          const uint2 u0 = __builtin_bit_cast(uint2, b0), u1 = __builtin_bit_cast(uint2, b1);
+          bf[nb] = __builtin_bit_cast(bf16x8_t, make_uint4(u0.x, u0.y, u1.x, u1.y));
+        } else {
+          const unsigned char* q = bs + bbase + nb * 16 * RSB + ks * 64;
+          const uint2 lo = *reinterpret_cast<const uint2*>(q), hi = *reinterpret_cast<const uint2*>(q + 32);
+          bf[nb] = __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const int toff = ((t / 3) * Wp + (t % 3)) * RSX;
+        const s16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(xs + abase[ks][0] + toff));
+        const s16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(xs + abase[ks][1] + toff));
+        const uint2 u0 = __builtin_bit_cast(uint2, a0), u1 = __builtin_bit_cast(uint2, a1);
+        const bf16x8_t af = __builtin_bit_cast(bf16x8_t, make_uint4(u0.x, u0.y, u1.x, u1.y));
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[t][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[nb], acc[t][nb], 0, 0, 0);
+      }
+    }
+  }
+
+  if (do_sums) {       // the last sample's share, then the split's total = the bias column
+    fold_sums(acc_sample);
+    if (tid < 64 && n0 + tid < p.N) {
+      if (p.direct.grad_w) {
+        const int n = n0 + tid;
+        if (p.direct.grad_b && n < p.direct.n_bias) {
+          const int j = p.direct.bias_idx ? p.direct.bias_idx[n] : n;
+          if (j >= 0) p.direct.grad_b[j] += tot;
+        }
+      } else {
+        p.slabs[(size_t)split * p.slab_stride + (size_t)(n0 + tid) * p.ld + p.bias_col] = tot;
+      }
+    }
+  }
+  // row n of the slab receives, from this lane, the 36 consecutive floats of channels cc .. cc + 3: [e][t] = acc[t][..][e]
+  float* slab = p.slabs + (size_t)split * p.slab_stride;
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    const int n = n0 + nb * 16 + lq;
+    const int cc = c0 + wave * 16 + kg * 4;
+    if (n < p.N && cc < p.C) {
+      float v[4 * T];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int t = 0; t < T; ++t) v[e * T + t] = acc[t][nb][e];
+      if (p.direct.grad_w) {
+        const int ro = n < p.direct.n_rows ? p.direct.row_off[n] : -1;
+        if (ro >= 0) {
+#pragma unroll
+          for (int q = 0; q < T; ++q) direct_add4(p.direct, ro, cc * T + 4 * q, v + 4 * q);
+        }
+      } else {
+        float* dst = slab + (size_t)n * p.ld + (size_t)cc * T;
+#pragma unroll
+        for (int q = 0; q < T; ++q) *reinterpret_cast<float4*>(dst + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+      }
+    }
+  }
+}
+
 // slab[s][n][col0]         = sum over split s's positions of dY^T[n][m]                         (bias gradient)
 // slab[s][n][col0 + 1 + b] = the same restricted to sample b = m / hw, b < nb                  (d temb of the resnets' conv1)
 // One wave per (output channel, split); 8 positions per lane and load (the row is contiguous and 16-byte aligned: mp % 8 == 0).
@@ -343,7 +544,7 @@ extern "C" int ctta_wgrad_implicit_supported(int taps, int c, int h, int w, int 
   if (c < 32 || c % 8 != 0 || x_ld % 8 != 0 || n < 8) return 0;
   if (taps == 1) return 1;
   if (taps != 9) return 0;
-  if (w < 2 || w > 32 || (w & (w - 1)) != 0) return 0;                 // 64 / w rows per chunk, patch <= 136 pixels
+  if (w < 2 || w > 64 || (w & (w - 1)) != 0) return 0;                 // 64 / w rows per chunk, patch <= 136 pixels (w = 64: 198, its own kernel)
   return ((long long)h * w) % 64 == 0 ? 1 : 0;
 }
 
@@ -394,7 +595,7 @@ static ctta_status wgrad_implicit_launch(const void* dyt, const void* dy_nat, in
                "wgrad_implicit: bad arguments");
   CTTA_REQUIRE(ctta_wgrad_implicit_supported(taps, c, h, w, x_ld, n),
                "wgrad_implicit: taps=%d c=%d h=%d w=%d x_ld=%d is outside the kernel's range (1x1, or 3x3 stride 1 pad 1 with a "
-               "power-of-two width <= 32 and h*w a multiple of 64; c >= 32, multiples of 8)", taps, c, h, w, x_ld);
+               "power-of-two width <= 64 and h*w a multiple of 64; c >= 32, multiples of 8)", taps, c, h, w, x_ld);
   CTTA_REQUIRE(mp % (64 * splits) == 0 && mp % 8 == 0, "wgrad_implicit: mp=%d must be a multiple of 64 * splits=%d", mp, 64 * splits);
   CTTA_REQUIRE(ld % 4 == 0 && ld >= c * taps + (bias_col >= 0 ? 1 + sample_cols : 0) && slab_stride % 4 == 0 &&
                ((uintptr_t)slabs & 15) == 0, "wgrad_implicit: slab rows must be 16-byte aligned and hold c * taps (+ bias) columns");
@@ -410,7 +611,13 @@ static ctta_status wgrad_implicit_launch(const void* dyt, const void* dy_nat, in
   hipStream_t s = (hipStream_t)stream;
   const bool prof = ctta_prof_active();
   if (prof) ctta_prof_begin(0, 130 + (taps == 9 ? 1 : 0), n, (long long)c * taps, mp / splits, splits, s);
-  if (taps == 9 && nat) {
+  if (taps == 9 && w == WgTile64::W) {
+    using K = WgTile<9>;
+    const size_t smem = (size_t)WgTile64::NPIX * K::RSX + 64 * (nat ? K::RSN + 32 * (int)sizeof(float) : K::RSB);
+    dim3 grid((unsigned)((c + K::TC - 1) / K::TC), (unsigned)((n + 63) / 64), (unsigned)splits);
+    if (nat) hipLaunchKernelGGL((wgrad_implicit_w64_kernel<true>), grid, dim3(256), smem, s, p);
+    else hipLaunchKernelGGL((wgrad_implicit_w64_kernel<false>), grid, dim3(256), smem, s, p);
+  } else if (taps == 9 && nat) {
     using K = WgTile<9>;
     const size_t smem = (size_t)K::MAXPIX * K::RSX + 64 * K::RSN + 32 * 64 * sizeof(float);
     dim3 grid((unsigned)((c + K::TC - 1) / K::TC), (unsigned)((n + 63) / 64), (unsigned)splits);

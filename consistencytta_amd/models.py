@@ -17,7 +17,9 @@ runs the HIP engine's own backward pass and fills `student_unet` `.grad`s, so th
 buffer, fused AdamW, two-shadow EMA) that replaces accelerate's DDP wrapper (train.py:377-379),
 whose autograd hooks cannot see gradients produced outside autograd.
 """
+import math
 import os
+from collections import OrderedDict
 from copy import deepcopy
 from time import time
 
@@ -26,7 +28,7 @@ import torch
 from torch import nn
 
 from . import _native as N
-from . import dist_util
+from . import dist_util, spec
 from .modules import AutoencoderKL, UNet2DConditionGuidedModel, UNet2DConditionModel
 from .scheduler import DDIMScheduler, DDPMScheduler, HeunDiscreteScheduler
 
@@ -1696,6 +1698,140 @@ def _capture_train_graph(self, optimizer, z_0, prompt, segmented=None, accumulat
 
 
 AudioLCM.capture_train_graph = _capture_train_graph
+
+
+class AudioLCM_FTVAE(AudioLCM):
+    """models/audio_consistency_model_ftvae.py: the CLAP fine-tuning stage with the VAE decoder and post_quant_conv trained
+    beside the student U-Net, and EMA copies of both that `vae.decode_first_stage(use_ema=True)` decodes through.  The
+    decoder's parameter gradients come from the engine's own backward (ctta_vae_decode_backward_params) and land in the VAE's
+    flat gradient buffer; a second FusedAdamW with the student's hyper-parameters runs over its trainable prefix (AdamW is
+    element-wise: two instances equal the reference's single optimizer over the concatenated list, train_utils.py:31-36).
+    Single process only: the decoder's gradients are not in the bucketed all-reduce."""
+
+    def __init__(self, *args, loss_type="clap", **kwargs):
+        assert loss_type == "clap"
+        super().__init__(*args, loss_type=loss_type, **kwargs)
+        from .modules import _DecoderShadow
+        dec = spec.vae_decoder_param_spec(self.vae.ddconfig, self.vae.embed_dim)
+        self.ema_vae_decoder = _DecoderShadow(OrderedDict((k[len("decoder."):], v) for k, v in dec.items() if k.startswith("decoder.")))
+        self.ema_vae_pqconv = _DecoderShadow(OrderedDict((k[len("post_quant_conv."):], v) for k, v in dec.items()
+                                                         if k.startswith("post_quant_conv.")))
+        dev = self.vae.device
+        self.ema_vae_decoder.to(dev).load_state_dict(self.vae.decoder.state_dict())
+        self.ema_vae_pqconv.to(dev).load_state_dict(self.vae.post_quant_conv.state_dict())
+        self.vae.train_decoder_(True)
+        self.vae.decoder.train(self.training)
+        self._attach_ema()
+
+    def _attach_ema(self):
+        # plain attributes: the holders are this model's submodules, not a second time the VAE's (its flat buffers hold
+        # the VAE's own parameters only)
+        object.__setattr__(self.vae, "ema_decoder", self.ema_vae_decoder)
+        object.__setattr__(self.vae, "ema_post_quant_conv", self.ema_vae_pqconv)
+
+    def load_pretrained(self, state_dict, strict=True):
+        """:69-91: the U-Nets as AudioLCM loads them, then the four decoder modules by name; a `loss.vae.*` duplicate of a
+        `vae.*` entry (the CLAP loss holds the same VAE) fills only what its twin did not."""
+        info = super().load_pretrained(state_dict, strict)
+        for module, name in ((self.vae.decoder, "vae.decoder"), (self.vae.post_quant_conv, "vae.post_quant_conv"),
+                             (self.ema_vae_decoder, "ema_vae_decoder"), (self.ema_vae_pqconv, "ema_vae_pqconv")):
+            off = len(name) + 1
+            module_sd = {}
+            for key, val in state_dict.items():
+                if name in key:
+                    if "loss" in key:
+                        new_key = key[5:]
+                        if new_key[off:] not in module_sd:
+                            module_sd[new_key[off:]] = val
+                    else:
+                        module_sd[key[off:]] = val
+            module.load_state_dict(module_sd)
+        self._attach_ema()
+        return info
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.ema_vae_decoder.eval()
+        self.vae.decoder.train(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def check_eval_mode(self):
+        AudioDistilledModel.check_eval_mode(self)
+        for model, name in ((self.student_target_unet, "student_target_unet"), (self.ema_vae_decoder, "ema_vae_decoder"),
+                            (self.vae.vocoder, "vae.vocoder")):
+            assert model.training is False, f"The {name} is not in eval mode."
+            for p in model.parameters():
+                assert p.requires_grad is False, f"The {name} is not frozen."
+        for p in self.ema_vae_pqconv.parameters():
+            assert p.requires_grad is False, "The ema_vae_pqconv is not frozen."
+
+    # ---- training
+    def _ema_flat(self):
+        """One buffer for both EMA holders, laid out like the trainable prefix of the VAE's flat buffer."""
+        holders = list(self.ema_vae_decoder.parameters()) + list(self.ema_vae_pqconv.parameters())
+        flat = getattr(self, "_vae_ema_flat", None)
+        if flat is not None and flat.device == holders[0].device and all(
+                flat.data_ptr() <= p.data_ptr() < flat.data_ptr() + flat.numel() * 4 for p in (holders[0], holders[-1])):
+            return flat
+        flat = torch.empty(sum(p.numel() for p in holders), dtype=torch.float32, device=holders[0].device)
+        off = 0
+        for p in holders:
+            n = p.numel()
+            flat[off:off + n].copy_(p.data.reshape(-1))
+            p.data = flat[off:off + n].view(p.shape)
+            off += n
+        self._vae_ema_flat = flat
+        return flat
+
+    def _update_vae_ema(self):
+        vae, n = self.vae, self.vae.n_trainable()
+        src, dst = vae.flatten_parameters_(), self._ema_flat()
+        assert dst.numel() == n and 0 <= self.ema_decay <= 1
+        with torch.cuda.device(src.device):
+            N.check(N.lib().ctta_ema_update2(N.ptr(src), N.ptr(dst), float(self.ema_decay), N.c_void_p(0), 0.0, n, N.stream_ptr()))
+        self.ema_vae_decoder.mark_weights_changed()
+        self.ema_vae_pqconv.mark_weights_changed()
+
+    def update_ema(self):
+        super().update_ema()
+        self._update_vae_ema()
+
+    def prepare_training(self, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, broadcast=True):
+        """The student's optimizer; the decoder's (same hyper-parameters) rides on it as `.vae_optimizer`."""
+        from .optim import FusedAdamW
+        if dist_util.dist.is_initialized() and dist_util.dist.get_world_size() > 1:
+            raise NotImplementedError("AudioLCM_FTVAE trains on one process: the decoder's gradients are not in the gradient all-reduce")
+        opt = super().prepare_training(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, broadcast=broadcast)
+        self.vae.train_decoder_(True)
+        opt.vae_optimizer = FusedAdamW(self.vae, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._ema_flat()
+        return opt
+
+    def train_step(self, z_0, prompt, optimizer, lr_scheduler=None, gt_wav=None, skip_nan=True, accumulation_steps=1, **fw):
+        """AudioLCM.train_step (its backward runs the decoder's too), then on the same boundary the decoder's AdamW, zero_grad
+        and EMA.  A NaN loss skips both updates together; the EMAs still move (train_utils.py:167-183)."""
+        if dist_util.dist.is_initialized() and dist_util.dist.get_world_size() > 1:
+            raise NotImplementedError("AudioLCM_FTVAE trains on one process: the decoder's gradients are not in the gradient all-reduce")
+        vopt = getattr(optimizer, "vae_optimizer", None)
+        if vopt is None:
+            raise N.CttaError("AudioLCM_FTVAE.train_step needs the optimizer prepare_training() returned (it carries the decoder's)")
+        lr_now = optimizer.param_groups[0]["lr"]          # one schedule drives both optimizers
+        value = super().train_step(z_0, prompt, optimizer, lr_scheduler, gt_wav=gt_wav, skip_nan=skip_nan,
+                                   accumulation_steps=accumulation_steps, **fw)
+        if self._micro % max(1, int(accumulation_steps)) != 0:
+            return value
+        if not (skip_nan and math.isnan(value)):
+            vopt.param_groups[0]["lr"] = lr_now
+            vopt.step()
+        vopt.zero_grad()
+        self._update_vae_ema()
+        return value
+
+    def capture_train_graph(self, *args, **kwargs):
+        raise NotImplementedError("AudioLCM_FTVAE: the captured training step does not cover the decoder's optimizer; use train_step")
 
 
 class ConsistencyTTA(nn.Module):

@@ -227,7 +227,7 @@ class _ParamTree(nn.Module):
             return True, N.EngineHandle(v.destroy)
         if k == "_eng":
             return True, {w: [N.EngineHandle(e.destroy) for e in es] for w, es in v.items()}
-        if k.startswith("_h_") or k in ("_vae_pending", "_voc_pending"):
+        if k.startswith("_h_") or k in ("_vae_pending", "_voc_pending", "_anchor"):
             return True, None
         return False, v
 
@@ -595,6 +595,54 @@ class _VaeDecodeWithGrad(torch.autograd.Function):
         return gz.to(ctx.dtype), None
 
 
+class _VaeDecodeWithParamGrad(torch.autograd.Function):
+    """decode_first_stage(allow_grad=True) for a TRAINABLE decoder (AudioLCM_FTVAE): the backward also accumulates
+    d loss / d parameter of every decoder.* / post_quant_conv.* tensor into the `.grad` views of the VAE's flat gradient
+    buffer (ctta_vae_decode_backward_params).  `anchor` is a scalar that requires grad, so that the backward runs even when
+    the latent itself does not require grad (the pattern of models._EngineLoss)."""
+
+    @staticmethod
+    def forward(ctx, z, anchor, vae):
+        B, _, T, F = z.shape
+        h = vae._ensure_vae(B, T, F, grad=2)
+        zz = z.detach().to(device=vae.device, dtype=torch.float32).contiguous()
+        up = 2 ** (len(vae.ddconfig["ch_mult"]) - 1)
+        mel = torch.empty((B, vae.ddconfig["out_ch"], T * up, F * up), dtype=torch.float32, device=vae.device)
+        with torch.cuda.device(vae.device):
+            N.check(N.lib().ctta_vae_decode_with_grad(h, N.ptr(zz), B, N.ptr(mel), N.stream_ptr()))
+        ctx.vae, ctx.shape, ctx.dtype, ctx.need_z = vae, tuple(z.shape), z.dtype, z.requires_grad
+        ctx.token = vae._vae_pending = object()
+        return mel
+
+    @staticmethod
+    def backward(ctx, grad_mel):
+        vae = ctx.vae
+        if vae._vae_pending is not ctx.token:
+            raise N.CttaError("decode_first_stage(allow_grad=True): the decoder ran again (or its handle was rebuilt) "
+                              "before this backward -- only the latest differentiable decode can be back-propagated")
+        g = grad_mel.to(device=vae.device, dtype=torch.float32).contiguous()
+        gz = torch.empty(ctx.shape, dtype=torch.float32, device=vae.device) if ctx.need_z else None
+        vae.flat_grad_()
+        if not vae.grads_alias_flat():
+            vae.realias_grads_()
+        table, keep = N.tensor_table({k: p.grad for k, p in vae._decoder_named()})
+        with torch.cuda.device(vae.device):
+            N.check(N.lib().ctta_vae_decode_backward_params(vae._eng["vae"][1].h, N.ptr(g), ctx.shape[0], N.ptr(gz), table,
+                                                            len(table), N.stream_ptr()))
+        vae._vae_pending = None
+        return (gz.to(ctx.dtype) if ctx.need_z else None), None, None
+
+
+class _DecoderShadow(_ParamTree):
+    """Frozen parameter holder with the decoder's (or post_quant_conv's) own key names: the EMA copies of AudioLCM_FTVAE
+    (audio_consistency_model_ftvae.py:52-57)."""
+
+    def __init__(self, table):
+        super().__init__()
+        self._register(table, frozen=tuple(table))
+        self.eval()
+
+
 class _VocodeWithGrad(torch.autograd.Function):
     """vocoder(mels) of vocoder_infer(allow_grad=True) (hifigan/utilities.py:79-80) for the frozen generator."""
 
@@ -668,7 +716,8 @@ class AutoencoderKL(_ParamTree):
         self._register(table)
         self.vocoder = Generator(hifigan_config)
         self._enc = N.EngineHandle("ctta_vae_encoder_destroy")
-        self.ema_decoder = None
+        self.ema_decoder = self.ema_post_quant_conv = None     # set by AudioLCM_FTVAE (autoencoder.py:91-101 decodes through them)
+        self._ema_eng = N.EngineHandle("ctta_vae_destroy")
         # engine handles: [plain, differentiable] per stage -- separate handles, so that a plain decode (e.g. of the
         # target latent in MelLoss) never disturbs the tensors a pending differentiable decode saved for its backward
         self._eng = {"vae": [N.EngineHandle("ctta_vae_destroy") for _ in range(2)],
@@ -758,24 +807,84 @@ class AutoencoderKL(_ParamTree):
     def read_encoder_taps(self):
         return N.read_taps("ctta_vae_encoder", self._enc.h, self.device)
 
-    def _ensure_vae(self, B, T, F, grad=False):
+    _DECODER_KEYS = ("decoder.", "post_quant_conv.")
+
+    def _decoder_named(self):
+        return [(k, p) for k, p in self.named_parameters() if k.startswith(self._DECODER_KEYS)]
+
+    def decoder_trainable(self):
+        return any(p.requires_grad for _, p in self._decoder_named())
+
+    def train_decoder_(self, mode=True):
+        """Fine-tuning of the decoder (audio_consistency_model_ftvae.py:59-62): decoder.* and post_quant_conv.* require grad
+        and become the trainable PREFIX of the flat parameter / gradient buffers -- what `optim.FusedAdamW(vae)` and the EMA
+        kernel run over; encoder, quant_conv and vocoder stay frozen behind it."""
+        self._decoder_training = bool(mode)
+        frozen = tuple(k for k, _ in self.named_parameters() if not (mode and k.startswith(self._DECODER_KEYS)))
+        for k, p in self.named_parameters():
+            p.requires_grad_(bool(mode) and k.startswith(self._DECODER_KEYS))
+            if not p.requires_grad:
+                p.grad = None
+        if frozen != tuple(getattr(self, "_frozen_keys", ())):
+            self._frozen_keys = frozen
+            self._flat = self._flat_grad = None      # the flat order changed: the next flatten_parameters_() re-homes
+            self._trainable_cache = None
+        return self
+
+    def _make_config(self, B, T, F, sf, grad):
+        dd = self.ddconfig
+        c = N.VAEConfig()
+        c.z_channels, c.embed_dim, c.ch, c.out_ch = dd["z_channels"], self.embed_dim, dd["ch"], dd["out_ch"]
+        c.n_levels, c.num_res_blocks = len(dd["ch_mult"]), dd["num_res_blocks"]
+        for i, m in enumerate(dd["ch_mult"]):
+            c.ch_mult[i] = m
+        c.scale_factor = sf
+        c.max_batch, c.latent_h, c.latent_w = B, T, F
+        c.debug_taps = int(self.debug_taps)
+        c.enable_grad = int(grad)
+        return c
+
+    def _ensure_ema_vae(self, B, T, F):
+        """Plain handle over the EMA decoder / post_quant_conv holders (decode_first_stage(use_ema=True))."""
         L_ = N.lib()
         sf = float(self.scale_factor)
-        key = (T, F, sf, self.debug_taps, self.device)
-        named = [(k, p) for k, p in self.named_parameters() if k.startswith(("decoder.", "post_quant_conv."))]
-        ver = sum(p._version for k, p in named)
-        e = self._eng["vae"][int(grad)]
+        key = (T, F, sf, self.device)
+        named = [("decoder." + k, p) for k, p in self.ema_decoder.named_parameters()]
+        named += [("post_quant_conv." + k, p) for k, p in self.ema_post_quant_conv.named_parameters()]
+        ver = (sum(p._version for _, p in named) + 7 * getattr(self.ema_decoder, "_manual_version", 0)
+               + 7 * getattr(self.ema_post_quant_conv, "_manual_version", 0))
+        e = self._ema_eng
         if not e.fits((B,), key, ver):
-            dd = self.ddconfig
-            c = N.VAEConfig()
-            c.z_channels, c.embed_dim, c.ch, c.out_ch = dd["z_channels"], self.embed_dim, dd["ch"], dd["out_ch"]
-            c.n_levels, c.num_res_blocks = len(dd["ch_mult"]), dd["num_res_blocks"]
-            for i, m in enumerate(dd["ch_mult"]):
-                c.ch_mult[i] = m
-            c.scale_factor = sf
-            c.max_batch, c.latent_h, c.latent_w = B, T, F
-            c.debug_taps = int(self.debug_taps)
-            c.enable_grad = int(grad)
+            table, keep = N.param_table(named)
+            if e.h is not None and e.key == key and B <= e.capacity[0]:
+                with torch.cuda.device(self.device):
+                    N.check(L_.ctta_vae_load_weights(e.h, table, len(table), N.stream_ptr()))
+                e.version = ver
+            else:
+                c = self._make_config(B, T, F, sf, 0)
+                e.replace(lambda h: L_.ctta_vae_create(c, table, len(table), N.stream_ptr(), h), (B,), key, ver, self.device)
+        return e.h
+
+    def _ensure_vae(self, B, T, F, grad=False):
+        """grad: 0 plain, 1 differentiable in z (frozen decoder), 2 parameter gradients as well (trainable decoder)."""
+        L_ = N.lib()
+        sf = float(self.scale_factor)
+        key = (T, F, sf, self.debug_taps, self.device) + ((2,) if int(grad) == 2 else ())
+        named = self._decoder_named()
+        training = getattr(self, "_decoder_training", False)       # train_decoder_(): the weights move every step
+        # the fused optimizer updates a trainable decoder through raw pointers: mark_weights_changed() counts those
+        ver = sum(p._version for k, p in named) + (7 * getattr(self, "_manual_version", 0) if training else 0)
+        e = self._eng["vae"][int(bool(grad))]
+        if training and e.h is not None and e.key == key and B <= e.capacity[0] and e.version != ver:
+            # an optimizer step moved the weights: repack them in place instead of rebuilding the handle
+            table, keep = N.param_table(named)
+            with torch.cuda.device(self.device):
+                N.check(L_.ctta_vae_load_weights(e.h, table, len(table), N.stream_ptr()))
+            e.version = ver
+            if grad:
+                self._vae_pending = None
+        if not e.fits((B,), key, ver):
+            c = self._make_config(B, T, F, sf, grad)
             if grad:
                 self._vae_pending = None
             table, keep = N.param_table(named)
@@ -817,23 +926,37 @@ class AutoencoderKL(_ParamTree):
     def decode_first_stage(self, z, allow_grad=False, use_ema=False):
         """z (B,8,T,F) -> mel (B,1,4T,4F); z is divided by scale_factor first (autoencoder.py:105).
         allow_grad=True (CLAPLoss, tools/losses.py:294-296) returns a mel that back-propagates into z through the
-        frozen decoder (ctta_vae_decode_with_grad / ctta_vae_decode_backward)."""
+        frozen decoder (ctta_vae_decode_with_grad / ctta_vae_decode_backward).  When decoder.* / post_quant_conv.* require
+        grad (`train_decoder_()`, AudioLCM_FTVAE) the backward also accumulates their gradients, whether or not z requires
+        grad.  use_ema=True decodes through `ema_decoder` / `ema_post_quant_conv` when they are set (autoencoder.py:91-101)."""
         if use_ema and self.ema_decoder is None:
             print("VAE does not have EMA modules, but specified use_ema. Using the none-EMA modules instead.")
         if z.ndim != 4 or z.shape[1] != self.embed_dim:
             raise ValueError("z must be (batch, %d, T, F), got %s" % (self.embed_dim, tuple(z.shape)))
         if not z.is_cuda:
             raise N.CttaError("z is on %s: the HIP engine has no CPU path" % z.device)
-        if allow_grad and torch.is_grad_enabled() and z.requires_grad:
+        ema = use_ema and self.ema_decoder is not None
+        if allow_grad and torch.is_grad_enabled() and not ema and self.decoder_trainable():
+            if not all(p.requires_grad for _, p in self._decoder_named()):
+                raise N.CttaError("decode_first_stage(allow_grad=True): only some decoder parameters require grad -- "
+                                  "train_decoder_() makes decoder.* and post_quant_conv.* trainable together")
+            return _VaeDecodeWithParamGrad.apply(z, self._grad_anchor(), self)
+        if allow_grad and torch.is_grad_enabled() and z.requires_grad and not ema:
             return _VaeDecodeWithGrad.apply(z, self)
         B, _, T, F = z.shape
-        h = self._ensure_vae(B, T, F)
+        h = self._ensure_ema_vae(B, T, F) if ema else self._ensure_vae(B, T, F)
         zz = z.detach().to(device=self.device, dtype=torch.float32).contiguous()
         up = 2 ** (len(self.ddconfig["ch_mult"]) - 1)
         mel = torch.empty((B, self.ddconfig["out_ch"], T * up, F * up), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             N.check(N.lib().ctta_vae_decode(h, N.ptr(zz), B, N.ptr(mel), N.stream_ptr()))
         return mel
+
+    def _grad_anchor(self):
+        a = getattr(self, "_anchor", None)
+        if a is None or a.device != self.device:
+            a = self._anchor = torch.zeros((), device=self.device, requires_grad=True)
+        return a
 
     def vocode(self, mel):
         """mel (B,1,T,F) -> float waveform (B, L) before centring (Generator.forward)."""

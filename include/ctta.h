@@ -149,7 +149,9 @@ typedef struct {
   int max_batch, latent_h, latent_w;
   int debug_taps;
   int enable_grad;   /* 1: also build the data-gradient packs and size the arena for
-                        ctta_vae_decode_with_grad + ctta_vae_decode_backward (decoder only) */
+                        ctta_vae_decode_with_grad + ctta_vae_decode_backward (decoder only);
+                        2: the differentiable forward also keeps every convolution's input, and
+                        ctta_vae_decode_backward_params forms the parameter gradients too */
 } ctta_vae_config;
 
 typedef struct ctta_vae ctta_vae;
@@ -164,6 +166,14 @@ ctta_status ctta_vae_decode(ctta_vae* h, const float* z, int batch, float* mel, 
  * may be pending per handle; the backward consumes it.  Requires cfg.enable_grad. */
 ctta_status ctta_vae_decode_with_grad(ctta_vae* h, const float* z, int batch, float* mel, void* stream);
 ctta_status ctta_vae_decode_backward(ctta_vae* h, const float* grad_mel, int batch, float* grad_z, void* stream);
+/* Fine-tuning the decoder (AudioLCM_FTVAE): on a handle created with enable_grad = 2 the same backward also ACCUMULATES
+ * d loss / d parameter into `grads`, fp32 tensors with the state dict's names and shapes (`.grad` semantics, as
+ * ctta_unet_backward): every decoder.* and post_quant_conv.* key.  grad_z may be NULL.  Consumes the pending forward. */
+ctta_status ctta_vae_decode_backward_params(ctta_vae* h, const float* grad_mel, int batch, float* grad_z,
+                                            const ctta_tensor* grads, int n_grads, void* stream);
+/* a new state dict into an existing handle (forward packs, data-gradient packs, conv_out's fp32 taps), e.g. after an
+ * optimizer step on the decoder; a pending differentiable forward is dropped */
+ctta_status ctta_vae_load_weights(ctta_vae* h, const ctta_tensor* weights, int n_weights, void* stream);
 size_t ctta_vae_arena_bytes(const ctta_vae* h);
 int ctta_vae_num_taps(const ctta_vae* h);
 ctta_status ctta_vae_tap_info(const ctta_vae* h, int i, const char** name, int dims[4]);
@@ -863,7 +873,8 @@ ctta_status ctta_wgrad_scatter(const float* slabs, int n_slabs, int64_t slab_str
 /* Implicit weight-gradient GEMM (csrc/wgrad_gemm.hip): slabs[s][n][c * taps + t] = sum over split s's positions m of
  * dY^T[n][m] * X[pixel(m, tap t)][c] -- the product ctta_im2col_t + ctta_conv_gemm compute, without materialising im2col(X)^T.
  * dyt: bf16 [n][mp] (ctta_transpose_bf16 of dY, zero beyond m_valid); x: bf16 NHWC (batch, h, w) with x_ld elements per
- * pixel, c channels used; taps = 9: 3x3, stride 1, pad 1, columns in (cin, kh, kw) order; taps = 1: a linear layer
+ * pixel, c channels used; taps = 9: 3x3, stride 1, pad 1, a power-of-two width from 2 to 64 with h * w a multiple of 64,
+ * columns in (cin, kh, kw) order; taps = 1: a linear layer
  * (batch * h * w = rows).  bias_col >= 0 also writes the row sums of dY^T into column bias_col (bias gradient) and, for
  * sample_cols > 0, per-sample sums into the columns behind it (d temb).  mp % (64 * splits) == 0.
  * ctta_wgrad_implicit_supported: whether a geometry is inside the kernel's range (CTTA_WGRAD_IMPLICIT=0 turns it off). */
@@ -920,6 +931,19 @@ ctta_status ctta_lrelu_bwd(const void* g, const void* act, float slope, float al
 ctta_status ctta_conv_cout1_dgrad(const float* gy, const float* y_tanh, const float* w, int batch, int h, int wd,
                                   int kh, int kw, int pad_h, int pad_w, int c, const void* act, float slope,
                                   void* dx, void* stream);
+/* weight and bias gradient of the same 1-output-channel conv (at most 9 taps, c a multiple of 8 up to 2048):
+ * dw[c][tap] (+)= sum_m gy[m] * a[pixel(m, tap)][c] in the state dict's (1, c, kh, kw) order, db[0] (+)= sum_m gy[m]
+ * (db may be NULL); gy fp32 (batch, h, wd), a NHWC bf16 with c channels.  Per-workgroup partial rows in `scratch`
+ * (ctta_conv_cout1_wgrad_scratch_floats floats) are folded in a fixed order: no atomics, the same bits every run. */
+size_t ctta_conv_cout1_wgrad_scratch_floats(int batch, int h, int wd, int kh, int kw, int c);
+ctta_status ctta_conv_cout1_wgrad(const float* gy, const void* a, int batch, int h, int wd, int kh, int kw, int pad_h,
+                                  int pad_w, int c, float* dw, float* db, int accumulate, float* scratch, void* stream);
+/* post_quant_conv's parameter gradients (1x1 conv of z / scale, embed_dim zin <= 16 -> z_channels zout <= 32):
+ * dw[o][e] (+)= sum_pix dzin[pix][o] * (z[b][e][hw] * inv_scale), db[o] (+)= sum_pix dzin[pix][o] (db may be NULL);
+ * dzin NHWC bf16 with ld elements per pixel, z fp32 (batch, zin, hw).  Same fixed-order fold through `scratch`. */
+size_t ctta_post_quant_wgrad_scratch_floats(int batch, int hw, int zin, int zout);
+ctta_status ctta_post_quant_wgrad(const void* dzin, int ld, const float* z, float inv_scale, int batch, int zin, int zout,
+                                  int hw, float* dw, float* db, int accumulate, float* scratch, void* stream);
 /* GroupNorm(+SiLU) backward; stats [B][G][2] = (mean, rstd) from ctta_groupnorm_stats */
 size_t ctta_groupnorm_bwd_scratch_floats(int batch, int hw, int c, int groups);
 ctta_status ctta_groupnorm_stats(const void* x, int batch, int hw, int c, int groups, float eps, float* stats,
@@ -947,6 +971,8 @@ ctta_status ctta_add_slices(const void* a, int lda, const void* b, int ldb, void
                             int cols, void* stream);
 ctta_status ctta_zero_insert2(const void* dy, void* dz, int batch, int ho, int wo, int hz, int wz, int c,
                               void* stream);
+/* out (batch, 2h, 2w, c) = nearest x2 of x (batch, h, w, c), NHWC bf16, c a multiple of 8 (pool2_sum's forward twin) */
+ctta_status ctta_upsample2_nearest(const void* x, void* out, int batch, int h, int w, int c, void* stream);
 ctta_status ctta_pool2_sum(const void* dup, void* dx, int batch, int h, int w, int c, int accumulate,
                            void* stream);
 ctta_status ctta_softmax_bias_rows(const float* s, int lds, const float* bias, int rows_per_bias, void* p,
