@@ -110,6 +110,23 @@ class ConvPlanInfo(Structure):
         "plain_out", "wide_store", "wide_f32", "splitk_wide_f32", "epi_fast", "epi_fast_geglu", "epi_act")]
 
 
+class WgradGeom(Structure):
+    """ctta_wgrad_geom (include/ctta.h): all ints"""
+    _fields_ = [(n, c_int) for n in ("kh", "kw", "c", "batch", "hi", "wi", "upsample", "ho", "wo", "stride", "pad", "n", "nb",
+                                     "direct_ok", "run_async", "keeps_dy")]
+
+
+class WgradPolicy(Structure):
+    """ctta_wgrad_policy (include/ctta.h)"""
+    _fields_ = [(n, c_int) for n in ("implicit_target", "implicit_cap", "direct", "upsample_copy")]
+
+
+class WgradPlanInfo(Structure):
+    """ctta_wgrad_plan_info (include/ctta.h)"""
+    _fields_ = [(n, c_int) for n in ("route", "splits", "mp", "seg", "rows", "ld", "sums_apart", "upsample_copy")] + \
+               [(n, c_int64) for n in ("slabs", "q", "pt", "xu")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/ctta.h
 SIGNATURES = {
     "ctta_last_error": (c_char_p, []),
@@ -230,6 +247,8 @@ SIGNATURES = {
     "ctta_conv_gemm_num_variants": (c_int, []),
     "ctta_conv_gemm_variant_name": (c_char_p, [c_int]),
     "ctta_conv_plan": (c_int, [POINTER(ConvDesc), POINTER(ConvPlanEnv), POINTER(ConvPlanInfo)]),
+    "ctta_wgrad_plan": (c_int, [POINTER(WgradGeom), POINTER(WgradPolicy), POINTER(WgradPlanInfo)]),
+    "ctta_wgrad_engine_policy": (c_int, [c_int, POINTER(WgradPolicy)]),
     "ctta_attention_fullbias": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ctta_attention_fullbias_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,

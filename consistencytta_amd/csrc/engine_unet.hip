@@ -10,7 +10,7 @@
 // hidden width `inner = heads * (C // heads)` (255/510/1020 in the light config) is padded to a
 // multiple of 64 (`cp`), heads are padded from dh to 64 lanes (`hp = heads*64`) by zero rows /
 // columns placed at weight-packing time, so no kernel ever sees an odd width.
-#include "engine_common.h"
+#include "engine_backward.h"
 
 #include <stdlib.h>
 
@@ -145,24 +145,7 @@ struct ctta_unet : EngineBase {
     const bf16_t *enc_bf = nullptr, *xin = nullptr, *h_last = nullptr, *a_out = nullptr;
     const float *mask_bias = nullptr, *st_out = nullptr;
   } ts;
-  // Weight-gradient jobs (transposed im2col, the split-M GEMM, the scatter into the caller's gradient tensors) run on a
-  // SECOND stream: the data-gradient chain on the caller's stream is the critical path of the backward pass, its thin
-  // batch-9 launches leave CUs idle, and a layer's weight gradient depends on nothing that comes after it.  Each job
-  // owns one of NS scratch slots (dY^T is written by the main stream, everything else by the side stream); events
-  // order slot reuse and the joins at block boundaries.  Option "wgrad_stream" = 0 keeps everything on one stream.
-  struct WgradSide {
-    static constexpr int NS = 2;
-    hipStream_t stream = nullptr;
-    Arena slot[NS];
-    char* base = nullptr;
-    hipEvent_t ready[NS] = {nullptr, nullptr}, freed[NS] = {nullptr, nullptr}, joined = nullptr;
-    bool in_use[NS] = {false, false};
-    bool dirty = false;     // side stream has work the main stream has not joined yet
-    hipStream_t joined_on = nullptr;   // the main stream that last joined the side stream (see unet_backward_begin_impl)
-    bool was_capturing = false;        // whether the previous backward was recorded into a hipGraph capture
-    int next = 0;
-    bool enabled = false;
-  } wg;
+  WgradSide wg;   // the weight-gradient side stream and its scratch slots (engine_backward.h)
   struct BackwardState {   // between ctta_unet_backward_begin / _next calls
     bool active = false;
     bf16_t* dh = nullptr;
@@ -172,14 +155,13 @@ struct ctta_unet : EngineBase {
   } bw;
 };
 
-struct UCtx : RunCtx {
+struct UCtx : GradCtx {
   ctta_unet* U;
   bool reuse_text = false;
-  int B, L, Lp;
+  int L, Lp;
   const float* temb_all;
   const bf16_t* enc_bf;
   const float* mask_bias;
-  size_t gn_need = 0;
   bool train = false;
 };
 
@@ -855,15 +837,15 @@ extern "C" ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_
     }
   }
   if (st == CTTA_OK && cfg->enable_training) {   // scratch slots + stream + events of the weight-gradient side stream
-    ctta_unet::WgradSide& W = U->wg;
+    WgradSide& W = U->wg;
     size_t slot_bytes = 0;
     for (Arena& a : W.slot) if (a.peak > slot_bytes) slot_bytes = a.peak;
     slot_bytes = (slot_bytes + 4095) & ~(size_t)4095;
-    if (hipMalloc((void**)&W.base, slot_bytes * ctta_unet::WgradSide::NS + 4096) != hipSuccess) {
+    if (hipMalloc((void**)&W.base, slot_bytes * WgradSide::NS + 4096) != hipSuccess) {
       ctta_set_error("unet_create: hipMalloc of the weight-gradient scratch (%zu bytes) failed", slot_bytes * 2);
       st = CTTA_ERR_NOMEM;
     } else {
-      for (int i = 0; i < ctta_unet::WgradSide::NS; ++i) {
+      for (int i = 0; i < WgradSide::NS; ++i) {
         W.slot[i].dry = false; W.slot[i].base = W.base + (size_t)i * slot_bytes; W.slot[i].cap = slot_bytes; W.slot[i].reset();
         if (hipEventCreateWithFlags(&W.ready[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&W.freed[i], hipEventDisableTiming) != hipSuccess) st = CTTA_ERR_HIP;
@@ -905,7 +887,7 @@ extern "C" void ctta_unet_destroy(ctta_unet* U) {
   U->destroy_base();
   if (U->tc_base) (void)hipFree(U->tc_base);
   if (U->wg.stream) { (void)hipStreamSynchronize(U->wg.stream); (void)hipStreamDestroy(U->wg.stream); }
-  for (int i = 0; i < ctta_unet::WgradSide::NS; ++i) {
+  for (int i = 0; i < WgradSide::NS; ++i) {
     if (U->wg.ready[i]) (void)hipEventDestroy(U->wg.ready[i]);
     if (U->wg.freed[i]) (void)hipEventDestroy(U->wg.freed[i]);
   }

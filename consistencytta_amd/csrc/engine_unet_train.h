@@ -9,324 +9,35 @@
 //   * attention        : flash-style backward (ctta_attention_bwd): probabilities rebuilt from the forward's
 //                        log-sum-exp, dV = P^T dO, dP = dO V^T, dS = P (dP - D) scale, dQ = dS K, dK = dS^T Q,
 //   * norms / GEGLU / embedding MLP: the kernels in backward.hip.
-// Gradients are ACCUMULATED into the caller's fp32 tensors (same names / shapes as the state dict),
+// The leaf operators and the weight-gradient jobs (plan, launch, scatter, side stream) are engine_backward.h's, shared
+// with the VAE decoder; this file keeps the U-Net's blocks.  Gradients are ACCUMULATED into the caller's fp32 tensors (same names / shapes as the state dict),
 // i.e. `.grad` semantics; the caller zeroes them.  Activation gradients travel in bf16.
 
 struct BCtx : UCtx {
-  const GradTable* grads = nullptr;
   float* dtemb_all = nullptr;   // [B][temb_total] fp32, filled from the conv1 indicator rows
 };
 
-// One weight-gradient job: `w` is the context its launches use (scratch slot as arena; side stream when enabled).
-struct WgJob {
-  BCtx w;
-  int slot = 0;
-  bool async = false;
-};
-static ctta_status wg_begin(BCtx& c, WgJob* j) {
-  ctta_unet::WgradSide& W = c.U->wg;
-  j->slot = W.next;
-  W.next = (W.next + 1) % ctta_unet::WgradSide::NS;
-  // ("wgrad_stream" is read per job: switched off between two backward passes -- bench.py's profiled step, whose per-launch
-  // event brackets must not overlap -- the jobs run on the caller's stream in the same slots; the handle's arena policy,
-  // W.enabled, was fixed when it was created)
-  j->async = !c.dry && W.enabled && W.stream != nullptr && ctta_opt(CTTA_OPT_WGRAD_STREAM) != 0;
-  j->w = c;
-  j->w.arena = &W.slot[j->slot];
-  W.slot[j->slot].reset();
-  if (!j->async && !c.dry && W.in_use[j->slot]) {      // a side-stream job of an earlier pass may still own the slot
-    CTTA_CHECK_HIP(hipStreamWaitEvent(c.stream, W.freed[j->slot], 0));
-    W.in_use[j->slot] = false;
-  }
-  if (j->async) {
-    j->w.stream = W.stream;
-    // the slot's previous job must have drained before the main stream writes dY^T into it.  Jobs that read their operands
-    // in place (ctta_wgrad_tn) never touch the slot from the main stream, but they keep this wait: it is the back-pressure
-    // that lets the main stream run at most two jobs ahead of the side stream.  Without it the main stream races to the
-    // block's wg_join and idles there while the side stream drains alone: 92.4 vs 83.9 ms per pipelined step (round 4).
-    if (W.in_use[j->slot]) CTTA_CHECK_HIP(hipStreamWaitEvent(c.stream, W.freed[j->slot], 0));
-  }
-  return CTTA_OK;
-}
-// dY^T is in the slot (written on the main stream): hand over to the side stream
-static ctta_status wg_handoff(BCtx& c, WgJob& j) {
-  if (!j.async) return CTTA_OK;
-  ctta_unet::WgradSide& W = c.U->wg;
-  CTTA_CHECK_HIP(hipEventRecord(W.ready[j.slot], c.stream));
-  CTTA_CHECK_HIP(hipStreamWaitEvent(W.stream, W.ready[j.slot], 0));
-  return CTTA_OK;
-}
-static ctta_status wg_end(BCtx& c, WgJob& j) {
-  if (!j.async) return CTTA_OK;
-  ctta_unet::WgradSide& W = c.U->wg;
-  CTTA_CHECK_HIP(hipEventRecord(W.freed[j.slot], W.stream));
-  W.in_use[j.slot] = true;
-  W.dirty = true;
-  return CTTA_OK;
-}
-// the main stream waits for every weight-gradient job issued so far (block boundaries: the caller may start the
-// all-reduce of the block's gradients; before the embedding MLPs, which read d temb)
-static ctta_status wg_join(BCtx& c) {
-  ctta_unet::WgradSide& W = c.U->wg;
-  if (c.dry || !W.dirty) return CTTA_OK;
-  CTTA_CHECK_HIP(hipEventRecord(W.joined, W.stream));
-  CTTA_CHECK_HIP(hipStreamWaitEvent(c.stream, W.joined, 0));
-  W.dirty = false;
-  W.joined_on = c.stream;
-  return CTTA_OK;
-}
-
-static ctta_status grad_ptr(BCtx& c, const std::string& key, float** out) {
-  *out = nullptr;
-  if (c.dry) return CTTA_OK;
-  auto it = c.grads->map.find(key);
-  if (it == c.grads->map.end() || !it->second) {
-    ctta_set_error("unet_backward: no gradient tensor for '%s'", key.c_str());
-    return CTTA_ERR_MISSING_KEY;
-  }
-  *out = it->second;
-  return CTTA_OK;
-}
-
-// ------------------------------------------------------------------------------ weight gradients
-// slabs[s][n][r]: one row per OUTPUT channel n, r = (cin, kh, kw) index of the weight row (then the bias column,
-// then per-sample columns) -- the state dict's own row layout, so the scatter is a coalesced streaming add.
-struct Slabs { float* p = nullptr; int S = 1, R = 0, ld = 0, N = 0; };
-
-static int pick_splits(int64_t M, int R, int N) {
-  const int64_t tiles = (int64_t)((R + 127) / 128) * ((N + 127) / 128);
-  int S = 1;
-  while (tiles * S < 256 && S < 16 && M / (2 * S) >= 256) S *= 2;
-  return S;
-}
-
-// slabs[s][n][r] = sum_{m in segment s} dY[m][n] * Q[r][m];  x is the layer input in NHWC (a linear is the 1x1 case
-// with batch=1, hi=rows), dy [M][N] contiguous.  Rows of Q: (channel, tap) then the all-ones row, then `nb`
-// per-sample indicator rows.  Both GEMM operands are made m-contiguous (dY^T, im2col^T).
-static constexpr bool wgrad_inplace_on() { return true; }   // operands read where they lie (round 5); the copies route serves the geometries it does not
-// Linear layers: both operands are read WHERE THEY LIE by ctta_wgrad_tn on the side stream (no dY^T, no X^T copy).  dY stays
-// valid until the block's wg_join because the backward's arena releases nothing while the side stream is on
-// (unet_backward_begin_impl), and no dY is rewritten in place: the transformer's running token-stream gradient moves to a
-// new buffer at every LayerNorm backward (ctta_layernorm_bwd_add).
-static bool wgrad_inplace_ok(int taps, bool ups, int stride, int pad, int nb, int C, int N) {
-  return wgrad_inplace_on() && taps == 1 && !ups && stride == 1 && pad == 0 && nb == 0 && C % 8 == 0 && N % 8 == 0;
-}
-static constexpr bool wgrad_direct_on() { return true; }    // one-split layers add their tiles straight into the gradient tensors
-// `dm` (may be NULL): the layer's pack map when the caller allows the DIRECT form -- one split: the kernel adds its tiles
-// straight into the gradient tensors and `out->p` comes back NULL (nothing to scatter).
-static ctta_status wgrad_slabs(BCtx& cm, WgJob& job, const bf16_t* x, int C, int B, int hi, int wi, bool ups, int ho, int wo,
-                               int kh, int kw, int stride, int pad, const bf16_t* dy, int N, int nb, Slabs* out,
-                               const PackMap* dm = nullptr) {
-  BCtx& c = job.w;
-  Arena& A = *c.arena;
-  const int64_t M = (int64_t)B * ho * wo;
-  const int K = kh * kw * C;
-  const int R = K + 1 + nb;
-  const int ld = round_up(R, 4);
-  if (wgrad_inplace_ok(kh * kw, ups, stride, pad, nb, C, N) && M < (1LL << 31) - 4096) {
-    const int64_t tiles = (int64_t)((N + 127) / 128) * ((C + 127) / 128);
-    int S = 1;
-    // 128 x 128 tiles at two workgroups per CU; the level-0 / level-1 linears have 4..16 tiles over 9 216..36 864 rows: up to 64
-    // splits of >= 4 chunks (16 splits left a 256 x 256 layer with 64 workgroups walking 36 chunks each: 75 us per launch)
-    constexpr int tn_cap = 32, tn_target = 256;    // splits aimed at 256 workgroups, at most 32 (round 5)
-    // round 5: 256 workgroups / <= 32 splits instead of 512 / 64.  In a replayed step ONE kernel has the device to itself 79 % of
-    // the time (profiles/gaps_distill_pipelined_r05.txt): a launch that fills every CU pushes the other streams' kernels behind
-    // it, a narrower, longer one runs BESIDE them, and every halving of the splits halves the slab bytes.  Pipelined step
-    // 77.5 -> 76.2 ms at (256, 16..32); too narrow (64 workgroups, 8 splits) loses 4 ms (profiles/ab_r05_wgrad_splits.txt).
-    while (tiles * S < tn_target && S < tn_cap && M / (2 * S) >= 128) S *= 2;
-    const int mp = (int)round_up64(M, 64 * S);
-    if (S == 1 && dm && wgrad_direct_on() && dm->n <= N && (dm->bkey.empty() || dm->n_bias <= dm->n)) {
-      float *gw, *gb = nullptr;
-      CTTA_TRY(grad_ptr(c, dm->wkey, &gw));
-      if (!dm->bkey.empty()) CTTA_TRY(grad_ptr(c, dm->bkey, &gb));
-      if (!cm.dry) CTTA_TRY(wg_handoff(cm, job));
-      RUN(c, ctta_wgrad_tn_direct(dy, N, N, x, C, C, (int)M, mp, dm->k_ident > 0 ? dm->k_ident : K, dm->n, dm->ro,
-                                  dm->k_ident > 0 ? nullptr : dm->co, gw, dm->n_bias, dm->bidx, gb, c.stream));
-      out->p = nullptr; out->S = 1; out->R = R; out->ld = ld; out->N = N;
-      return CTTA_OK;
-    }
-    float* slabs = A.get<float>((size_t)S * N * ld); ALLOC_OR_FAIL(slabs);
-    if (!cm.dry) CTTA_TRY(wg_handoff(cm, job));
-    RUN(c, ctta_wgrad_tn(dy, N, N, x, C, C, (int)M, mp, S, K, slabs, (int64_t)N * ld, ld, c.stream));
-    out->p = slabs; out->S = S; out->R = R; out->ld = ld; out->N = N;
-    return CTTA_OK;
-  }
-  // the layer input read in place through LDS transpose reads (wgrad_gemm.hip) wherever the geometry allows: every linear
-  // and every 3x3 stride-1 convolution of the U-Net except conv_in (8 channels); the stride-2 / upsampling samplers and
-  // conv_in keep the im2col^T route below
-  // Linears (taps == 1) stay on the transposed-operand route by default: there the old Q is ONE transposed copy of X, not
-  // nine, and the implicit kernel's 1-tap tiling reads LDS once per MFMA (round-3 profile: 7.5 ms of side-stream kernel
-  // time per step against 3.9 ms for ALL gradient GEMMs before); CTTA_WGRAD_IMPLICIT_LINEAR=1 routes them through it too.
-  constexpr bool implicit_linear = false;
-  const int taps = kh * kw;
-  const bool implicit = !ups && stride == 1 && ho == hi && wo == wi &&
-                        ((taps == 9 && kh == 3 && pad == 1) || (taps == 1 && pad == 0 && implicit_linear)) &&
-                        M < (1LL << 31) - 4096 && ctta_wgrad_implicit_supported(taps, C, hi, wi, C, N) != 0;
-  int S = pick_splits(M, R, N);
-  if (implicit) {   // 64 x 64 (x 9 taps) / 64 x 256 tiles, two workgroups per CU
-    const int64_t tiles = (int64_t)((N + 63) / 64) * ((C + (taps == 9 ? 63 : 255)) / (taps == 9 ? 64 : 256));
-    S = 1;
-    constexpr int im_cap = 16, im_target = 256;    // (round 5: 256 workgroups, see the linears above)
-    while (tiles * S < im_target && S < im_cap && M / (2 * S) >= 256) S *= 2;
-  }
-  const int mp = (int)round_up64(M, 64 * S);
-  const int seg = mp / S;
-  bf16_t* q = nullptr;
-  if (!implicit) { q = A.get<bf16_t>((size_t)R * mp); ALLOC_OR_FAIL(q); }
-  // 3x3 convolutions: dY read in place too (no convolution's dY is rewritten by the main stream later) when the arena policy
-  // keeps it alive for the side stream
-  const bool conv_inplace = implicit && kh * kw == 9 && wgrad_inplace_on() && N % 8 == 0 && (nb == 0 || (ho * wo) % 64 == 0) &&
-                            (!job.async || c.U->wg.enabled);
-  if (conv_inplace && S == 1 && nb == 0 && dm && wgrad_direct_on() && dm->k_ident > 0 && dm->n <= N &&
-      (dm->bkey.empty() || dm->n_bias <= dm->n)) {
-    float *gw, *gb = nullptr;
-    CTTA_TRY(grad_ptr(c, dm->wkey, &gw));
-    if (!dm->bkey.empty()) CTTA_TRY(grad_ptr(c, dm->bkey, &gb));
-    if (!cm.dry) CTTA_TRY(wg_handoff(cm, job));
-    RUN(c, ctta_wgrad_implicit_direct(dy, N, N, mp, x, C, C, B, hi, wi, (int)M, dm->k_ident, dm->n, dm->ro, gw, dm->n_bias, dm->bidx, gb,
-                                      c.stream));
-    out->p = nullptr; out->S = 1; out->R = R; out->ld = ld; out->N = N;
-    return CTTA_OK;
-  }
-  if (conv_inplace) {
-    float* slabs = A.get<float>((size_t)S * N * ld); ALLOC_OR_FAIL(slabs);
-    if (!cm.dry) CTTA_TRY(wg_handoff(cm, job));
-    RUN(c, ctta_wgrad_implicit_inplace(dy, N, N, mp, x, C, C, B, hi, wi, 9, (int)M, S, K, nb, slabs, (int64_t)N * ld, ld, c.stream));
-    out->p = slabs; out->S = S; out->R = R; out->ld = ld; out->N = N;
-    return CTTA_OK;
-  }
-  bf16_t* pt = A.get<bf16_t>((size_t)N * mp); ALLOC_OR_FAIL(pt);
-  float* slabs = A.get<float>((size_t)S * N * ld); ALLOC_OR_FAIL(slabs);
-  RUN(cm, ctta_transpose_bf16(dy, 0, (int)M, N, N, 0, pt, 0, mp, 1, cm.stream));   // dY lives in the main stream's arena
-  if (!cm.dry) CTTA_TRY(wg_handoff(cm, job));
-  if (implicit) {
-    RUN(c, ctta_wgrad_implicit(pt, N, mp, x, C, C, B, hi, wi, taps, (int)M, S, K, nb, slabs, (int64_t)N * ld, ld, c.stream));
-    out->p = slabs; out->S = S; out->R = R; out->ld = ld; out->N = N;
-    return CTTA_OK;
-  }
-  RUN(c, ctta_im2col_t(x, C, B, hi, wi, ups ? 1 : 0, ho, wo, kh, kw, stride, pad, pad, 1, q, mp, nb, c.stream));
-  ctta_conv_desc d;
-  desc_init(&d);
-  d.x0 = pt; d.c0 = seg; d.x_stride = mp;
-  d.batch = 1; d.hi = N; d.wi = 1; d.ho = N; d.wo = 1;
-  // the GEMM produces the K weight columns only; the bias column K (and the nb per-sample columns behind it) are row sums
-  // of dY^T (ctta_wgrad_rowsum) -- as GEMM rows (the all-ones / indicator rows im2col_t still writes) they cost a whole
-  // extra tile column: N = 257 ran 3 column tiles of 128 for 2 tiles of work
-  const bool sums_apart = (nb == 0 || (ho * wo) % 8 == 0) && mp % (8 * S) == 0;
-  d.w = q; d.k_pad = mp; d.n = sums_apart ? K : R;
-  d.out = slabs; d.ldc = ld; d.out_f32 = 1;
-  d.groups = S; d.x_group_stride = seg; d.w_group_stride = seg; d.out_group_stride = (int64_t)N * ld;
-  if (job.async) ctta_conv_suppress_splitk(1);   // the handle's split-K slabs belong to the main stream's launches
-  const ctta_status gst = c.dry ? CTTA_OK : ctta_conv_gemm(&d, c.stream);
-  if (job.async) ctta_conv_suppress_splitk(0);
-  CTTA_TRY(gst);
-  if (sums_apart) RUN(c, ctta_wgrad_rowsum(pt, N, mp, (int)M, S, ho * wo, nb, slabs, (int64_t)N * ld, ld, K, c.stream));
-  out->p = slabs; out->S = S; out->R = R; out->ld = ld; out->N = N;
-  return CTTA_OK;
-}
-
-// slab rows [row0, row0 + m.n) -> weight / bias gradients of the layer described by `m`
-static ctta_status scatter_wgrad(BCtx& c, const Slabs& sl, int k_rows, const PackMap& m, int row0 = 0) {
-  const int64_t stride = (int64_t)sl.N * sl.ld;
-  const float* base = sl.p + (size_t)row0 * sl.ld;
-  float *gw, *gb = nullptr;
-  CTTA_TRY(grad_ptr(c, m.wkey, &gw));
-  if (!m.bkey.empty()) CTTA_TRY(grad_ptr(c, m.bkey, &gb));
-  // weight rows and (same launch) the bias column of the slabs
-  const bool bias_here = !m.bkey.empty() && m.n_bias <= m.n;
-  const int bcol = bias_here ? k_rows : -1;
-  if (m.k_ident > 0)
-    RUN(c, ctta_wgrad_scatter_rows_bias(base, sl.S, stride, sl.ld, m.k_ident, m.n, m.ro, nullptr, gw, bcol, m.n_bias, m.bidx, gb, 1,
-                                        c.stream));
-  else
-    RUN(c, ctta_wgrad_scatter_rows_bias(base, sl.S, stride, sl.ld, k_rows, m.n, m.ro, m.co, gw, bcol, m.n_bias, m.bidx, gb, 1,
-                                        c.stream));
-  if (!m.bkey.empty() && !bias_here)
-    RUN(c, ctta_col_scatter(base, sl.S, stride, sl.ld, k_rows, 1, m.n_bias, m.bidx, gb, 0, 1, c.stream));
-  return CTTA_OK;
-}
-
-static ctta_status conv_wgrad(BCtx& c, const ConvLayer& L, const PackMap& m, const bf16_t* x, int H, int W, bool ups,
-                              const bf16_t* dy, int temb_off = -1, const Resnet* temb_of = nullptr) {
-  WgJob job;
-  CTTA_TRY(wg_begin(c, &job));
-  BCtx& w = job.w;
-  const int hi = ups ? 2 * H : H, wi = ups ? 2 * W : W;
-  const int ho = (hi + 2 * L.pad - L.kh) / L.stride + 1, wo = (wi + 2 * L.pad - L.kw) / L.stride + 1;
-  const int nb = temb_off >= 0 ? c.B : 0;
-  Slabs sl;
-  CTTA_TRY(wgrad_slabs(c, job, x, L.cin_pad, c.B, hi, wi, ups, ho, wo, L.kh, L.kw, L.stride, L.pad, dy, L.p.n, nb, &sl,
-                       nb == 0 ? &m : nullptr));
+// conv1 of a resnet: the shared job with one indicator row per sample behind the bias row (nb = B), whose slab columns
+// are d temb; then time_emb_proj's own gradients
+static ctta_status conv1_wgrad(BCtx& c, const Resnet& R, const bf16_t* x, int H, int W, const bf16_t* dy) {
+  const ConvLayer& L = R.c1;
   const int K = L.kh * L.kw * L.cin_pad;
-  if (sl.p) CTTA_TRY(scatter_wgrad(w, sl, K, m));      // sl.p == NULL: the kernel added into the gradients itself
-  if (nb > 0)   // d temb[b][off + n] = sum over the sample's pixels of dY: columns K+1 .. K+B of the slab
-    RUN(w, ctta_col_scatter(sl.p, sl.S, (int64_t)sl.N * sl.ld, sl.ld, K + 1, nb, L.cout, nullptr,
-                            c.dtemb_all + temb_off, c.U->temb_total, 0, w.stream));
-  if (temb_of) {  // temb = time_emb_proj(SiLU(emb)): its weight / bias gradients need only this resnet's rows of d temb,
-                  // which the scatter above just produced (same stream, in order)
+  return layer_wgrad(c, wgrad_geom(c.B, L.kh, L.kw, L.cin_pad, H, W, false, L.stride, L.pad, L.p.n, c.B), R.t1.m, nullptr, x, dy,
+                     [&](GradCtx& w, const WgradDone& d) -> ctta_status {
+    // d temb[b][off + n] = sum over the sample's pixels of dY: columns K+1 .. K+B of the slab
+    RUN(w, ctta_col_scatter(d.slabs, d.pl.splits, (int64_t)d.g.n * d.pl.ld, d.pl.ld, K + 1, c.B, L.cout, nullptr,
+                            c.dtemb_all + R.temb_off, c.U->temb_total, 0, w.stream));
+    // temb = time_emb_proj(SiLU(emb)): its weight / bias gradients need only this resnet's rows of d temb, which the
+    // scatter above just produced (same stream, in order)
     float *gw, *gb;
-    CTTA_TRY(grad_ptr(w, temb_of->key + "time_emb_proj.weight", &gw));
-    CTTA_TRY(grad_ptr(w, temb_of->key + "time_emb_proj.bias", &gb));
-    RUN(w, ctta_linear_f32_bwd(c.U->ts.emb_silu, c.U->temb_w, c.dtemb_all + temb_of->temb_off, c.U->temb_total, nullptr,
-                               nullptr, gw, gb, c.B, temb_of->cout, c.U->temb_dim, 0, 1, w.stream));
-  }
-  if (!c.dry) CTTA_TRY(wg_end(c, job));
-  return CTTA_OK;
+    CTTA_TRY(grad_ptr(w, R.key + "time_emb_proj.weight", &gw));
+    CTTA_TRY(grad_ptr(w, R.key + "time_emb_proj.bias", &gb));
+    RUN(w, ctta_linear_f32_bwd(c.U->ts.emb_silu, c.U->temb_w, c.dtemb_all + R.temb_off, c.U->temb_total, nullptr, nullptr, gw, gb,
+                               c.B, R.cout, c.U->temb_dim, 0, 1, w.stream));
+    return CTTA_OK;
+  });
 }
 
-// linear y = x W^T (+b): x [rows][x_ld] (the first k_rows columns are the GEMM K), dy [rows][N]
-static ctta_status linear_wgrad(BCtx& c, const PackMap& m, const PackMap* m2, const bf16_t* x, int x_ld, int64_t rows,
-                                const bf16_t* dy, int N) {
-  WgJob job;
-  CTTA_TRY(wg_begin(c, &job));
-  Slabs sl;
-  CTTA_TRY(wgrad_slabs(c, job, x, x_ld, 1, (int)rows, 1, false, (int)rows, 1, 1, 1, 1, 0, dy, N, 0, &sl, m2 ? nullptr : &m));
-  if (sl.p) CTTA_TRY(scatter_wgrad(job.w, sl, x_ld, m, 0));
-  if (m2) CTTA_TRY(scatter_wgrad(job.w, sl, x_ld, *m2, m.n));   // fused [q | k]
-  if (!c.dry) CTTA_TRY(wg_end(c, job));
-  return CTTA_OK;
-}
-
-// ------------------------------------------------------------------------------ data gradients
-static ctta_status conv_dgrad(BCtx& c, const ConvLayer& D, const bf16_t* dy, int Hdy, int Wdy, bf16_t* dx, int Hout,
-                              int Wout, bool accumulate) {
-  ctta_conv_desc d;
-  desc_init(&d);
-  d.x0 = dy; d.c0 = D.cin_pad;
-  d.batch = c.B; d.hi = Hdy; d.wi = Wdy; d.ho = Hout; d.wo = Wout;
-  d.kh = D.kh; d.kw = D.kw; d.pad_h = d.pad_w = D.pad;
-  d.w = D.p.w; d.k_pad = D.p.k_pad; d.n = D.p.n;
-  d.out = dx; d.ldc = D.cout; d.accumulate = accumulate ? 1 : 0;
-  RUN(c, ctta_conv_gemm(&d, c.stream));
-  return CTTA_OK;
-}
-// dx [rows][ldx] (first n_out columns written) (+)= dy[:, :k] * W   with dy row stride dy_ld
-static ctta_status linear_dgrad(BCtx& c, const PackedW& D, const bf16_t* dy, int dy_k, int dy_ld, int64_t rows, bf16_t* dx,
-                                int n_out, int ldx, bool accumulate) {
-  ctta_conv_desc d;
-  desc_init(&d);
-  d.x0 = dy; d.c0 = dy_k; d.x_stride = dy_ld;
-  d.batch = 1; d.hi = (int)rows; d.wi = 1; d.ho = (int)rows; d.wo = 1;
-  d.w = D.w; d.k_pad = D.k_pad; d.n = n_out;
-  d.out = dx; d.ldc = ldx; d.accumulate = accumulate ? 1 : 0;
-  RUN(c, ctta_conv_gemm(&d, c.stream));
-  return CTTA_OK;
-}
-
-static ctta_status gn_backward(BCtx& c, const GNLayer& g, const bf16_t* x, const bf16_t* dy, bf16_t* dx, int hw,
-                               const float* stats, bool silu, bool accumulate_dx) {
-  float *dg, *db;
-  CTTA_TRY(grad_ptr(c, g.key + "weight", &dg));
-  CTTA_TRY(grad_ptr(c, g.key + "bias", &db));
-  const int groups = c.U->cfg.norm_num_groups;
-  if (!c.dry && ctta_groupnorm_bwd_scratch_floats(c.B, hw, g.c, groups) > c.gn_scratch_floats) {
-    ctta_set_error("groupnorm backward scratch too small");
-    return CTTA_ERR_INVALID;
-  }
-  RUN(c, ctta_groupnorm_bwd(x, dy, dx, c.B, hw, g.c, groups, stats, g.gamma, g.beta, silu ? 1 : 0, accumulate_dx ? 1 : 0,
-                            dg, db, 1, c.gn_scratch, c.stream));
-  return CTTA_OK;
-}
 // dx = dx_add + dL/dx (dx_add NULL: plain).  The transformer's running token-stream gradient moves to a NEW buffer at every
 // LayerNorm: the previous one stays as it was for the weight-gradient jobs that read it in place on the side stream.
 static ctta_status ln_backward(BCtx& c, const LNLayer& l, const bf16_t* x, const bf16_t* dy, const bf16_t* dx_add, bf16_t* dx,
@@ -360,7 +71,7 @@ static ctta_status bwd_resnet(BCtx& c, Resnet& R, const bf16_t* dout, bf16_t** d
   CTTA_TRY(conv_wgrad(c, R.c2, R.t2.m, S.a2, H, W, false, dout));
   bf16_t* dt1 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(dt1);
   CTTA_TRY(gn_backward(c, R.n2, S.t1, da2, dt1, H * W, S.st2, true, false));
-  CTTA_TRY(conv_wgrad(c, R.c1, R.t1.m, S.a, H, W, false, dt1, R.temb_off, &R));   // + time_emb_proj weight / bias gradients
+  CTTA_TRY(conv1_wgrad(c, R, S.a, H, W, dt1));   // + d temb and time_emb_proj's weight / bias gradients
   bf16_t* da = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(da);
   CTTA_TRY(conv_dgrad(c, R.t1.d, dt1, H, W, da, H, W, false));
   if (R.has_sc) {
@@ -381,7 +92,6 @@ static ctta_status bwd_resnet(BCtx& c, Resnet& R, const bf16_t* dout, bf16_t** d
 // out zero).  Flash-style (no score matrix).  Round 5: Q, K, dO are read where they lie and V as the forward keeps it
 // (transposed) -- ctta_attention_bwd_inplace takes the operands it needs in the other orientation out of its own LDS tiles
 // through transposing reads; the four whole-tensor transposes per call of rounds 1-4 (CTTA_ATTN_BWD_INPLACE=0) are gone.
-static constexpr bool attn_bwd_inplace_on() { return true; }
 static ctta_status bwd_attention(BCtx& c, int heads, int dh, const bf16_t* q, int ldq, const bf16_t* k, int ldk, int krows,
                                  const bf16_t* vt, int vt_ld, const float* bias, int nq, int nk, const bf16_t* out,
                                  const bf16_t* dO, int hp, const float* lse, bf16_t* dq, int lddq, bf16_t* dk, int lddk,
@@ -390,7 +100,7 @@ static ctta_status bwd_attention(BCtx& c, int heads, int dh, const bf16_t* q, in
   const int B = c.B;
   const int nk64 = round_up(nk, 64), nq64 = round_up(nq, 64);
   const size_t mk = A.mark();
-  const bool inplace = attn_bwd_inplace_on() && vt_ld % 8 == 0 && vt_ld >= nk;
+  const bool inplace = vt_ld % 8 == 0 && vt_ld >= nk;
   bf16_t *vn = nullptr, *kt = nullptr, *qt = nullptr, *dot = nullptr;
   if (!inplace) {
     vn = A.get<bf16_t>((size_t)B * vt_ld * hp); ALLOC_OR_FAIL(vn);      // V   [B][vt_ld][hp]
@@ -543,7 +253,9 @@ static void bctx_init(BCtx& c, ctta_unet* U, bool dry, const GradTable* grads, h
   const ctta_unet::TrainSaved& S = U->ts;
   U->bind(c, stream, dry, false, 0);   // the backward emits no fused GroupNorm statistics
   c.U = U; c.B = S.B; c.L = S.L; c.Lp = S.Lp; c.train = true;
-  c.enc_bf = S.enc_bf; c.mask_bias = S.mask_bias; c.grads = grads;
+  c.enc_bf = S.enc_bf; c.mask_bias = S.mask_bias;
+  c.grads = grads; c.params = true; c.who = "unet_backward"; c.norm_groups = U->cfg.norm_num_groups;
+  c.side = &U->wg; c.policy = &kWgradPolicyUnet;
   c.dtemb_all = U->bw.dtemb_all;
 }
 
@@ -556,7 +268,7 @@ static ctta_status unet_backward_begin_impl(ctta_unet* U, bool dry, const bf16_t
   // With the weight-gradient side stream on, a linear layer's dY is read in place by the SIDE stream some time after the main
   // stream has moved on: nothing the backward allocates is released before the next training forward resets the arena
   // (the dry run sizes it under the same policy; a few GB more at batch 9 -- HBM is what this part has).
-  A.no_release = U->wg.enabled && wgrad_inplace_on();
+  A.no_release = U->wg.enabled;
   const int B = S.B, H = cfg.height, W = cfg.width, c0 = cfg.block_out_channels[0];
   U->bw.dtemb_all = A.get<float>((size_t)B * U->temb_total); ALLOC_OR_FAIL(U->bw.dtemb_all);
   U->bw.dskip.assign((size_t)S.n_skips, nullptr);
@@ -570,12 +282,12 @@ static ctta_status unet_backward_begin_impl(ctta_unet* U, bool dry, const bf16_t
     // capture that is a dependency on uncaptured work (hipErrorStreamCaptureIsolation).
     // The same when this call is the first one inside / after a capture: events recorded on the other side of that
     // boundary must not be waited on (torch's graph context synchronises the device when it opens and closes).
-    ctta_unet::WgradSide& Wg = U->wg;
+    WgradSide& Wg = U->wg;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &cs);
     const bool capturing = cs == hipStreamCaptureStatusActive;
     if (!Wg.dirty && (Wg.joined_on == stream || capturing != Wg.was_capturing))
-      for (int i = 0; i < ctta_unet::WgradSide::NS; ++i) Wg.in_use[i] = false;
+      for (int i = 0; i < WgradSide::NS; ++i) Wg.in_use[i] = false;
     Wg.was_capturing = capturing;
   }
   // ---- conv_out, conv_norm_out
@@ -607,9 +319,9 @@ static ctta_status unet_backward_next_impl(ctta_unet* U, bool dry, const GradTab
     // begin / every earlier next ended with wg_join on this stream: no scratch slot is in use any more, and the `freed`
     // events of the previous call must not be waited on when this call is captured into its OWN hipGraph (segmented
     // capture of the data-parallel step: they were recorded in another capture).
-    ctta_unet::WgradSide& Wg = U->wg;
+    WgradSide& Wg = U->wg;
     if (!Wg.dirty && Wg.joined_on == stream)
-      for (int i = 0; i < ctta_unet::WgradSide::NS; ++i) Wg.in_use[i] = false;
+      for (int i = 0; i < WgradSide::NS; ++i) Wg.in_use[i] = false;
   }
   const int B = S.B;
   bf16_t* dh = U->bw.dh;

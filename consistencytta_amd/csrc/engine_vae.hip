@@ -5,7 +5,7 @@
 //   HiFi-GAN: Generator.forward hifigan/models.py:101-117, ResBlock.forward :56-63.
 // Layout: NHWC bf16 for the decoder; (B, L, C) bf16 for the vocoder (the decoder's
 // (B,1,T,F) mel IS the vocoder's (B, T, F=num_mels) input, autoencoder.py:109).
-#include "engine_common.h"
+#include "engine_backward.h"
 
 #include <stdlib.h>
 
@@ -117,12 +117,8 @@ struct ctta_vae : EngineBase {
   } sv;
 };
 
-struct VCtx : RunCtx {
-  int B;
-  size_t gn_need = 0;
-  bool grad = false;   // differentiable forward: keep what vae_backward_impl reads
-  bool pgrad = false;  // forward: also keep the convolutions' inputs; backward: also form the parameter gradients
-  const GradTable* grads = nullptr;   // backward with pgrad: the caller's gradient tensors
+struct VCtx : GradCtx {   // params -- forward: also keep the convolutions' inputs; backward: also form the parameter gradients
+  bool grad = false;     // differentiable forward: keep what vae_backward_impl reads
 };
 
 static const int kVaeGroups = 32;    // Normalize(): GroupNorm(32, eps=1e-6)  modules.py:38-41
@@ -166,7 +162,7 @@ static ctta_status run_vae_res(VCtx& c, VaeRes& R, const bf16_t* x, int H, int W
     R.sv.x = x; R.sv.t1 = t1; R.sv.st1 = st1; R.sv.st2 = st2; R.sv.H = H; R.sv.W = W;
   }
   bf16_t *a = nullptr, *a2 = nullptr;
-  if (c.pgrad) {  // the normalised activations are the convolutions' inputs: the weight gradients read them
+  if (c.params) {  // the normalised activations are the convolutions' inputs: the weight gradients read them
     a = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(a);
     a2 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(a2);
     R.sv.a = a; R.sv.a2 = a2;
@@ -226,7 +222,7 @@ static ctta_status run_vae_attn(VCtx& c, VaeAttn* V, const bf16_t* x, int H, int
     V->sv.x = x; V->sv.q = q; V->sv.k = k; V->sv.vt = vt; V->sv.p = p; V->sv.st = st; V->sv.H = H; V->sv.W = W;
   }
   bf16_t *g = nullptr, *o = nullptr;
-  if (c.pgrad) {
+  if (c.params) {
     g = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(g);
     o = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(o);
     V->sv.g = g; V->sv.o = o;
@@ -301,15 +297,15 @@ static ctta_status vae_forward_impl(ctta_vae* V, bool dry, const float* z, int B
   V->bind(c, stream, dry, cfg.debug_taps != 0, 32);
   c.B = B;
   c.grad = grad;
-  c.pgrad = grad && cfg.enable_grad == 2;
+  c.params = grad && cfg.enable_grad == 2;
   V->sv.B = grad ? B : 0;
-  V->sv.params = c.pgrad;
+  V->sv.params = c.params;
   Arena& A = V->arena;
   A.reset();
   int H = cfg.latent_h, W = cfg.latent_w;
   const int cpad = 32;
   bf16_t* zin = A.get<bf16_t>((size_t)B * H * W * cpad); ALLOC_OR_FAIL(zin);
-  if (c.pgrad) {   // post_quant_conv's weight gradient reads the latent after the caller's tensor may be gone
+  if (c.params) {   // post_quant_conv's weight gradient reads the latent after the caller's tensor may be gone
     const size_t nz = (size_t)B * cfg.embed_dim * H * W;
     float* zc = A.get<float>(nz); ALLOC_OR_FAIL(zc);
     if (!dry) CTTA_CHECK_HIP(hipMemcpyAsync(zc, z, nz * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -383,111 +379,16 @@ __global__ void post_quant_bwd_kernel(const bf16_t* __restrict__ dzin, int ld, c
   }
 }
 
-static ctta_status vconv_dgrad(VCtx& c, const ConvLayer& D, const bf16_t* dy, int H, int W, bf16_t* dx, bool accumulate) {
-  ctta_conv_desc d;
-  desc_init(&d);
-  d.x0 = dy; d.c0 = D.cin_pad;
-  d.batch = c.B; d.hi = H; d.wi = W; d.ho = H; d.wo = W;
-  d.kh = D.kh; d.kw = D.kw; d.pad_h = d.pad_w = D.pad;
-  d.w = D.p.w; d.k_pad = D.p.k_pad; d.n = D.p.n;
-  d.out = dx; d.ldc = D.cout; d.accumulate = accumulate ? 1 : 0;
-  RUN(c, ctta_conv_gemm(&d, c.stream));
-  return CTTA_OK;
-}
-
-static ctta_status vgrad_ptr(VCtx& c, const std::string& key, float** out) {
-  *out = nullptr;
-  if (c.dry) return CTTA_OK;
-  auto it = c.grads->map.find(key);
-  if (it == c.grads->map.end() || !it->second) {
-    ctta_set_error("vae_decode_backward_params: no gradient tensor for '%s'", key.c_str());
-    return CTTA_ERR_MISSING_KEY;
-  }
-  *out = it->second;
-  return CTTA_OK;
-}
-
-static ctta_status vgn_bwd(VCtx& c, const GNLayer& g, const bf16_t* x, const bf16_t* dy, bf16_t* dx, int hw,
-                           const float* stats, bool silu, bool accumulate_dx) {
-  const size_t need = ctta_groupnorm_bwd_scratch_floats(c.B, hw, g.c, kVaeGroups);
-  if (need > c.gn_need) c.gn_need = need;
-  if (!c.dry && need > c.gn_scratch_floats) { ctta_set_error("groupnorm backward scratch too small"); return CTTA_ERR_INVALID; }
-  float *dgamma = nullptr, *dbeta = nullptr;
-  if (c.pgrad) {
-    CTTA_TRY(vgrad_ptr(c, g.key + "weight", &dgamma));
-    CTTA_TRY(vgrad_ptr(c, g.key + "bias", &dbeta));
-  }
-  RUN(c, ctta_groupnorm_bwd(x, dy, dx, c.B, hw, g.c, kVaeGroups, stats, g.gamma, g.beta, silu ? 1 : 0,
-                            accumulate_dx ? 1 : 0, dgamma, dbeta, dgamma ? 1 : 0, c.gn_scratch, c.stream));
-  return CTTA_OK;
-}
-
-// dW / db of one convolution, ACCUMULATED into the caller's tensors (`.grad` semantics, as ctta_unet_backward).  x: the
-// layer's input, NHWC with L.cin_pad channels (ups: at half the output extent); dy [B * H * W][cout] at the OUTPUT extent.
-//   1x1                      : both operands read where they lie (ctta_wgrad_tn);
-//   3x3, widths 2 .. 64      : the implicit kernel with dY in place (ctta_wgrad_implicit_inplace; width 64 is the last
-//                              level's 1024 x 64, where most of the backward's pixels are);
-//   the x2 upsampling convs  : the same kernel over a materialised x2 copy of the input (ctta_upsample2_nearest);
-//   anything else            : im2col^T (which knows `upsample`) + conv_gemm + row sums.
-// Split-M slabs in the arena, folded by ctta_wgrad_scatter_rows_bias in slab order: no atomics.  The implicit launches aim
-// at 512 workgroups (two per CU) with up to 128 position splits: at 1024 x 64 and batch 4 a 128 -> 128 layer has four 64 x 64
-// tiles, and 0.53 / 0.17 / 0.14 ms were measured at 16 / 64 / 128 splits against 0.51 ms for the copies route
-// (profiles/vae_wgrad.txt; past two workgroups per CU the time rises again).
+// dW / db of one decoder convolution (1x1 or 3x3, stride 1; ups: x at half the output extent), on the caller's stream out of
+// the arena, under kWgradPolicyVae.  Every pack map here comes from make_conv with a bias: identity column map (k_ident > 0)
+// and n_bias = cout <= n, so scatter_wgrad folds the slabs' bias column in its one launch.
 static ctta_status vconv_wgrad(VCtx& c, const ConvLayer& L, const PackMap& m, const bf16_t* x, int H, int W, bool ups,
                                const bf16_t* dy) {
-  Arena& A = *c.arena;
-  const size_t mk = A.mark();
   const int C = L.cin_pad, N = L.cout, taps = L.kh * L.kw, K = taps * C;
   const int64_t M = (int64_t)c.B * H * W;
   CTTA_REQUIRE(M < (1LL << 31) - 4096 && N % 8 == 0 && C % 8 == 0 && m.n <= N && m.k_ident > 0 && m.k_ident <= K && (taps == 1 || taps == 9),
                "vae weight gradient: unsupported layer '%s'", m.wkey.c_str());
-  float *gw, *gb;
-  CTTA_TRY(vgrad_ptr(c, m.wkey, &gw));
-  CTTA_TRY(vgrad_ptr(c, m.bkey, &gb));
-  const int ld = round_up(K + 1, 4);
-  const bool implicit = taps == 9 && ctta_wgrad_implicit_supported(9, C, H, W, C, N) != 0;
-  int S = 1;
-  if (taps == 1) {          // 128 x 128 tiles, 256 workgroups
-    const int64_t tiles = (int64_t)((N + 127) / 128) * ((C + 127) / 128);
-    while (tiles * S < 256 && S < 32 && M / (2 * S) >= 128) S *= 2;
-  } else if (implicit) {    // 64 x 64 (x 9 taps) tiles
-    const int64_t tiles = (int64_t)((N + 63) / 64) * ((C + 63) / 64);
-    while (tiles * S < 512 && S < 128 && M / (2 * S) >= 256) S *= 2;
-  } else {
-    const int64_t tiles = (int64_t)((K + 127) / 128) * ((N + 127) / 128);
-    while (tiles * S < 256 && S < 16 && M / (2 * S) >= 256) S *= 2;
-  }
-  const int mp = (int)round_up64(M, 64 * S);
-  float* slabs = A.get<float>((size_t)S * N * ld); ALLOC_OR_FAIL(slabs);
-  if (taps == 1) {
-    RUN(c, ctta_wgrad_tn(dy, N, N, x, C, C, (int)M, mp, S, K, slabs, (int64_t)N * ld, ld, c.stream));
-  } else if (implicit) {
-    if (ups) {
-      bf16_t* xu = A.get<bf16_t>((size_t)M * C); ALLOC_OR_FAIL(xu);
-      RUN(c, ctta_upsample2_nearest(x, xu, c.B, H / 2, W / 2, C, c.stream));
-      x = xu;
-    }
-    RUN(c, ctta_wgrad_implicit_inplace(dy, N, N, mp, x, C, C, c.B, H, W, 9, (int)M, S, K, 0, slabs, (int64_t)N * ld, ld, c.stream));
-  } else {
-    const int seg = mp / S;
-    bf16_t* q = A.get<bf16_t>((size_t)(K + 1) * mp); ALLOC_OR_FAIL(q);
-    bf16_t* pt = A.get<bf16_t>((size_t)N * mp); ALLOC_OR_FAIL(pt);
-    RUN(c, ctta_transpose_bf16(dy, 0, (int)M, N, N, 0, pt, 0, mp, 1, c.stream));
-    RUN(c, ctta_im2col_t(x, C, c.B, H, W, ups ? 1 : 0, H, W, L.kh, L.kw, 1, L.pad, L.pad, 1, q, mp, 0, c.stream));
-    ctta_conv_desc d;
-    desc_init(&d);
-    d.x0 = pt; d.c0 = seg; d.x_stride = mp;
-    d.batch = 1; d.hi = N; d.wi = 1; d.ho = N; d.wo = 1;
-    d.w = q; d.k_pad = mp; d.n = K;
-    d.out = slabs; d.ldc = ld; d.out_f32 = 1;
-    d.groups = S; d.x_group_stride = seg; d.w_group_stride = seg; d.out_group_stride = (int64_t)N * ld;
-    RUN(c, ctta_conv_gemm(&d, c.stream));
-    RUN(c, ctta_wgrad_rowsum(pt, N, mp, (int)M, S, H * W, 0, slabs, (int64_t)N * ld, ld, K, c.stream));
-  }
-  RUN(c, ctta_wgrad_scatter_rows_bias(slabs, S, (int64_t)N * ld, ld, m.k_ident, m.n, m.ro, nullptr, gw, K, m.n_bias, m.bidx, gb, 1,
-                                      c.stream));
-  A.release(mk);
-  return CTTA_OK;
+  return conv_wgrad(c, L, m, x, ups ? H / 2 : H, ups ? W / 2 : W, ups, dy);
 }
 
 // out = conv2(silu(gn2(t1))) + shortcut(x), t1 = conv1(silu(gn1(x)))   (ResnetBlock.forward modules.py:155-175)
@@ -498,15 +399,15 @@ static ctta_status bwd_vae_res(VCtx& c, const VaeRes& R, const bf16_t* dout, bf1
   bf16_t* dx = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(dx);
   const size_t mk = A.mark();
   bf16_t* da2 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(da2);
-  CTTA_TRY(vconv_dgrad(c, R.d2, dout, H, W, da2, false));
+  CTTA_TRY(conv_dgrad(c, R.d2, dout, H, W, da2, H, W, false));
   bf16_t* dt1 = A.get<bf16_t>(M * R.cout); ALLOC_OR_FAIL(dt1);
-  CTTA_TRY(vgn_bwd(c, R.n2, R.sv.t1, da2, dt1, H * W, R.sv.st2, true, false));
+  CTTA_TRY(gn_backward(c, R.n2, R.sv.t1, da2, dt1, H * W, R.sv.st2, true, false));
   bf16_t* da = A.get<bf16_t>(M * R.cin); ALLOC_OR_FAIL(da);
-  CTTA_TRY(vconv_dgrad(c, R.d1, dt1, H, W, da, false));
-  if (R.has_sc) CTTA_TRY(vconv_dgrad(c, R.dsc, dout, H, W, dx, false));
+  CTTA_TRY(conv_dgrad(c, R.d1, dt1, H, W, da, H, W, false));
+  if (R.has_sc) CTTA_TRY(conv_dgrad(c, R.dsc, dout, H, W, dx, H, W, false));
   else RUN(c, ctta_add_slices(dout, R.cout, nullptr, 0, dx, R.cin, (int64_t)M, R.cin, c.stream));
-  CTTA_TRY(vgn_bwd(c, R.n1, R.sv.x, da, dx, H * W, R.sv.st1, true, true));
-  if (c.pgrad) {
+  CTTA_TRY(gn_backward(c, R.n1, R.sv.x, da, dx, H * W, R.sv.st1, true, true));
+  if (c.params) {
     CTTA_TRY(vconv_wgrad(c, R.c2, R.m2, R.sv.a2, H, W, false, dout));
     CTTA_TRY(vconv_wgrad(c, R.c1, R.m1, R.sv.a, H, W, false, dt1));
     if (R.has_sc) CTTA_TRY(vconv_wgrad(c, R.sc, R.msc, R.sv.x, H, W, false, dout));
@@ -541,7 +442,7 @@ static ctta_status bwd_vae_attn(VCtx& c, const VaeAttn& T, const bf16_t* dout, b
   bf16_t* dx = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(dx);
   const size_t mk = A.mark();
   bf16_t* dO = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(dO);
-  CTTA_TRY(vconv_dgrad(c, T.dproj, dout, H, W, dO, false));
+  CTTA_TRY(conv_dgrad(c, T.dproj, dout, H, W, dO, H, W, false));
   bf16_t* vn = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(vn);     // V   [B][N][C]
   bf16_t* kt = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(kt);     // K^T [B][C][N]
   bf16_t* qt = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(qt);     // Q^T
@@ -564,12 +465,12 @@ static ctta_status bwd_vae_attn(VCtx& c, const VaeAttn& T, const bf16_t* dout, b
   RUN(c, ctta_transpose_bf16(T.sv.p, NN, N, N, N, 0, tt, NN, N, B, c.stream));
   CTTA_TRY(bgemm(c, tt, NN, dOt, NC, N, C, N, dv, NC, C, false));
   bf16_t* dg = A.get<bf16_t>(M * C); ALLOC_OR_FAIL(dg);
-  CTTA_TRY(vconv_dgrad(c, T.dq, dq, H, W, dg, false));
-  CTTA_TRY(vconv_dgrad(c, T.dk, dk, H, W, dg, true));
-  CTTA_TRY(vconv_dgrad(c, T.dv, dv, H, W, dg, true));
+  CTTA_TRY(conv_dgrad(c, T.dq, dq, H, W, dg, H, W, false));
+  CTTA_TRY(conv_dgrad(c, T.dk, dk, H, W, dg, H, W, true));
+  CTTA_TRY(conv_dgrad(c, T.dv, dv, H, W, dg, H, W, true));
   RUN(c, ctta_add_slices(dout, C, nullptr, 0, dx, C, (int64_t)M, C, c.stream));
-  CTTA_TRY(vgn_bwd(c, T.norm, T.sv.x, dg, dx, N, T.sv.st, false, true));
-  if (c.pgrad) {   // four linear weight gradients: X = the attention output (proj_out) or the normalised input (q, k, v)
+  CTTA_TRY(gn_backward(c, T.norm, T.sv.x, dg, dx, N, T.sv.st, false, true));
+  if (c.params) {   // four linear weight gradients: X = the attention output (proj_out) or the normalised input (q, k, v)
     CTTA_TRY(vconv_wgrad(c, T.proj, T.mproj, T.sv.o, H, W, false, dout));
     CTTA_TRY(vconv_wgrad(c, T.q, T.mq, T.sv.g, H, W, false, dq));
     CTTA_TRY(vconv_wgrad(c, T.k, T.mk, T.sv.g, H, W, false, dk));
@@ -586,7 +487,8 @@ static ctta_status vae_backward_impl(ctta_vae* V, bool dry, const float* gmel, i
   VCtx c;
   V->bind(c, stream, dry, false, 32);
   c.B = B;
-  c.pgrad = pgrad; c.grads = grads;
+  c.params = pgrad; c.grads = grads; c.who = "vae_decode_backward_params"; c.norm_groups = kVaeGroups;
+  c.policy = &kWgradPolicyVae;
   Arena& A = V->arena;   // continues above the differentiable forward's saved tensors
   const int up = 1 << (cfg.n_levels - 1);
   int H = cfg.latent_h * up, W = cfg.latent_w * up, ch = V->c_last;
@@ -594,19 +496,19 @@ static ctta_status vae_backward_impl(ctta_vae* V, bool dry, const float* gmel, i
   RUN(c, ctta_conv_cout1_dgrad(gmel, nullptr, V->out_w, B, H, W, 3, 3, 1, 1, ch, nullptr, 0.f, da, stream));
   if (pgrad) {
     float *gw, *gb;
-    CTTA_TRY(vgrad_ptr(c, "decoder.conv_out.weight", &gw));
-    CTTA_TRY(vgrad_ptr(c, "decoder.conv_out.bias", &gb));
+    CTTA_TRY(grad_ptr(c, "decoder.conv_out.weight", &gw));
+    CTTA_TRY(grad_ptr(c, "decoder.conv_out.bias", &gb));
     const size_t mk = A.mark();
     float* part = A.get<float>(ctta_conv_cout1_wgrad_scratch_floats(B, H, W, 3, 3, ch)); ALLOC_OR_FAIL(part);
     RUN(c, ctta_conv_cout1_wgrad(gmel, V->sv.a_out, B, H, W, 3, 3, 1, 1, ch, gw, gb, 1, part, stream));
     A.release(mk);
   }
   bf16_t* dh = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(dh);
-  CTTA_TRY(vgn_bwd(c, V->norm_out, V->sv.h_last, da, dh, H * W, V->sv.st_out, true, false));
+  CTTA_TRY(gn_backward(c, V->norm_out, V->sv.h_last, da, dh, H * W, V->sv.st_out, true, false));
   for (int lvl = 0; lvl < cfg.n_levels; ++lvl) {
     if (lvl != 0) {   // u = conv(nearest x2 (h)): data gradient at the fine resolution, then the 2x2 sum
       bf16_t* du = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(du);
-      CTTA_TRY(vconv_dgrad(c, V->d_upsample[lvl], dh, H, W, du, false));
+      CTTA_TRY(conv_dgrad(c, V->d_upsample[lvl], dh, H, W, du, H, W, false));
       if (pgrad) CTTA_TRY(vconv_wgrad(c, V->upsample[lvl], V->m_upsample[lvl], V->sv.up_in[lvl], H, W, true, dh));
       H /= 2; W /= 2;
       bf16_t* dl = A.get<bf16_t>((size_t)B * H * W * ch); ALLOC_OR_FAIL(dl);
@@ -623,12 +525,12 @@ static ctta_status vae_backward_impl(ctta_vae* V, bool dry, const float* gmel, i
   CTTA_TRY(bwd_vae_res(c, V->mid1, dh, &dh));
   const int zc = V->d_conv_in.cout;
   bf16_t* dzin = A.get<bf16_t>((size_t)B * H * W * zc); ALLOC_OR_FAIL(dzin);
-  CTTA_TRY(vconv_dgrad(c, V->d_conv_in, dh, H, W, dzin, false));
+  CTTA_TRY(conv_dgrad(c, V->d_conv_in, dh, H, W, dzin, H, W, false));
   if (pgrad) {
     CTTA_TRY(vconv_wgrad(c, V->conv_in, V->m_conv_in, V->sv.zin, H, W, false, dh));
     float *gw, *gb;
-    CTTA_TRY(vgrad_ptr(c, "post_quant_conv.weight", &gw));
-    CTTA_TRY(vgrad_ptr(c, "post_quant_conv.bias", &gb));
+    CTTA_TRY(grad_ptr(c, "post_quant_conv.weight", &gw));
+    CTTA_TRY(grad_ptr(c, "post_quant_conv.bias", &gb));
     float* part = A.get<float>(ctta_post_quant_wgrad_scratch_floats(B, H * W, cfg.embed_dim, cfg.z_channels)); ALLOC_OR_FAIL(part);
     RUN(c, ctta_post_quant_wgrad(dzin, zc, V->sv.z, 1.0f / cfg.scale_factor, B, cfg.embed_dim, cfg.z_channels, H * W, gw, gb, 1, part,
                                  stream));

@@ -494,6 +494,36 @@ typedef struct {
   int plain_out, wide_store, wide_f32, splitk_wide_f32, epi_fast, epi_fast_geglu, epi_act;   /* epilogue flags */
 } ctta_conv_plan_info;
 ctta_status ctta_conv_plan(const ctta_conv_desc* d, const ctta_conv_plan_env* env, ctta_conv_plan_info* out);
+/* The PLAN of one layer's weight gradient in the engines' backward passes, without a device: which of the weight-gradient
+ * kernels below runs for a layer geometry, over how many position splits, and what scratch it takes.  ctta_unet_backward* and
+ * ctta_vae_decode_backward_params launch from the same plan, each under its own policy (ctta_wgrad_engine_policy). */
+typedef struct {
+  int kh, kw, c;                      /* taps and input channels (the row stride of x) */
+  int batch, hi, wi, upsample;        /* input extent AFTER the x2 nearest upsampling, if any */
+  int ho, wo, stride, pad;            /* output extent: dY is [batch * ho * wo][n] */
+  int n;                              /* output channels */
+  int nb;                             /* per-sample columns behind the bias column (time-embedding gradient); 0: none */
+  int direct_ok;                      /* the layer's pack map lets a one-split kernel add into the gradient tensors itself */
+  int run_async, keeps_dy;            /* the job runs on a side stream; the handle keeps dY alive until that stream is joined */
+} ctta_wgrad_geom;
+typedef struct {
+  int implicit_target, implicit_cap;  /* implicit kernel: workgroups a launch aims for, most splits */
+  int direct;                         /* one-split launches add straight into the gradient tensors */
+  int upsample_copy;                  /* x2-upsampling convolutions: implicit kernel over an x2 copy (0: im2col^T) */
+} ctta_wgrad_policy;
+enum { CTTA_WGRAD_TN = 0, CTTA_WGRAD_TN_DIRECT, CTTA_WGRAD_IMPLICIT_INPLACE, CTTA_WGRAD_IMPLICIT_DIRECT,
+       CTTA_WGRAD_IMPLICIT_DYT, CTTA_WGRAD_IM2COL_T };
+typedef struct {
+  int route;                          /* CTTA_WGRAD_* */
+  int splits, mp, seg;                /* position splits, padded positions (multiple of 64 * splits), positions per split */
+  int rows, ld;                       /* slab columns in use (k + 1 + nb) and the slab row stride */
+  int sums_apart;                     /* im2col^T: bias / per-sample columns from ctta_wgrad_rowsum, not from the GEMM */
+  int upsample_copy;                  /* the kernel reads an x2 copy of the input (xu) */
+  int64_t slabs, q, pt, xu;           /* elements of the scratch buffers: fp32 slabs, im2col^T, dY^T, x2 copy (0: not made) */
+} ctta_wgrad_plan_info;
+ctta_status ctta_wgrad_plan(const ctta_wgrad_geom* g, const ctta_wgrad_policy* policy, ctta_wgrad_plan_info* out);
+/* engine 0: the U-Net's policy, 1: the VAE decoder's */
+ctta_status ctta_wgrad_engine_policy(int engine, ctta_wgrad_policy* out);
 
 /* Fused HiFi-GAN ResBlock unit (hifigan/models.py:56-63) for C = 32 / 64 / 128 / 256 channels, odd k <= 11 (C = 512: k = 3 / 7 / 11):
  *   out = act( alpha * ( [old out +] x + conv2(leaky_relu(conv1(leaky_relu(x, slope)) + b1, slope)) + b2 ) )
