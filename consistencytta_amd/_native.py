@@ -127,6 +127,12 @@ class WgradPlanInfo(Structure):
                [(n, c_int64) for n in ("slabs", "q", "pt", "xu")]
 
 
+class ResampleClip(Structure):
+    """ctta_resample_clip (include/ctta.h)"""
+    _fields_ = [("x_off", c_int64), ("y_off", c_int64), ("n_in", c_int32), ("n_out", c_int32), ("time_increment", c_double),
+                ("scale", c_double), ("gain", c_float), ("index_step", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/ctta.h
 SIGNATURES = {
     "ctta_last_error": (c_char_p, []),
@@ -300,6 +306,8 @@ SIGNATURES = {
     "ctta_ssim_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int, c_double, c_int, c_void_p,
                                c_void_p, c_void_p]),
     "ctta_psnr_mse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "ctta_resample_sinc": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "ctta_wave_prepare": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ctta_reschain_supported": (c_int, [c_int, c_int, c_void_p]),
     "ctta_reschain_conv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_float, c_void_p, c_int, c_float, c_float, c_void_p]),

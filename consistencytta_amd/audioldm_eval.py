@@ -40,7 +40,10 @@ arithmetic on its features.
 The four paired keys are computed only by a helper built with `paired_metrics=True`; otherwise they are reported as NaN, exactly
 like a key the reference leaves out (eval.py:297-299 `out.get(key, nan)`), and so is frechet_audio_distance when no
 `vggish_model` is given.  Resampling of files whose rate is not an integer multiple of the target (`resampy`,
-load_mel.py:25-28, fad.py:33-34) is refused loudly.
+load_mel.py:25-28, fad.py:33-34) is refused loudly by default; `EvaluationHelper(resample="kaiser_best")` and the loaders'
+`resampler="kaiser_best"` send such files through `audio.resample`, the HIP restatement of resampy 0.4.2's kaiser_best
+(built from the published definition; the package is not part of the reference tree), and the CLAP scores' 48 kHz
+conversion with them.  Integer multiples keep the reference's striding either way.
 """
 import os
 from collections import OrderedDict
@@ -503,9 +506,24 @@ def pad_short_audio(audio, min_samples=32000):
     return audio
 
 
-def read_centered_wav(audio_file, target_sr):
+def _check_resampler(resampler):
+    if resampler not in (None, "kaiser_best"):
+        raise ValueError("resampler must be None (refuse such files) or 'kaiser_best', got %r" % (resampler,))
+
+
+def _resample_host(audio, orig_sr, target_sr, resampler):
+    """resampy.resample(audio, orig_sr, target_sr, filter=resampler) (load_mel.py:25-28, fad.py:33-34) for one host clip:
+    up to the current GPU as fp32, `audio.resample`, back as float64."""
+    from .audio import resample
+    x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).cuda()
+    return resample([x], orig_sr, target_sr, filter=resampler)[0].cpu().numpy().astype(np.float64)
+
+
+def read_centered_wav(audio_file, target_sr, resampler=None):
     """datasets/load_mel.py:17-29 with scipy.io.wavfile in place of soundfile: first channel mix-down, integer-ratio
-    decimation by plain striding (as the reference does), mean removed; PCM widths scaled to [-1, 1) like soundfile."""
+    decimation by plain striding (as the reference does), mean removed; PCM widths scaled to [-1, 1) like soundfile.
+    Any other rate is refused unless `resampler="kaiser_best"`, which resamples it as the reference does, on the GPU."""
+    _check_resampler(resampler)
     from scipy.io import wavfile
     orig_sr, audio = wavfile.read(audio_file)
     if audio.dtype.kind == "i":
@@ -518,17 +536,22 @@ def read_centered_wav(audio_file, target_sr):
         audio = audio.mean(axis=1)                           # librosa.to_mono
     if orig_sr != target_sr and orig_sr % target_sr == 0:
         audio = audio[..., ::(orig_sr // target_sr)]
+    elif orig_sr != target_sr and resampler is not None:
+        audio = _resample_host(audio, orig_sr, target_sr, resampler)
     elif orig_sr != target_sr:
         raise N.CttaError("%s: %d Hz is not an integer multiple of %d Hz; the reference resamples such files with resampy "
-                          "(kaiser_best), which is not rebuilt -- resample the directory first" % (audio_file, orig_sr, target_sr))
+                          "(kaiser_best) -- pass resampler='kaiser_best' or resample the directory first"
+                          % (audio_file, orig_sr, target_sr))
     return audio - audio.mean()
 
 
-def load_audio_task(fname, target_sr=16000, target_length=1000):
+def load_audio_task(fname, target_sr=16000, target_length=1000, resampler=None):
     """metrics/fad.py:22-36, the Frechet Audio Distance's own loader, with scipy.io.wavfile in place of soundfile: samples as
     int16 / 32768, MEAN over the channels, integer-ratio decimation by plain striding, cut to `target_length` centiseconds;
-    the mean is NOT removed (unlike `read_centered_wav`: the two loaders differ in the reference too).  float64 array."""
+    the mean is NOT removed (unlike `read_centered_wav`: the two loaders differ in the reference too).  float64 array.
+    `resampler`: as in `read_centered_wav`."""
     from scipy.io import wavfile
+    _check_resampler(resampler)
     orig_sr, audio = wavfile.read(fname)
     if audio.dtype != np.int16:
         raise N.CttaError("%s holds %s samples: only 16-bit PCM is read (the reference converts other widths with soundfile's "
@@ -538,16 +561,21 @@ def load_audio_task(fname, target_sr=16000, target_length=1000):
         audio = np.mean(audio, axis=1)
     if orig_sr % target_sr == 0:
         audio = audio[::(orig_sr // target_sr)]
+    elif resampler is not None:
+        audio = _resample_host(audio, orig_sr, target_sr, resampler)
     else:
         raise N.CttaError("%s: %d Hz is not an integer multiple of %d Hz; the reference resamples such files with resampy "
-                          "(kaiser_best), which is not rebuilt -- resample the directory first" % (fname, orig_sr, target_sr))
+                          "(kaiser_best) -- pass resampler='kaiser_best' or resample the directory first"
+                          % (fname, orig_sr, target_sr))
     return audio[:int(target_length * target_sr / 100)]
 
 
 class WaveDataset:
     """datasets/load_mel.py:123-151: sorted .wav files of a directory -> (waveform (1, n) fp32, base name)."""
 
-    def __init__(self, datadir, sr=16000, target_length=1000, limit_num=None):
+    def __init__(self, datadir, sr=16000, target_length=1000, limit_num=None, resampler=None):
+        _check_resampler(resampler)
+        self.resampler = resampler
         self.datalist = sorted(os.path.join(datadir, x) for x in os.listdir(datadir))
         self.datalist = [x for x in self.datalist if x.endswith(".wav")]
         if limit_num is not None:
@@ -559,7 +587,7 @@ class WaveDataset:
 
     def __getitem__(self, index):
         filename = self.datalist[index]
-        audio = torch.from_numpy(read_centered_wav(filename, self.sr)).float()[None]
+        audio = torch.from_numpy(read_centered_wav(filename, self.sr, self.resampler)).float()[None]
         audio = pad_short_audio(audio[..., :int(self.sr * self.target_length / 100)], min_samples=32000)
         if audio.shape[-1] < 1:
             raise ValueError("empty file %s" % filename)
@@ -597,7 +625,10 @@ class MelPairedDataset:
     `augment` are accepted and unused, as in the reference.  `EvaluationHelper` reads the audio through `audio_pair` and
     batches the mels itself instead of indexing pair by pair."""
 
-    def __init__(self, datadir1, datadir2, _stft, sr=16000, fbin_mean=None, fbin_std=None, augment=False, limit_num=None):
+    def __init__(self, datadir1, datadir2, _stft, sr=16000, fbin_mean=None, fbin_std=None, augment=False, limit_num=None,
+                 resampler=None):
+        _check_resampler(resampler)
+        self.resampler = resampler
         lists = []
         for d in (datadir1, datadir2):
             files = [x for x in sorted(os.path.join(d, x) for x in os.listdir(d)) if x.endswith(".wav")]
@@ -614,13 +645,14 @@ class MelPairedDataset:
         return os.path.basename(self.datalist1[index])
 
     def audio_pair(self, index):
-        return read_centered_wav(self.datalist1[index], self.sr), read_centered_wav(self.datalist2[index], self.sr)
+        return (read_centered_wav(self.datalist1[index], self.sr, self.resampler),
+                read_centered_wav(self.datalist2[index], self.sr, self.resampler))
 
     def get_mel_from_wav(self, audio):
         return _normalised_mels(self._stft, [np.asarray(audio, dtype=np.float64)])[0].cpu().numpy(), None
 
     def get_mel_from_file(self, audio_file):
-        audio = read_centered_wav(audio_file, self.sr)
+        audio = read_centered_wav(audio_file, self.sr, self.resampler)
         melspec, energy = self.get_mel_from_wav(audio) if self._stft is not None else (None, None)
         return melspec, energy, audio
 
@@ -697,7 +729,9 @@ class EvaluationHelper:
     `ssim_stft`, `psnr` and `ssim` (eval.py:137-179) on the HIP path; the default leaves them NaN.  Their version-dependent
     choices: `stft_pad_mode` -- the centre padding of the LSD's |librosa.stft|, "reflect" (librosa 0.9, which `ssr_eval` was
     released against) or "constant" (librosa 0.10); `stft_ssim_data_range` -- the data range of `ssim_stft`, 2.0 being what
-    skimage infers for a float image."""
+    skimage infers for a float image.  `resample="kaiser_best"`: files whose rate is not an integer multiple of the target
+    are resampled as the reference does (resampy's kaiser_best on the HIP path, `audio.resample`) instead of refused, and
+    the CLAP scores' 16 -> 48 kHz conversion uses it too; None keeps both as they were."""
 
     KEYS = ["frechet_distance", "frechet_audio_distance", "lsd", "psnr", "kullback_leibler_divergence_sigmoid",
             "kullback_leibler_divergence_softmax", "ssim", "ssim_stft", "inception_score_mean", "inception_score_std",
@@ -708,7 +742,7 @@ class EvaluationHelper:
     SSIM_WIN = 7            # skimage's default win_size
 
     def __init__(self, sampling_rate, device, backbone="cnn14", mel_model=None, clap_model=None, vggish_model=None,
-                 paired_metrics=False, stft_pad_mode="reflect", stft_ssim_data_range=2.0):
+                 paired_metrics=False, stft_pad_mode="reflect", stft_ssim_data_range=2.0, resample=None):
         self.device, self.backbone, self.sampling_rate = device, backbone, sampling_rate
         if sampling_rate not in (16000, 32000):
             raise ValueError("We only support the evaluation on 16kHz and 32kHz sampling rates.")
@@ -721,6 +755,8 @@ class EvaluationHelper:
         self.clap_model = clap_model
         self.vggish_model = vggish_model.eval() if vggish_model is not None else None
         self.paired_metrics = bool(paired_metrics)
+        _check_resampler(resample)
+        self.resample = resample
         self.stft_pad_mode, self.stft_ssim_data_range = stft_pad_mode, float(stft_ssim_data_range)
         if self.stft_ssim_data_range <= 0.0:
             raise ValueError("stft_ssim_data_range must be positive, got %r" % (stft_ssim_data_range,))
@@ -770,7 +806,9 @@ class EvaluationHelper:
 
         def length(path):                                    # samples `load_audio_task` will return, from the header alone
             sr, data = wavfile.read(path, mmap=True)
-            return min(-(-data.shape[0] // (sr // 16000)), limit) if sr % 16000 == 0 else limit
+            if sr % 16000 == 0:
+                return min(-(-data.shape[0] // (sr // 16000)), limit)
+            return min(int(data.shape[0] * 16000 / sr), limit) if self.resample is not None else limit   # else: it raises
 
         lengths = [length(p) for p in paths]
         order = sorted((i for i in range(len(paths)) if m.n_examples(lengths[i]) > 0), key=lambda i: lengths[i])
@@ -781,7 +819,8 @@ class EvaluationHelper:
                 j = i
                 while j < len(order) and j - i < 32 and lengths[order[j]] == lengths[order[i]]:
                     j += 1
-                waves = [torch.from_numpy(load_audio_task(paths[order[k]], 16000, target_length)).float() for k in range(i, j)]
+                waves = [torch.from_numpy(load_audio_task(paths[order[k]], 16000, target_length, self.resample)).float()
+                         for k in range(i, j)]
                 out = m(torch.stack(waves).to(self.device)).cpu()
                 rows = out.shape[0] // (j - i)
                 for k in range(i, j):
@@ -817,8 +856,8 @@ class EvaluationHelper:
             raise ValueError("Generated and groundtruth diretories have different files.\nGenerated: %s;\nGround truth: %s."
                              % (gen_files, gt_files))
         sr = self.sampling_rate
-        gen = WaveDataset(generate_files_path, sr, limit_num=limit_num, target_length=target_length)
-        gt = WaveDataset(groundtruth_path, sr, limit_num=limit_num, target_length=1000)
+        gen = WaveDataset(generate_files_path, sr, limit_num=limit_num, target_length=target_length, resampler=self.resample)
+        gt = WaveDataset(groundtruth_path, sr, limit_num=limit_num, target_length=1000, resampler=self.resample)
         featuresdict_2 = self.get_featuresdict(gt[i] for i in range(len(gt)))
         featuresdict_1 = self.get_featuresdict(gen[i] for i in range(len(gen)))
         out = {}
@@ -835,7 +874,8 @@ class EvaluationHelper:
                                  subset_size=len(gen) if subset_size is None else subset_size, coef0=1, rng_seed=2020))
         out.update(calculate_fid(featuresdict_1, featuresdict_2, feat_layer_name="2048"))
         if self.paired_metrics:                              # eval.py:222-228,238-240,259-263
-            paired = MelPairedDataset(generate_files_path, groundtruth_path, self.mel_stft(), sr, limit_num=limit_num)
+            paired = MelPairedDataset(generate_files_path, groundtruth_path, self.mel_stft(), sr, limit_num=limit_num,
+                                      resampler=self.resample)
             out.update(self.calculate_lsd(paired, same_name=same_name))
             out.update(self.calculate_psnr_ssim(paired, same_name=same_name))
         return {key: round(out.get(key, float("nan")), 4) for key in self.KEYS}
@@ -953,10 +993,19 @@ class EvaluationHelper:
     def _clap_wave(self, w, seconds=10.0):
         """What `T2APairedDataset` hands the CLAP tower (tools/t2a_dataset.py:111-125 -> tools/torch_tools.py:54-75): the clip at
         48 kHz, mean removed, scaled to peak 0.5, cut / zero-padded to the segment length, scaled again.  The reference
-        resamples with `resampy` (kaiser_best), which is not in its tree; here the Kaiser-windowed sinc resampler of the CLAP loss
-        (tools/losses.py:299-303 = `clap.Resampler`) does it -- a stated deviation of the filter, not of the pipeline."""
+        resamples with `resampy` (kaiser_best), which is not in its tree.  A helper built with `resample="kaiser_best"` does
+        the same on the HIP path (`audio.resample` + `data.wave_prepare`, fp64 normalisation rounded once like the reference's
+        `.float()`); by default the Kaiser-windowed sinc resampler of the CLAP loss (tools/losses.py:299-303 =
+        `clap.Resampler`) does it and the normalisation is fp32 -- a stated deviation of the filter, not of the pipeline."""
         from .clap import Resampler
         w = w.reshape(1, -1).float().to(self.device)
+        if self.resample is not None:
+            from .audio import resample
+            from .data import wave_prepare
+            w = w[0].contiguous()
+            if self.sampling_rate != 48000:
+                w = resample([w], self.sampling_rate, 48000, filter=self.resample)[0]
+            return wave_prepare(w, [0], [w.shape[0]], int(round(seconds * 48000)))
         if self.sampling_rate != 48000:
             if getattr(self, "_to48k", None) is None:
                 self._to48k = Resampler(orig_freq=self.sampling_rate, new_freq=48000)

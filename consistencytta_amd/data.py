@@ -8,7 +8,11 @@ same seed selects the same pairs.  Everything numerical runs on the GPU (csrc/mi
 tensor inputs are copied to the current CUDA device and the results copied back.
 
 The HIP stage cannot run in DataLoader worker processes, so the loader keeps augment=False and the training loop calls
-`collate(captions, waveforms)` on the raw batch before `wav_to_fbank`."""
+`collate(captions, waveforms)` on the raw batch before `wav_to_fbank`.
+
+The file loader in front of it, `tools/torch_tools.py:54-75` (`read_wav_file`): `read_wav_batch` / `read_wav_file` read the
+files on the host and resample (resampy's kaiser_best, `audio.resample`) and normalise (`wave_prepare`) the ragged batch on
+the GPU (csrc/resample_sinc.hip), for the same reason in the same place: the loader hands out paths, the loop reads them."""
 import itertools
 import random
 
@@ -16,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import audio
 
 _MODES = {"A_weighting": 0, "RMSE": 1}
 
@@ -295,3 +300,103 @@ def collate(captions, waveforms, augment=True, out=None, groups=1, pairs=None):
     if n:
         mixer(dev).mix(out[:B], _pair_tensor(pairs, dev), out, dst_row0=B, groups=groups)
     return (captions + mixed_captions if mixed_captions is not None else None), out
+
+
+# ------------------------------------------------------------------------------------------------------- the file loader
+def read_mono(filename):
+    """`sf.read` + `librosa.to_mono` of torch_tools.py:56-58 through scipy.io.wavfile (there is no soundfile here), with the
+    rules of `audioldm_eval.read_centered_wav`: integer PCM scaled to [-1, 1), unsigned 8-bit re-centred, the mean over the
+    channels.  Returns (float64 samples, rate)."""
+    from scipy.io import wavfile
+    sr, wav = wavfile.read(filename)
+    if wav.dtype.kind == "i":
+        wav = wav.astype(np.float64) / float(2 ** (8 * wav.dtype.itemsize - 1))
+    elif wav.dtype.kind == "u":
+        wav = (wav.astype(np.float64) - 128.0) / 128.0
+    else:
+        wav = wav.astype(np.float64)
+    if wav.ndim > 1:
+        wav = wav.mean(axis=1)
+    return wav, int(sr)
+
+
+def wave_prepare(flat, offsets, lengths, segment_length, clips=None):
+    """torch_tools.py:69-73 for clips lying in one fp32 CUDA buffer (`flat[offsets[b]:offsets[b] + lengths[b]]`): mean
+    removal, peak 0.5, cut / zero-pad to `segment_length`, peak 0.5 again -> (B, segment_length) fp32.  One launch
+    (ctta_wave_prepare).  `clips`: a device table of ctta_resample_clip already holding these offsets (y_off) and lengths
+    (n_out), tensor or raw pointer; built and uploaded here when None."""
+    if not flat.is_cuda:
+        raise N.CttaError("waveforms on %s: the HIP loader has no CPU path (call .cuda())" % flat.device)
+    if flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("the sample buffer must be a contiguous fp32 tensor")
+    B, seg = len(lengths), int(segment_length)
+    if min(lengths) < 1:
+        raise ValueError("an empty clip has no mean")
+    if clips is None:
+        clips = audio.clip_table([N.ResampleClip(y_off=int(o), n_out=int(n)) for o, n in zip(offsets, lengths)], flat.device)
+    out = torch.empty(B, seg, dtype=torch.float32, device=flat.device)
+    ws = torch.empty(3 * B, dtype=torch.float64, device=flat.device)
+    cp = N.ptr(clips) if torch.is_tensor(clips) else N.c_void_p(clips)
+    with torch.cuda.device(flat.device):
+        N.check(N.lib().ctta_wave_prepare(N.ptr(flat), cp, B, seg, N.ptr(out), N.ptr(ws), N.stream_ptr()))
+    return out
+
+
+def read_wav_batch(filenames, segment_length, target_sr=16000, device=None, filter="kaiser_best"):
+    """`read_wav_file` (tools/torch_tools.py:54-75) for a list of files of any lengths and rates -> (B, segment_length) fp32 on
+    the GPU: what `collate` and `audio.wav_to_fbank` take.  `target_sr` may be a list of rates, resampled to in turn as the
+    reference does (t2a_dataset.py:111-122 passes [16000, 48000]).
+
+    The files are read and mixed down on the host; everything numerical runs on the GPU.  All samples and every stage's
+    clip descriptors go up in ONE copy into an arena that also holds the stages' outputs; then one ctta_resample_sinc
+    per rate stage (clips already at the stage's rate stay where they are) and one ctta_wave_prepare.  The resampler
+    follows the published definition of resampy 0.4.2 (see `audio.resample`); the package itself is not installed where
+    this was built, so parity with it is by definition, not by comparison."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise N.CttaError("the file loader's arithmetic runs on the GPU only (got device %s)" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    stages = [int(r) for r in target_sr] if isinstance(target_sr, (list, tuple)) else [int(target_sr)]
+    _, num_table = audio.resampy_filter(filter)
+    waves, rates = zip(*(read_mono(f) for f in filenames))
+    B = len(waves)
+    # arena, in fp32 elements: [the clip tables of every stage and of the normalisation | samples | stage outputs]
+    size = N.ctypes.sizeof(N.ResampleClip)
+    offs, lens, cur = [0] * B, [len(w) for w in waves], list(rates)
+    end = 0
+    for b in range(B):
+        offs[b], end = end, end + lens[b]
+    n_samples = end
+    tables = []                                               # (first descriptor, count, max_n_out) per launched stage
+    descs = []
+    for sr in stages:
+        first = len(descs)
+        for b in range(B):
+            if cur[b] != sr:
+                d = audio.resample_clip(lens[b], cur[b], sr, num_table, offs[b], end)
+                descs.append(d)
+                offs[b], lens[b], cur[b], end = end, d.n_out, sr, end + d.n_out
+        if len(descs) > first:
+            tables.append((first, len(descs) - first, max(d.n_out for d in descs[first:])))
+    final = len(descs)
+    descs += [N.ResampleClip(y_off=offs[b], n_out=lens[b]) for b in range(B)]
+    head = -(-len(descs) * size // 16) * 16                   # the samples start 16-byte aligned
+    shift = head // 4
+    for d in descs:
+        d.x_off += shift
+        d.y_off += shift
+    host = np.empty(head + 4 * n_samples, dtype=np.uint8)
+    host[:len(descs) * size] = np.frombuffer(bytes().join(bytes(d) for d in descs), dtype=np.uint8)
+    host[head:].view(np.float32)[:] = np.concatenate(waves)
+    arena = torch.empty(head + 4 * end, dtype=torch.uint8, device=dev)
+    arena[:host.shape[0]].copy_(torch.from_numpy(host))
+    samples = arena.view(torch.float32)
+    for first, count, max_n_out in tables:
+        audio.resample_launch(samples, samples, arena.data_ptr() + first * size, count, max_n_out, filter)
+    return wave_prepare(samples, None, lens, segment_length, clips=arena.data_ptr() + final * size)
+
+
+def read_wav_file(filename, segment_length, target_sr=16000, device=None):
+    """tools/torch_tools.py:54-75 -> (1, segment_length) fp32 on the GPU (`read_wav_batch` of one file)."""
+    return read_wav_batch([filename], segment_length, target_sr, device)

@@ -867,6 +867,40 @@ ctta_status ctta_ssim_mean(const float* x, const float* y, int pairs, int h_max,
 ctta_status ctta_psnr_mse(const float* x, const float* y, int pairs, int h_max, int w, const int32_t* h_valid, double* mse,
                           double* ws, void* stream);
 
+/* The file loaders' resampler and waveform normalisation for a ragged batch of clips (tools/torch_tools.py:54-75
+ * `read_wav_file`; the same call in tools/t2a_dataset.py:111-122, audioldm_eval/datasets/load_mel.py:25-28 and
+ * metrics/fad.py:33-34).  resampy is a pip dependency of the reference, not part of its tree: built from the published
+ * definition of version 0.4.2 (core.resample + interpn.resample_f), restated in float64 numpy in tests/resampy_ref.py.
+ * One ctta_resample_clip per clip, filled by the host (consistencytta_amd/audio.py `resample_clip`) and read from DEVICE memory:
+ *   ctta_resample_sinc  torch_tools.py:66 -> resampy.resample(x, sr_orig, sr_new, filter): clip p reads n_in samples at
+ *                       x + x_off and writes n_out at y + y_off (x and y may be one arena; a clip's input and output must
+ *                       not overlap).  `win`: the filter's half window, n_win fp32 entries at num_table entries per zero
+ *                       crossing, UNSCALED (the clip's gain carries sample_ratio when down-sampling); delta[j] = win[j + 1] -
+ *                       win[j], 0 at the end.  Output t: time_register = t * time_increment, n = int(time_register), frac =
+ *                       scale * (time_register - n), offset = int(frac * num_table), eta = frac * num_table - offset, all in
+ *                       fp64 as separate operations; left wing sum_i (win + eta * delta)[offset + i * index_step] * x[n - i],
+ *                       i < min(n + 1, (n_win - offset) / index_step); right wing the same with frac := scale - frac on
+ *                       x[n + 1 + k], k < min(n_in - n - 1, (n_win - offset) / index_step).  Weights and sums in fp64, in
+ *                       that order: a clip's output does not depend on the rest of the batch.  max_n_out >= every n_out
+ *                       sizes the grid.
+ *   ctta_wave_prepare   torch_tools.py:69-73 on clip p's n_out samples at y + y_off: wav - mean; / (max|wav| + 1e-8) / 2;
+ *                       cut or zero-padded to `segment`; / (max|.| of the kept segment + 1e-8) / 2 -> out [n_clips][segment].
+ *                       Mean and maxima in fp64 in a fixed order, the element arithmetic in fp64 rounded once to fp32.
+ *                       ws: 3 * n_clips doubles, left holding each clip's mean, first peak and second peak.
+ * Both only enqueue on `stream` (no allocation, no synchronisation). */
+typedef struct ctta_resample_clip {
+  int64_t x_off, y_off;      /* element offset of the clip's first sample in x / y */
+  int32_t n_in, n_out;       /* n_out = int(n_in * sr_new / sr_orig) >= 1 */
+  double time_increment;     /* 1.0 / (float(sr_new) / sr_orig) */
+  double scale;              /* min(1, sample_ratio) */
+  float gain;                /* sample_ratio when < 1, else 1 */
+  int32_t index_step;        /* int(scale * num_table): truncated */
+} ctta_resample_clip;
+ctta_status ctta_resample_sinc(const float* x, float* y, const ctta_resample_clip* clips, int n_clips, int max_n_out,
+                               const float* win, int n_win, int num_table, void* stream);
+ctta_status ctta_wave_prepare(const float* y, const ctta_resample_clip* clips, int n_clips, int segment, float* out, double* ws,
+                              void* stream);
+
 /* Small fp32 linear: y[m][n] = act_out(sum_k act_in(x[m][k]) * w[n][k] + b[n]); m <= 1024.
  * act: 0 none, 1 silu. */
 ctta_status ctta_linear_f32(const float* x, const float* w, const float* b, float* y, int m,

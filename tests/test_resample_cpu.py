@@ -1,0 +1,132 @@
+"""Host side of the resampy kaiser_best rebuild (tools/torch_tools.py:54-75 `read_wav_file`): the filter table, the host
+scalars of a clip descriptor, the float64 restatement the GPU tests compare against (tests/resampy_ref.py) checked against
+an analytic sine, and the library's entry points.  resampy itself is not installed where these tests run: the definition is
+pinned by facts that hold by construction, never by the package.  Nothing here needs a GPU."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import resampy_ref as R  # noqa: E402
+from consistencytta_amd import _native as N  # noqa: E402
+from consistencytta_amd import audio  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RESAMPLE_SYMBOLS = ("ctta_resample_sinc", "ctta_wave_prepare")
+
+
+@pytest.fixture(scope="module")
+def built_lib():
+    if not os.path.exists(N.LIB_PATH):
+        N.build()
+    return N.lib()
+
+
+def test_kaiser_best_table():
+    win, num_table = audio.resampy_filter("kaiser_best")
+    assert win.dtype == np.float64 and win.shape == (32769,) and num_table == 512
+    assert win[0] == 0.9475937167399596                       # kaiser(.)[n] == 1 and sinc(0) == 1: win[0] is the rolloff
+    # the sinc factor vanishes at multiples of 512 / rolloff = 540.34 table entries
+    assert win[540] > 0.0 > win[541] and np.all(win[:541] > 0.0)
+    # the Kaiser window ends at 1 / I0(beta) and |sinc| <= 1
+    assert abs(win[-1]) <= win[0] / np.i0(14.769656459379492) * (1 + 1e-12) and np.all(np.abs(win) <= win[0])
+    again, nt = audio.resampy_filter((64, 9, 14.769656459379492, 0.9475937167399596))
+    assert nt == 512 and np.array_equal(again, win)
+    assert np.array_equal(R.sinc_window()[0], win)            # the restatement's own table is the same function
+    small, nt = audio.resampy_filter((4, 3, 5.0, 0.9))
+    assert nt == 8 and small.shape == (33,) and small[0] == 0.9
+    with pytest.raises(ValueError):
+        audio.resampy_filter("kaiser_fast")                   # its constants cannot be checked here: not built
+
+
+@pytest.mark.parametrize("sr_orig,sr_new,n_in,index_step,n_out", [(44100, 16000, 441000, 185, 160000),
+                                                                  (16000, 48000, 160000, 512, 480000)])
+def test_index_step_and_output_length(sr_orig, sr_new, n_in, index_step, n_out):
+    d = audio.resample_clip(n_in, sr_orig, sr_new)
+    assert (d.index_step, d.n_out, d.n_in) == (index_step, n_out, n_in)
+    assert R.plan(n_in, sr_orig, sr_new)[0] == n_out and R.plan(n_in, sr_orig, sr_new)[4] == index_step
+    assert audio.resample_length(n_in, sr_orig, sr_new) == n_out
+
+
+def test_host_descriptor():
+    d = audio.resample_clip(4410, 44100, 16000, x_off=7, y_off=11)
+    assert d.time_increment == 1.0 / (16000.0 / 44100) and d.scale == 16000.0 / 44100
+    assert d.gain == np.float32(16000.0 / 44100) and d.index_step == 185 == int((16000.0 / 44100) * 512)
+    assert (d.x_off, d.y_off, d.n_in, d.n_out) == (7, 11, 4410, 1600)
+    u = audio.resample_clip(1, 16000, 48000)
+    assert (u.scale, u.gain, u.index_step, u.n_out, u.time_increment) == (1.0, 1.0, 512, 3, 1.0 / 3.0)
+    with pytest.raises(ValueError):
+        audio.resample_clip(2, 44100, 16000)                  # int(2 * 16000 / 44100) == 0: resampy's ValueError
+    with pytest.raises(ValueError):
+        R.resample(np.zeros(2), 44100, 16000)
+
+
+def test_descriptor_layout_matches_the_header(tmp_path):
+    src = tmp_path / "s.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ctta.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", '
+                   'sizeof(ctta_resample_clip), offsetof(ctta_resample_clip, n_in), offsetof(ctta_resample_clip, time_increment), '
+                   'offsetof(ctta_resample_clip, scale), offsetof(ctta_resample_clip, gain), '
+                   'offsetof(ctta_resample_clip, index_step)); return 0; }\n')
+    exe = str(tmp_path / "s")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = [int(v) for v in subprocess.check_output([exe]).split()]
+    C = N.ResampleClip
+    assert got == [ctypes.sizeof(C), C.n_in.offset, C.time_increment.offset, C.scale.offset, C.gain.offset, C.index_step.offset]
+    assert [f[0] for f in C._fields_] == ["x_off", "y_off", "n_in", "n_out", "time_increment", "scale", "gain", "index_step"]
+
+
+# Restatement against sin(2 pi 1000 t) sampled at the output rate, away from the edges.  Measured: 3.2e-8, 1.7e-7, 6.1e-4,
+# 2.8e-3 (the truncated table stride is a gain error when down-sampling); bounds with headroom of 30 (up) and about 2 (down).
+# They catch a mis-stated definition; they are not a parity claim.
+@pytest.mark.parametrize("sr_orig,sr_new,bound", [(8000, 16000, 1e-6), (11025, 16000, 5e-6), (22050, 16000, 1.5e-3),
+                                                  (44100, 16000, 5e-3)])
+def test_restatement_against_an_analytic_sine(sr_orig, sr_new, bound):
+    n_in = 6000
+    x = np.sin(2 * np.pi * 1000.0 * np.arange(n_in) / sr_orig)
+    n_out, _, scale, _, index_step = R.plan(n_in, sr_orig, sr_new)
+    half = int(np.ceil((32769 // index_step + 1) * sr_new / sr_orig)) + 1      # one filter half-width, in outputs
+    pos = np.arange(half, n_out - half)
+    assert len(pos) > 500
+    y, A, taps = R.resample(x, sr_orig, sr_new, positions=pos)
+    err = float(np.abs(y - np.sin(2 * np.pi * 1000.0 * pos / sr_new)).max())
+    print("%d -> %d: max error %.3g, max taps %d" % (sr_orig, sr_new, err, taps.max()))
+    assert err <= bound
+    assert taps.max() <= 2 * (32769 // index_step) + 1 and np.all(A >= np.abs(y))
+    full = R.resample(x, sr_orig, sr_new)[0]                  # positions= selects outputs, it does not change them
+    assert len(full) == n_out and np.array_equal(full[pos], y)
+
+
+def test_wave_prepare_restatement():
+    x = np.array([0.5, -0.25, 0.0, 1.0, 0.25])
+    got = R.wave_prepare(x, 3)
+    c = x - 0.3
+    first = c / (0.7 + 1e-8) / 2
+    np.testing.assert_allclose(got, first[:3] / (np.abs(first[:3]).max() + 1e-8) / 2, rtol=0, atol=1e-16)
+    assert R.wave_prepare(x, 8).shape == (8,) and np.all(R.wave_prepare(x, 8)[5:] == 0.0)
+    assert np.all(R.wave_prepare(np.zeros(4), 6) == 0.0)
+
+
+def test_resample_entry_points_are_declared_and_exported(built_lib):
+    header = open(os.path.join(ROOT, "include", "ctta.h")).read()
+    for name in RESAMPLE_SYMBOLS:
+        assert name in N.SIGNATURES
+        assert hasattr(built_lib, name)
+        assert ("ctta_status %s(" % name) in header
+    assert "} ctta_resample_clip;" in header
+    assert "resample_sinc" in open(os.path.join(N.CSRC, "build.sh")).read()
+
+
+def test_no_cpu_path():
+    import torch
+    from consistencytta_amd import data
+    with pytest.raises(N.CttaError):
+        audio.resample(torch.zeros(1, 100), 44100, 16000)
+    with pytest.raises(N.CttaError):
+        data.wave_prepare(torch.zeros(100), [0], [100], 50)
+    with pytest.raises(ValueError):
+        audio.resample(torch.zeros(2, 100), [44100], 16000)
