@@ -147,10 +147,6 @@ SIGNATURES = {
     "ctta_attention_bwd_inplace": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                            c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                            c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]),
-    "ctta_attention_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
-                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                   c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                   c_int, c_float, c_void_p, c_int64, c_void_p]),
     "ctta_wgrad_implicit_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ctta_wgrad_implicit_inplace": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                            c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
@@ -257,10 +253,10 @@ SIGNATURES = {
     "ctta_wgrad_engine_policy": (c_int, [c_int, POINTER(WgradPolicy)]),
     "ctta_attention_fullbias": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
-    "ctta_attention_fullbias_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
-                                            c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                            c_int, c_int, c_int, c_float, c_void_p]),
+    "ctta_attention_fullbias_bwd_inplace": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                                    c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                                    c_void_p]),
     "ctta_resample_poly": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "ctta_resample_poly_bwd": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                        c_void_p]),

@@ -200,23 +200,28 @@ class _WindowAttention(torch.autograd.Function):
     (q | k | v blocks of heads * 64 columns); bias_log2 fp32 [nbb][heads][n][n]; returns [windows * n][hp]."""
 
     @staticmethod
+    def _vt(qkv, hp, n):
+        """V^T [windows][hp][vt_ld] (keys contiguous) out of the v block of qkv: what both directions' kernels read."""
+        nw = qkv.shape[0] // n
+        vt_ld = max(8, _rup(n, 8))
+        vt = torch.empty(nw, hp, vt_ld, dtype=torch.bfloat16, device=qkv.device)
+        N.check(N.lib().ctta_transpose_bf16(N.ptr(qkv), n * 3 * hp, n, hp, 3 * hp, 2 * hp, N.ptr(vt), hp * vt_ld, vt_ld, nw,
+                                            N.stream_ptr()))
+        return vt, vt_ld
+
+    @staticmethod
     def forward(ctx, qkv, bias_log2, nbb, heads, n, scale):
         qkv = qkv.contiguous()
         hp = heads * 64
         T = qkv.shape[0]
         nw = T // n
         dev = qkv.device
-        L_ = N.lib()
-        vt_ld = max(8, _rup(n, 8))
-        vt = torch.empty(nw, hp, vt_ld, dtype=torch.bfloat16, device=dev)
-        N.check(L_.ctta_transpose_bf16(N.ptr(qkv), n * 3 * hp, n, hp, 3 * hp, 2 * hp, N.ptr(vt), hp * vt_ld, vt_ld, nw,
-                                       N.stream_ptr()))
+        vt, vt_ld = _WindowAttention._vt(qkv, hp, n)
         out = torch.empty(T, hp, dtype=torch.bfloat16, device=dev)
-        need = qkv.requires_grad
         lse = torch.empty(nw, heads, n, dtype=torch.float32, device=dev)
         kptr = N.c_void_p(qkv.data_ptr() + hp * 2)
-        N.check(L_.ctta_attention_fullbias(N.ptr(qkv), 3 * hp, kptr, 3 * hp, n, N.ptr(vt), vt_ld, N.ptr(bias_log2), nbb,
-                                           N.ptr(out), hp, nw, heads, n, n, float(scale), N.ptr(lse), N.stream_ptr()))
+        N.check(N.lib().ctta_attention_fullbias(N.ptr(qkv), 3 * hp, kptr, 3 * hp, n, N.ptr(vt), vt_ld, N.ptr(bias_log2), nbb,
+                                                N.ptr(out), hp, nw, heads, n, n, float(scale), N.ptr(lse), N.stream_ptr()))
         ctx.save_for_backward(qkv, out, lse, bias_log2)
         ctx.cfg = (nbb, heads, n, scale)
         return out
@@ -226,27 +231,18 @@ class _WindowAttention(torch.autograd.Function):
         qkv, out, lse, bias_log2 = ctx.saved_tensors
         nbb, heads, n, scale = ctx.cfg
         hp = heads * 64
-        T = qkv.shape[0]
-        nw = T // n
-        dev = qkv.device
-        L_ = N.lib()
+        nw = qkv.shape[0] // n
         dout = dout.contiguous()
-        s = N.stream_ptr()
-
-        def tpose(src, col0, ld):
-            dst = torch.empty(nw, hp, 64, dtype=torch.bfloat16, device=dev)
-            N.check(L_.ctta_transpose_bf16(N.ptr(src), n * ld, n, hp, ld, col0, N.ptr(dst), hp * 64, 64, nw, s))
-            return dst
-        qt, kt, dot = tpose(qkv, 0, 3 * hp), tpose(qkv, hp, 3 * hp), tpose(dout, 0, hp)
+        vt, vt_ld = _WindowAttention._vt(qkv, hp, n)   # rebuilt, not saved: activation memory stays as it is
         dqkv = torch.empty_like(qkv)
-        dsum = torch.empty(nw, heads, n, dtype=torch.float32, device=dev)
+        dsum = torch.empty(nw, heads, n, dtype=torch.float32, device=qkv.device)
         base = qkv.data_ptr()
         dbase = dqkv.data_ptr()
-        N.check(L_.ctta_attention_fullbias_bwd(
-            N.c_void_p(base), 3 * hp, N.c_void_p(base + hp * 2), 3 * hp, n, N.c_void_p(base + 4 * hp), 3 * hp, n,
-            N.ptr(kt), 64, N.ptr(qt), N.ptr(dot), 64, N.ptr(bias_log2), nbb, N.ptr(out), hp, N.ptr(dout), hp, N.ptr(lse),
-            N.ptr(dsum), N.c_void_p(dbase), 3 * hp, N.c_void_p(dbase + hp * 2), 3 * hp, N.c_void_p(dbase + 4 * hp), 3 * hp,
-            nw, heads, n, n, float(scale), s))
+        N.check(N.lib().ctta_attention_fullbias_bwd_inplace(
+            N.c_void_p(base), 3 * hp, N.c_void_p(base + hp * 2), 3 * hp, n, N.ptr(vt), vt_ld, N.ptr(bias_log2), nbb,
+            N.ptr(out), hp, N.ptr(dout), hp, N.ptr(lse), N.ptr(dsum), N.c_void_p(dbase), 3 * hp,
+            N.c_void_p(dbase + hp * 2), 3 * hp, N.c_void_p(dbase + 4 * hp), 3 * hp, nw, heads, n, n, float(scale),
+            N.stream_ptr()))
         return dqkv, None, None, None, None, None
 
 

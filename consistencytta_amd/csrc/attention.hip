@@ -58,7 +58,6 @@ __device__ __forceinline__ float rows_sum(float x) {
   return b + o;
 }
 
-static constexpr bool attn_plain_enabled() { return true; }   // the plain self-attention kernels wherever they apply
 #define ATT_KT 64          // keys per tile
 #define ATT_LDK 80         // K tile row stride (bf16): 160 B rows are conflict-free for ds_read_b128
 #define ATT_LDV 72         // V^T tile row stride: 144 B rows are conflict-free for the paired ds_read_b64
@@ -351,11 +350,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 // while its eight waves sit at the barrier); two waves per SIMD at 186 registers (same time as three).
 // STAMP (tools/attn_timeline.py): every wave notes s_memtime at six points of every tile (first 64 tiles) in LDS and the
 // workgroup dumps them -- plus the hardware id of each wave -- when it is done.
-// ABL (timing only, WRONG results; CTTA_ATTN_ABLATE): 1 no LDS-DMA inside the loop, 2 plain FMAs instead of the
-// exponentials, 4 no score MFMAs, 6 no cross-lane row maximum -- what each component costs with everything else in place
-// (profiles/attn_timeline_r05.txt: 0.866 ms whole; 0.753 / 0.776 / 0.751 / 0.835 without: every part costs its 4-13 % and none
-// hides behind another -- the loop is bound by the number of instructions a SIMD issues, not by one pipe).
-template <bool STAMP, int ABL>
+template <bool STAMP>
 __global__ __launch_bounds__(256, 3) void attention_plain2_kernel(
     const bf16_t* __restrict__ q, int q_ld, const bf16_t* __restrict__ k, int k_ld, int k_rows,
     const bf16_t* __restrict__ vt, int vt_ld, bf16_t* __restrict__ out, int out_ld, int heads, int nq, int nk,
@@ -419,13 +414,8 @@ __global__ __launch_bounds__(256, 3) void attention_plain2_kernel(
         const bf16x8_t kf = __builtin_bit_cast(
             bf16x8_t, *reinterpret_cast<const uint4*>(&Ks[slot][(ik * 16 + lq) * 64 + (((ds * 4 + lg) ^ fsw) * 8)]));
         const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (ABL == 4) {
-          s[ik][0] = ds ? s[ik][0] + __builtin_bit_cast(f32x4_t, kf) : __builtin_bit_cast(f32x4_t, qa);
-          s[ik][1] = ds ? s[ik][1] + __builtin_bit_cast(f32x4_t, kf) : __builtin_bit_cast(f32x4_t, qc);
-        } else {
-          s[ik][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qa, ds ? s[ik][0] : z, 0, 0, 0);
-          s[ik][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qc, ds ? s[ik][1] : z, 0, 0, 0);
-        }
+        s[ik][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qa, ds ? s[ik][0] : z, 0, 0, 0);
+        s[ik][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qc, ds ? s[ik][1] : z, 0, 0, 0);
       }
     }
   };
@@ -463,8 +453,8 @@ __global__ __launch_bounds__(256, 3) void attention_plain2_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of K(t+1) / V(t) has landed ...
     __builtin_amdgcn_s_barrier();                        // ... and so has everybody else's; tile t-1 is finished everywhere
     if constexpr (STAMP) ts1 = __builtin_amdgcn_s_memtime();
-    if (ABL != 1 && t + 2 < ntiles) issue_k((t + 2) * ATT_KT, par);
-    if (ABL != 1 && t + 1 < ntiles) issue_v((t + 1) * ATT_KT, par ^ 1);
+    if (t + 2 < ntiles) issue_k((t + 2) * ATT_KT, par);
+    if (t + 1 < ntiles) issue_v((t + 1) * ATT_KT, par ^ 1);
     if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); ts5 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
     scores(par ^ 1, sn);
     if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); ts2 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
@@ -478,7 +468,7 @@ __global__ __launch_bounds__(256, 3) void attention_plain2_kernel(
         mx = vmax3(mx, sc[ik][jq][0], sc[ik][jq][1]);
         mx = vmax3(mx, sc[ik][jq][2], sc[ik][jq][3]);
       }
-      if constexpr (ABL != 6) mx = rows_max(mx); else mx = sc[0][jq][0];
+      mx = rows_max(mx);
       const float mnew = vmax2(mrun[jq], mx * scale_log2e);
       const float alpha = fast_exp2(mrun[jq] - mnew);
       mrun[jq] = mnew;
@@ -487,7 +477,7 @@ __global__ __launch_bounds__(256, 3) void attention_plain2_kernel(
       for (int ik = 0; ik < 4; ++ik)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float pv = ABL == 2 ? fmaf(sc[ik][jq][r], scale_log2e, -mnew) : fast_exp2(fmaf(sc[ik][jq][r], scale_log2e, -mnew));
+          const float pv = fast_exp2(fmaf(sc[ik][jq][r], scale_log2e, -mnew));
           sc[ik][jq][r] = pv;
           ps += pv;
         }
@@ -578,7 +568,6 @@ __global__ __launch_bounds__(256, 3) void attention_plain2_kernel(
 // debugging aid, like ctta_conv_debug_stamps: buf = (4 * 64 * 6 + 8) unsigned per workgroup of the next self-attention launches
 static thread_local unsigned* t_attn_stamps = nullptr;
 extern "C" void ctta_attention_debug_stamps(void* buf) { t_attn_stamps = (unsigned*)buf; }
-static constexpr int attn_v2_mode() { return 1; }   // round 3's self-attention kernel (round 2's stays for the shapes it does not take)
 
 extern "C" ctta_status ctta_attention(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vt,
                                       int vt_ld, const float* bias, void* out, int out_ld, int batch,
@@ -598,18 +587,17 @@ extern "C" ctta_status ctta_attention_lse(const void* q, int q_ld, const void* k
   const bool prof = ctta_prof_active();
   // executed flops: QK^T and PV over the padded head dim (2 * 2*nq*nk*64 per head)
   if (prof) ctta_prof_begin(1, 0, nq, nk, 128, (long long)batch * heads, (hipStream_t)stream);
-  if (!bias && nk % ATT_KT == 0 && attn_plain_enabled() && attn_v2_mode() && nk >= 2 * ATT_KT)
+  if (!bias && nk % ATT_KT == 0 && nk >= 2 * ATT_KT)   // round 3's self-attention kernel (round 2's takes the rest)
   {
-#define CTTA_ATTN_LAUNCH(ST, AB, SP)                                                                                          \
-  hipLaunchKernelGGL((attention_plain2_kernel<ST, AB>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, q_ld,     \
+#define CTTA_ATTN_LAUNCH(ST, SP)                                                                                              \
+  hipLaunchKernelGGL((attention_plain2_kernel<ST>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, q_ld,         \
                      (const bf16_t*)k, k_ld, k_rows, (const bf16_t*)vt, vt_ld, (bf16_t*)out, out_ld, heads, nq, nk,          \
                      scale * 1.4426950408889634f, lse, SP)
-    // (round 5's timing-only ablations -- AB = 1 / 2 / 4 / 6 of the kernel template -- are no longer instantiated)
-    if (t_attn_stamps) CTTA_ATTN_LAUNCH(true, 0, t_attn_stamps);
-    else CTTA_ATTN_LAUNCH(false, 0, nullptr);
+    if (t_attn_stamps) CTTA_ATTN_LAUNCH(true, t_attn_stamps);
+    else CTTA_ATTN_LAUNCH(false, nullptr);
 #undef CTTA_ATTN_LAUNCH
   }
-  else if (!bias && nk % ATT_KT == 0 && attn_plain_enabled())   // self-attention over whole key tiles: no additive term
+  else if (!bias && nk % ATT_KT == 0)   // self-attention over whole key tiles: no additive term
     hipLaunchKernelGGL(attention_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, q_ld,
                        (const bf16_t*)k, k_ld, k_rows, (const bf16_t*)vt, vt_ld, bias, (bf16_t*)out, out_ld, heads,
                        nq, nk, scale * 1.4426950408889634f, lse, nq, (const float*)nullptr, 1);
@@ -673,12 +661,16 @@ extern "C" ctta_status ctta_attention_fullbias(const void* q, int q_ld, const vo
 //   * dkv kernel: a workgroup owns 128 keys (32 per wave) and walks the queries:
 //        S = Q K^T,  dP = dO V^T  (keys = MFMA columns, K / V rows in registers),
 //        dV^T += dO^T P,  dK^T += Q^T dS   (A = dO^T / Q^T tiles from LDS, B = P / dS from the accumulators).
-// Operands that are needed with the contraction index contiguous (K^T, Q^T, dO^T, and V in natural
-// layout) are produced once per call by ctta_transpose_bf16 over all heads.
+// Every operand is read where it lies: Q, K, dO and O in natural layout ([B][rows][heads*64]) and V as the forward keeps
+// it, transposed ([B][heads*64][vt_ld]).  Each kernel stages its walked operands once per tile in LDS and takes whichever
+// orientation a product needs out of that one tile -- K^T, Q^T, dO^T and the V rows come from the transposing LDS read
+// (tr_frag below), so there are no transposed copies in HBM and no second LDS image of a tile.
+// D is the dq kernel's job (it holds every query's dO row in registers): it writes dsum, the dkv kernel behind it reads it.
 struct AttnBwdParams {
-  const bf16_t *q, *k, *vn, *kt, *qt, *dot, *dO;
-  int q_ld, k_ld, k_rows, vn_ld, vn_rows, kt_ld, qt_ld, do_ld;
-  const float *bias, *lse, *dsum;
+  const bf16_t *q, *k, *vt, *dO, *o;
+  int q_ld, k_ld, k_rows, vt_ld, do_ld, o_ld;
+  const float *bias, *lse;
+  float* dsum;              // [B][heads][nq], caller-owned scratch
   bf16_t *dq, *dk, *dv;
   int dq_ld, dk_ld, dv_ld;
   int heads, nq, nk;
@@ -689,15 +681,6 @@ struct AttnBwdParams {
   int q_tiles_per_split, batch, hp;
   const float* full_bias;   // FULL kernels: [full_nb][heads][nq][nk], log2 domain (window attention)
   int full_nb;
-  // TR kernels (round 5): Q, K, dO are read where they lie and V as the forward keeps it, transposed [B][heads*64][vt_ld];
-  // kt / qt / dot / vn are unused
-  const bf16_t* vt;
-  int vt_ld;
-  // D = rowsum(dO * O) computed by the dq kernel itself (it holds every query's dO row in registers) and written to dsum
-  // for the dkv kernel behind it: no separate row-dot launch (76 launches per distillation step)
-  const bf16_t* o;
-  int o_ld;
-  float* dsum_out;
 };
 
 typedef short att_s16x4_t __attribute__((ext_vector_type(4)));
@@ -744,20 +727,8 @@ __device__ __forceinline__ void fetch_vt_rows(uint4 (&reg)[2], const bf16_t* src
   }
 }
 
-
-// stages a [64 rows][64 cols] bf16 tile (row stride ld in LDS); rows >= rows_valid are zero
-__device__ __forceinline__ void stage_rows(bf16_t* lds, int ld, const bf16_t* src, size_t src_ld, int rows_valid, int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int chunk = tid + i * 256;
-    const int r = chunk >> 3, cc = (chunk & 7) * 8;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < rows_valid) v = *reinterpret_cast<const uint4*>(src + (size_t)r * src_ld + cc);
-    *reinterpret_cast<uint4*>(lds + r * ld + cc) = v;
-  }
-}
-
-// stage_rows in two halves, so a tile's global loads can be issued one tile ahead of the MFMAs that consume it
+// a [64 rows][64 cols] bf16 tile into registers (rows >= rows_valid are zero) and, later, from there into LDS (row stride
+// ld): two halves, so a tile's global loads can be issued one tile ahead of the MFMAs that consume it
 __device__ __forceinline__ void fetch_rows(uint4 (&reg)[2], const bf16_t* src, size_t src_ld, int rows_valid, int tid) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -780,11 +751,10 @@ __device__ __forceinline__ void put_rows(bf16_t* lds, int ld, const uint4 (&reg)
 // PLAIN: no additive term (bias == nullptr, no full table) and nk % 64 == 0 -- the softmax rebuild on 4-vectors: P =
 // exp2(s * scale - lse) and dS = P * (dP * scale - D * scale) are one packed FMA + exp, one packed FMA and one packed
 // multiply per pair of elements instead of seven scalar operations and a key-range test per element.
-template <bool FULL, bool PLAIN, bool TR>
+template <bool FULL, bool PLAIN>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
-  __shared__ __attribute__((aligned(16))) bf16_t Ks[64 * ATT_LDK];    // [key][d]
-  __shared__ __attribute__((aligned(16))) bf16_t Vn[64 * ATT_LDK];    // [key][d]   (TR: the V^T tile, [d][key])
-  __shared__ __attribute__((aligned(16))) bf16_t KTs[TR ? 8 : 64 * ATT_LDV];   // [d][key]   (TR: K^T is read out of Ks)
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[64 * ATT_LDK];    // [key][d]   (K^T is read out of it too)
+  __shared__ __attribute__((aligned(16))) bf16_t Vts[64 * ATT_LDK];   // [d][key]   the V^T tile
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bh = blockIdx.y;
   const int b = bh / p.heads, h = bh - b * p.heads;
@@ -793,8 +763,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   const bf16_t* qb = p.q + (size_t)b * p.nq * p.q_ld + h * 64;
   const bf16_t* dob = p.dO + (size_t)b * p.nq * p.do_ld + h * 64;
   const bf16_t* kb = p.k + (size_t)b * p.k_rows * p.k_ld + h * 64;
-  const bf16_t* vb = TR ? p.vt + ((size_t)b * p.heads + h) * 64 * p.vt_ld : p.vn + (size_t)b * p.vn_rows * p.vn_ld + h * 64;
-  const bf16_t* ktb = TR ? nullptr : p.kt + ((size_t)b * p.heads + h) * 64 * p.kt_ld;
+  const bf16_t* vb = p.vt + ((size_t)b * p.heads + h) * 64 * p.vt_ld;
   const float* bb = p.bias ? p.bias + (size_t)b * p.nk : nullptr;
   const float* fb = FULL ? p.full_bias + ((size_t)(b % p.full_nb) * p.heads + h) * p.nq * p.nk : nullptr;
 
@@ -809,30 +778,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
 #pragma unroll
     for (int ds = 0; ds < 2; ++ds) {
       qf[jq][ds] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(qb + (size_t)qi * p.q_ld + ds * 32 + lg * 8));
-      // TR: dP = dO V^T contracts over d in the k-slot order of the transposing read that delivers V out of the V^T tile
-      if constexpr (TR) dof[jq][ds] = load_perm8(dob + (size_t)qi * p.do_ld, ds * 32, lg);
-      else dof[jq][ds] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(dob + (size_t)qi * p.do_ld + ds * 32 + lg * 8));
+      // dP = dO V^T contracts over d in the k-slot order of the transposing read that delivers V out of the V^T tile
+      dof[jq][ds] = load_perm8(dob + (size_t)qi * p.do_ld, ds * 32, lg);
     }
     lse_q[jq] = p.lse[((size_t)b * p.heads + h) * p.nq + qi];
-    if (p.dsum_out) {     // this lane's 16 of the query's 64 products, then the four lane rows (fixed butterfly)
-      const bf16_t* orow = p.o + ((size_t)b * p.nq + qi) * p.o_ld + h * 64;
-      float part = 0.f;
+    // D = rowsum(dO * O): this lane's 16 of the query's 64 products, then the four lane rows (fixed butterfly)
+    const bf16_t* orow = p.o + ((size_t)b * p.nq + qi) * p.o_ld + h * 64;
+    float part = 0.f;
 #pragma unroll
-      for (int ds = 0; ds < 2; ++ds) {
-        bf16x8_t of;
-        if constexpr (TR) of = load_perm8(orow, ds * 32, lg);
-        else of = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(orow + ds * 32 + lg * 8));
-        float a[8], g[8];
-        unpack8(__builtin_bit_cast(uint4, dof[jq][ds]), a);
-        unpack8(__builtin_bit_cast(uint4, of), g);
+    for (int ds = 0; ds < 2; ++ds) {
+      float a[8], g[8];
+      unpack8(__builtin_bit_cast(uint4, dof[jq][ds]), a);
+      unpack8(__builtin_bit_cast(uint4, load_perm8(orow, ds * 32, lg)), g);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) part += a[e] * g[e];
-      }
-      d_q[jq] = rows_sum(part);
-      if (lg == 0 && q0 + jq * 16 + lq < p.nq) p.dsum_out[((size_t)b * p.heads + h) * p.nq + qi] = d_q[jq];
-    } else {
-      d_q[jq] = p.dsum[((size_t)b * p.heads + h) * p.nq + qi];
+      for (int e = 0; e < 8; ++e) part += a[e] * g[e];
     }
+    d_q[jq] = rows_sum(part);
+    if (lg == 0 && q0 + jq * 16 + lq < p.nq) p.dsum[((size_t)b * p.heads + h) * p.nq + qi] = d_q[jq];
   }
   f32x4_t o[4][2];   // dQ^T accumulators [d block][q block]
 #pragma unroll
@@ -841,23 +803,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
     for (int jq = 0; jq < 2; ++jq) o[jd][jq] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
   const int ntiles = (p.nk + 63) / 64;
-  uint4 rk[2], rv[2], rkt[2];
+  uint4 rk[2], rv[2];
   auto fetch = [&](int key0) {
     fetch_rows(rk, kb + (size_t)key0 * p.k_ld, p.k_ld, p.nk - key0, tid);
-    if constexpr (TR) {
-      fetch_vt_rows(rv, vb, p.vt_ld, key0, p.nk, tid);
-    } else {
-      fetch_rows(rv, vb + (size_t)key0 * p.vn_ld, p.vn_ld, p.nk - key0, tid);
-      fetch_rows(rkt, ktb + key0, p.kt_ld, 64, tid);   // zero beyond nk by construction of K^T
-    }
+    fetch_vt_rows(rv, vb, p.vt_ld, key0, p.nk, tid);
   };
   fetch(0);
   for (int t = 0; t < ntiles; ++t) {
     const int key0 = t * 64;
     __syncthreads();
     put_rows(Ks, ATT_LDK, rk, tid);
-    put_rows(Vn, ATT_LDK, rv, tid);
-    if constexpr (!TR) put_rows(KTs, ATT_LDV, rkt, tid);
+    put_rows(Vts, ATT_LDK, rv, tid);
     __syncthreads();
     if (t + 1 < ntiles) fetch(key0 + 64);
     f32x4_t s[4][2], dp[4][2];
@@ -868,9 +824,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
 #pragma unroll
       for (int ds = 0; ds < 2; ++ds) {
         const bf16x8_t kf = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(Ks + (ik * 16 + lq) * ATT_LDK + ds * 32 + lg * 8));
-        bf16x8_t vf;      // V rows of keys ik * 16 + lq: natural tile, or (TR) out of the [d][key] tile
-        if constexpr (TR) vf = tr_frag(Vn, ATT_LDK, ds * 32, ik * 16, lq, lg);
-        else vf = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(Vn + (ik * 16 + lq) * ATT_LDK + ds * 32 + lg * 8));
+        const bf16x8_t vf = tr_frag(Vts, ATT_LDK, ds * 32, ik * 16, lq, lg);   // V rows of keys ik * 16 + lq out of the [d][key] tile
 #pragma unroll
         for (int jq = 0; jq < 2; ++jq) {
           s[ik][jq] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[jq][ds], s[ik][jq], 0, 0, 0);
@@ -925,15 +879,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
       }
 #pragma unroll
       for (int jd = 0; jd < 4; ++jd) {
-        bf16x8_t af;      // K^T rows d = jd * 16 + lq over the 32 keys of chunk kk
-        if constexpr (TR) {
-          af = tr_frag(Ks, ATT_LDK, kk * 32, jd * 16, lq, lg);
-        } else {
-          const bf16_t* kr = KTs + (jd * 16 + lq) * ATT_LDV + kk * 32 + lg * 4;
-          const uint2 lo = *reinterpret_cast<const uint2*>(kr);
-          const uint2 hi = *reinterpret_cast<const uint2*>(kr + 16);
-          af = __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
-        }
+        const bf16x8_t af = tr_frag(Ks, ATT_LDK, kk * 32, jd * 16, lq, lg);   // K^T rows d = jd * 16 + lq over the 32 keys of chunk kk
 #pragma unroll
         for (int jq = 0; jq < 2; ++jq) o[jd][jq] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, sf[jq], o[jd][jq], 0, 0, 0);
       }
@@ -955,12 +901,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   }
 }
 
-template <bool FULL, bool PLAIN, bool TR>
+template <bool FULL, bool PLAIN>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
-  __shared__ __attribute__((aligned(16))) bf16_t Qs[64 * ATT_LDK];     // [query][d]
-  __shared__ __attribute__((aligned(16))) bf16_t dOs[64 * ATT_LDK];    // [query][d]
-  __shared__ __attribute__((aligned(16))) bf16_t QTs[TR ? 8 : 64 * ATT_LDV];    // [d][query]   (TR: read out of Qs / dOs)
-  __shared__ __attribute__((aligned(16))) bf16_t dOTs[TR ? 8 : 64 * ATT_LDV];   // [d][query]
+  __shared__ __attribute__((aligned(16))) bf16_t Qs[64 * ATT_LDK];     // [query][d]   (Q^T and dO^T are read out of
+  __shared__ __attribute__((aligned(16))) bf16_t dOs[64 * ATT_LDK];    // [query][d]    these two as well)
   __shared__ __attribute__((aligned(16))) float lse_s[64];
   __shared__ __attribute__((aligned(16))) float d_s[64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -971,9 +915,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
   const bf16_t* qb = p.q + (size_t)b * p.nq * p.q_ld + h * 64;
   const bf16_t* dob = p.dO + (size_t)b * p.nq * p.do_ld + h * 64;
   const bf16_t* kb = p.k + (size_t)b * p.k_rows * p.k_ld + h * 64;
-  const bf16_t* vb = TR ? p.vt + ((size_t)b * p.heads + h) * 64 * p.vt_ld : p.vn + (size_t)b * p.vn_rows * p.vn_ld + h * 64;
-  const bf16_t* qtb = TR ? nullptr : p.qt + ((size_t)b * p.heads + h) * 64 * p.qt_ld;
-  const bf16_t* dotb = TR ? nullptr : p.dot + ((size_t)b * p.heads + h) * 64 * p.qt_ld;
+  const bf16_t* vb = p.vt + ((size_t)b * p.heads + h) * 64 * p.vt_ld;
   const float* lseb = p.lse + ((size_t)b * p.heads + h) * p.nq;
   const float* dsb = p.dsum + ((size_t)b * p.heads + h) * p.nq;
   const float* fb = FULL ? p.full_bias + ((size_t)(b % p.full_nb) * p.heads + h) * p.nq * p.nk : nullptr;
@@ -987,15 +929,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 #pragma unroll
     for (int ds = 0; ds < 2; ++ds) {
       kf[jk][ds] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(kb + (size_t)kc * p.k_ld + ds * 32 + lg * 8));
-      if constexpr (TR) {   // this key's 8 consecutive d out of V^T [d][key]: 8 strided 2-byte loads, once per workgroup
-        unsigned short e[8];
+      unsigned short e[8];   // this key's 8 consecutive d out of V^T [d][key]: 8 strided 2-byte loads, once per workgroup
 #pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = vb[(size_t)(ds * 32 + lg * 8 + i) * p.vt_ld + kc];
-        vf[jk][ds] = __builtin_bit_cast(bf16x8_t, make_uint4(e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16),
-                                                               e[4] | ((unsigned)e[5] << 16), e[6] | ((unsigned)e[7] << 16)));
-      } else {
-        vf[jk][ds] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(vb + (size_t)kc * p.vn_ld + ds * 32 + lg * 8));
-      }
+      for (int i = 0; i < 8; ++i) e[i] = vb[(size_t)(ds * 32 + lg * 8 + i) * p.vt_ld + kc];
+      vf[jk][ds] = __builtin_bit_cast(bf16x8_t, make_uint4(e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16),
+                                                             e[4] | ((unsigned)e[5] << 16), e[6] | ((unsigned)e[7] << 16)));
     }
     kb2[jk] = key < p.nk ? (p.bias ? p.bias[(size_t)b * p.nk + key] * 1.4426950408889634f : 0.f) : -INFINITY;
   }
@@ -1008,12 +946,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
   const int ntiles = (p.nq + 63) / 64;
   const int t_begin = blockIdx.z * p.q_tiles_per_split;
   const int t_end = min(ntiles, t_begin + p.q_tiles_per_split);
-  uint4 rq[2], rdo[2], rqt[2];
+  uint4 rq[2], rdo[2];
   float r_lse = INFINITY, r_d = 0.f;
-  auto fetch = [&](int q0) {   // dO^T stays a synchronous stage: a fourth register tile spills the accumulators
+  auto fetch = [&](int q0) {
     fetch_rows(rq, qb + (size_t)q0 * p.q_ld, p.q_ld, p.nq - q0, tid);
     fetch_rows(rdo, dob + (size_t)q0 * p.do_ld, p.do_ld, p.nq - q0, tid);
-    if constexpr (!TR) fetch_rows(rqt, qtb + q0, p.qt_ld, 64, tid);     // zero beyond nq by construction
     if (tid < 64) {
       const bool ok = q0 + tid < p.nq;
       r_lse = ok ? lseb[q0 + tid] : INFINITY;   // exp2(-inf) = 0 for padded queries
@@ -1026,10 +963,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
     __syncthreads();
     put_rows(Qs, ATT_LDK, rq, tid);
     put_rows(dOs, ATT_LDK, rdo, tid);
-    if constexpr (!TR) {
-      put_rows(QTs, ATT_LDV, rqt, tid);
-      stage_rows(dOTs, ATT_LDV, dotb + q0, p.qt_ld, 64, tid);
-    }
     if (tid < 64) {   // PLAIN keeps them negated (and D pre-scaled): operands of the packed FMAs below
       lse_s[tid] = PLAIN ? -r_lse : r_lse;
       d_s[tid] = PLAIN ? -r_d * p.scale : r_d;
@@ -1102,18 +1035,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
       }
 #pragma unroll
       for (int jd = 0; jd < 4; ++jd) {
-        bf16x8_t daf, qaf;    // dO^T / Q^T rows d = jd * 16 + lq over the 32 queries of chunk kk
-        if constexpr (TR) {
-          daf = tr_frag(dOs, ATT_LDK, kk * 32, jd * 16, lq, lg);
-          qaf = tr_frag(Qs, ATT_LDK, kk * 32, jd * 16, lq, lg);
-        } else {
-          const bf16_t* dr = dOTs + (jd * 16 + lq) * ATT_LDV + kk * 32 + lg * 4;
-          const bf16_t* qr = QTs + (jd * 16 + lq) * ATT_LDV + kk * 32 + lg * 4;
-          const uint2 dlo = *reinterpret_cast<const uint2*>(dr), dhi = *reinterpret_cast<const uint2*>(dr + 16);
-          const uint2 qlo = *reinterpret_cast<const uint2*>(qr), qhi = *reinterpret_cast<const uint2*>(qr + 16);
-          daf = __builtin_bit_cast(bf16x8_t, make_uint4(dlo.x, dlo.y, dhi.x, dhi.y));
-          qaf = __builtin_bit_cast(bf16x8_t, make_uint4(qlo.x, qlo.y, qhi.x, qhi.y));
-        }
+        // dO^T / Q^T rows d = jd * 16 + lq over the 32 queries of chunk kk
+        const bf16x8_t daf = tr_frag(dOs, ATT_LDK, kk * 32, jd * 16, lq, lg);
+        const bf16x8_t qaf = tr_frag(Qs, ATT_LDK, kk * 32, jd * 16, lq, lg);
 #pragma unroll
         for (int jk = 0; jk < 2; ++jk) {
           dv[jd][jk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(daf, pf[jk], dv[jd][jk], 0, 0, 0);
@@ -1177,69 +1101,34 @@ __global__ void attn_bwd_fold_kernel(const float* __restrict__ part, int nz, int
   }
 }
 
-// D[b][h][q] = sum_d dO[q][h*64+d] * O[q][h*64+d]: one wave per query row, 8 lanes per head
-__global__ __launch_bounds__(256) void attn_rowdot_kernel(const bf16_t* __restrict__ dO, int do_ld,
-                                                          const bf16_t* __restrict__ o, int o_ld, float* __restrict__ dsum,
-                                                          int batch, int heads, int nq) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long long)batch * nq) return;
-  const int b = (int)(row / nq), qi = (int)(row - (long long)b * nq);
-  for (int c8 = lane; c8 < heads * 8; c8 += 64) {
-    float a[8], g[8];
-    unpack8(*reinterpret_cast<const uint4*>(dO + (size_t)row * do_ld + c8 * 8), a);
-    unpack8(*reinterpret_cast<const uint4*>(o + (size_t)row * o_ld + c8 * 8), g);
-    float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc += a[e] * g[e];
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    acc += __shfl_xor(acc, 4, 64);
-    if ((lane & 7) == 0) dsum[((size_t)b * heads + (c8 >> 3)) * nq + qi] = acc;
-  }
-}
-
-static ctta_status attention_bwd_impl(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vn,
-                                      int vn_ld, int vn_rows, const void* kt, int kt_ld, const void* qt,
-                                      const void* dot, int qt_ld, const float* bias, const void* out, int out_ld,
-                                      const void* dout, int do_ld, const float* lse, float* dsum, void* dq, int dq_ld,
-                                      void* dk, int dk_ld, void* dv, int dv_ld, int batch, int heads, int nq, int nk,
-                                      float scale, float* partial, int64_t partial_floats, void* stream,
-                                      const float* full_bias, int full_nb, const void* vt = nullptr, int vt_ld = 0) {
-  const bool tr = vt != nullptr;      // operands read where they lie (ctta_attention_bwd_inplace)
-  CTTA_REQUIRE(q && k && out && dout && lse && dsum && dq && dk && dv && (tr ? !full_bias : (vn && kt && qt && dot)),
-               "attention_bwd: null pointer");
-  CTTA_REQUIRE(q_ld % 8 == 0 && k_ld % 8 == 0 && do_ld % 8 == 0 && out_ld % 8 == 0 && dq_ld % 4 == 0 && dk_ld % 4 == 0 && dv_ld % 4 == 0 &&
-                   (tr ? (vt_ld % 8 == 0 && vt_ld >= nk) : (vn_ld % 8 == 0 && kt_ld % 64 == 0 && qt_ld % 64 == 0)),
-               "attention_bwd: row strides (transposed operands need 64-multiples)");
-  CTTA_REQUIRE(nq > 0 && nk > 0 && k_rows >= nk && (tr || (vn_rows >= nk && kt_ld >= nk && qt_ld >= nq)), "attention_bwd: bad lengths");
+// bias (per key, may be null) and full_bias (per window position, head, query and key) are mutually exclusive; the split
+// path (partial) serves the per-key form only
+static ctta_status attention_bwd_impl(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vt,
+                                      int vt_ld, const float* bias, const float* full_bias, int full_nb, const void* out,
+                                      int out_ld, const void* dout, int do_ld, const float* lse, float* dsum, void* dq,
+                                      int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int batch, int heads, int nq,
+                                      int nk, float scale, float* partial, int64_t partial_floats, void* stream) {
+  CTTA_REQUIRE(q && k && vt && out && dout && lse && dsum && dq && dk && dv, "attention_bwd: null pointer");
+  CTTA_REQUIRE(q_ld % 8 == 0 && k_ld % 8 == 0 && do_ld % 8 == 0 && out_ld % 8 == 0 && dq_ld % 4 == 0 && dk_ld % 4 == 0 &&
+                   dv_ld % 4 == 0 && vt_ld % 8 == 0 && vt_ld >= nk,
+               "attention_bwd: row strides (vt_ld=%d must be a multiple of 8 and >= nk=%d)", vt_ld, nk);
+  CTTA_REQUIRE(nq > 0 && nk > 0 && k_rows >= nk, "attention_bwd: bad lengths");
   hipStream_t s = (hipStream_t)stream;
-  constexpr bool fuse_dsum = true;      // D = rowsum(dO * O) inside the dq kernel (round 5); the row-dot launch serves callers without it
-  if (!fuse_dsum) {
-    hipLaunchKernelGGL(attn_rowdot_kernel, dim3((unsigned)(((long long)batch * nq + 3) / 4)), dim3(256), 0, s,
-                       (const bf16_t*)dout, do_ld, (const bf16_t*)out, out_ld, dsum, batch, heads, nq);
-    CTTA_LAUNCH_CHECK();
-  }
   AttnBwdParams p;
-  p.o = (const bf16_t*)out; p.o_ld = out_ld; p.dsum_out = fuse_dsum ? dsum : nullptr;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vn = (const bf16_t*)vn; p.kt = (const bf16_t*)kt;
-  p.qt = (const bf16_t*)qt; p.dot = (const bf16_t*)dot; p.dO = (const bf16_t*)dout;
-  p.q_ld = q_ld; p.k_ld = k_ld; p.k_rows = k_rows; p.vn_ld = vn_ld; p.vn_rows = vn_rows; p.kt_ld = kt_ld; p.qt_ld = qt_ld;
-  p.do_ld = do_ld; p.bias = bias; p.lse = lse; p.dsum = dsum;
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.dO = (const bf16_t*)dout; p.o = (const bf16_t*)out;
+  p.q_ld = q_ld; p.k_ld = k_ld; p.k_rows = k_rows; p.vt_ld = vt_ld; p.do_ld = do_ld; p.o_ld = out_ld;
+  p.bias = bias; p.lse = lse; p.dsum = dsum;
   p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.dq_ld = dq_ld; p.dk_ld = dk_ld; p.dv_ld = dv_ld;
   p.heads = heads; p.nq = nq; p.nk = nk; p.scale = scale; p.scale_log2e = scale * 1.4426950408889634f;
   p.full_bias = full_bias; p.full_nb = full_nb > 0 ? full_nb : 1;
-  p.vt = (const bf16_t*)vt; p.vt_ld = vt_ld;
   const bool prof = ctta_prof_active();
   // executed flops: 7 products of 2*nq*nk*64 per head (S and dP are computed by both kernels)
   if (prof) ctta_prof_begin(1, 1, nq, nk, 448, (long long)batch * heads, s);
-  const bool plain = !full_bias && !p.bias && nk % 64 == 0 && nq % 64 == 0 && attn_plain_enabled();   // self-attention over whole tiles
+  const bool plain = !full_bias && !bias && nk % 64 == 0 && nq % 64 == 0;   // self-attention over whole tiles
   const dim3 gq((nq + 127) / 128, batch * heads);
-  if (full_bias) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false, false>), gq, dim3(256), 0, s, p);
-  else if (plain && tr) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, true>), gq, dim3(256), 0, s, p);
-  else if (plain) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, false>), gq, dim3(256), 0, s, p);
-  else if (tr) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, true>), gq, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, false>), gq, dim3(256), 0, s, p);
+  if (full_bias) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), gq, dim3(256), 0, s, p);
+  else if (plain) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), gq, dim3(256), 0, s, p);
   // few keys (cross-attention): split the query walk so that the launch still fills the chip
   const int ntiles = (nq + 63) / 64, kblocks = (nk + 127) / 128, hp = heads * 64;
   int nz = 1;
@@ -1251,11 +1140,9 @@ static ctta_status attention_bwd_impl(const void* q, int q_ld, const void* k, in
   p.part = nz > 1 ? partial : nullptr;
   p.batch = batch; p.hp = hp;
   const dim3 gk(kblocks, batch * heads, nz);
-  if (full_bias) hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, false, false>), gk, dim3(256), 0, s, p);
-  else if (plain && tr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, true, true>), gk, dim3(256), 0, s, p);
-  else if (plain) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, true, false>), gk, dim3(256), 0, s, p);
-  else if (tr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, true>), gk, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, false>), gk, dim3(256), 0, s, p);
+  if (full_bias) hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, false>), gk, dim3(256), 0, s, p);
+  else if (plain) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, true>), gk, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false>), gk, dim3(256), 0, s, p);
   if (nz > 1) {
     CTTA_REQUIRE(dk_ld >= hp && dv_ld >= hp, "attention_bwd: split path needs dk/dv rows of at least heads*64");
     const long long total = (long long)batch * nk * hp;
@@ -1267,39 +1154,24 @@ static ctta_status attention_bwd_impl(const void* q, int q_ld, const void* k, in
   return CTTA_OK;
 }
 
-extern "C" ctta_status ctta_attention_bwd(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vn,
-                                          int vn_ld, int vn_rows, const void* kt, int kt_ld, const void* qt,
-                                          const void* dot, int qt_ld, const float* bias, const void* out, int out_ld,
-                                          const void* dout, int do_ld, const float* lse, float* dsum, void* dq, int dq_ld,
-                                          void* dk, int dk_ld, void* dv, int dv_ld, int batch, int heads, int nq, int nk,
-                                          float scale, float* partial, int64_t partial_floats, void* stream) {
-  return attention_bwd_impl(q, q_ld, k, k_ld, k_rows, vn, vn_ld, vn_rows, kt, kt_ld, qt, dot, qt_ld, bias, out, out_ld, dout,
-                            do_ld, lse, dsum, dq, dq_ld, dk, dk_ld, dv, dv_ld, batch, heads, nq, nk, scale, partial,
-                            partial_floats, stream, nullptr, 1);
-}
-// The same backward with every operand read WHERE IT LIES (round 5): q / k / dout natural, V as the forward keeps it
-// (vt [B][heads*64][vt_ld], what ctta_attention consumes) -- no K^T, Q^T, dO^T or natural-V copies: the kernels take the
-// operands that need the other orientation out of the tiles they stage anyway through transposing LDS reads.
 extern "C" ctta_status ctta_attention_bwd_inplace(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vt,
                                                   int vt_ld, const float* bias, const void* out, int out_ld, const void* dout,
                                                   int do_ld, const float* lse, float* dsum, void* dq, int dq_ld, void* dk,
                                                   int dk_ld, void* dv, int dv_ld, int batch, int heads, int nq, int nk,
                                                   float scale, float* partial, int64_t partial_floats, void* stream) {
-  CTTA_REQUIRE(vt, "attention_bwd_inplace: null pointer");
-  return attention_bwd_impl(q, q_ld, k, k_ld, k_rows, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, bias, out, out_ld, dout, do_ld,
-                            lse, dsum, dq, dq_ld, dk, dk_ld, dv, dv_ld, batch, heads, nq, nk, scale, partial, partial_floats, stream,
-                            nullptr, 1, vt, vt_ld);
+  return attention_bwd_impl(q, q_ld, k, k_ld, k_rows, vt, vt_ld, bias, nullptr, 1, out, out_ld, dout, do_ld, lse, dsum, dq,
+                            dq_ld, dk, dk_ld, dv, dv_ld, batch, heads, nq, nk, scale, partial, partial_floats, stream);
 }
-// Backward of ctta_attention_fullbias (same operands as ctta_attention_bwd; no per-key bias, no split path)
-extern "C" ctta_status ctta_attention_fullbias_bwd(const void* q, int q_ld, const void* k, int k_ld, int k_rows,
-                                                   const void* vn, int vn_ld, int vn_rows, const void* kt, int kt_ld,
-                                                   const void* qt, const void* dot, int qt_ld,
-                                                   const float* full_bias_log2, int n_bias_batches, const void* out,
-                                                   int out_ld, const void* dout, int do_ld, const float* lse, float* dsum,
-                                                   void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int batch,
-                                                   int heads, int nq, int nk, float scale, void* stream) {
+// Backward of ctta_attention_fullbias: no per-key bias, no split path
+extern "C" ctta_status ctta_attention_fullbias_bwd_inplace(const void* q, int q_ld, const void* k, int k_ld, int k_rows,
+                                                           const void* vt, int vt_ld, const float* full_bias_log2,
+                                                           int n_bias_batches, const void* out, int out_ld,
+                                                           const void* dout, int do_ld, const float* lse, float* dsum,
+                                                           void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld,
+                                                           int batch, int heads, int nq, int nk, float scale,
+                                                           void* stream) {
   CTTA_REQUIRE(full_bias_log2 && n_bias_batches >= 1, "attention_fullbias_bwd: null bias table");
-  return attention_bwd_impl(q, q_ld, k, k_ld, k_rows, vn, vn_ld, vn_rows, kt, kt_ld, qt, dot, qt_ld, nullptr, out, out_ld,
-                            dout, do_ld, lse, dsum, dq, dq_ld, dk, dk_ld, dv, dv_ld, batch, heads, nq, nk, scale, nullptr, 0,
-                            stream, full_bias_log2, n_bias_batches);
+  return attention_bwd_impl(q, q_ld, k, k_ld, k_rows, vt, vt_ld, nullptr, full_bias_log2, n_bias_batches, out, out_ld, dout,
+                            do_ld, lse, dsum, dq, dq_ld, dk, dk_ld, dv, dv_ld, batch, heads, nq, nk, scale, nullptr, 0,
+                            stream);
 }

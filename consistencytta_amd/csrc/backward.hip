@@ -1066,12 +1066,11 @@ static int ln_bwd_rows_per_block(int64_t rows) {
   int rpb = (int)(rows / 2048);
   return rpb < 8 ? 8 : (rpb > 64 ? 64 : (rpb + 7) / 8 * 8);
 }
-static constexpr bool ln_bwd_two_pass() { return true; }
 // The per-block partial table of d gamma / d beta belongs to the CALLER (an engine handle's arena, a torch tensor): the
 // library keeps no table of its own (round 4 kept a process-global one keyed by (device, stream) that could only ever
 // grow -- SURVEY 8b: no global state, one handle per (device, model)).  0 = this shape takes the atomics-only path.
 extern "C" size_t ctta_layernorm_bwd_scratch_floats(int64_t rows, int ld) {
-  if (rows <= 0 || ld <= 0 || !ln_bwd_two_pass()) return 0;
+  if (rows <= 0 || ld <= 0) return 0;
   const int64_t blocks = cdiv64(rows, ln_bwd_rows_per_block(rows));
   const size_t floats = (size_t)blocks * 2 * (size_t)ld;
   return (blocks >= 16 && floats * sizeof(float) <= ((size_t)64 << 20)) ? floats : 0;

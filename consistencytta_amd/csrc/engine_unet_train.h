@@ -6,7 +6,7 @@
 //   * weight gradients : one split-M GEMM  dW[k][n] = sum_m Q[k][m] * dY^T[n][m]  per layer, where
 //                        Q = im2col(X)^T plus an all-ones row (bias gradient) and, for the resnets'
 //                        conv1, one indicator row per sample (time-embedding gradient),
-//   * attention        : flash-style backward (ctta_attention_bwd): probabilities rebuilt from the forward's
+//   * attention        : flash-style backward (ctta_attention_bwd_inplace): probabilities rebuilt from the forward's
 //                        log-sum-exp, dV = P^T dO, dP = dO V^T, dS = P (dP - D) scale, dQ = dS K, dK = dS^T Q,
 //   * norms / GEGLU / embedding MLP: the kernels in backward.hip.
 // The leaf operators and the weight-gradient jobs (plan, launch, scatter, side stream) are engine_backward.h's, shared
@@ -89,25 +89,17 @@ static ctta_status bwd_resnet(BCtx& c, Resnet& R, const bf16_t* dout, bf16_t** d
 // ------------------------------------------------------------------------------ attention
 // q [B][nq][ldq], k [B][krows][ldk] (head h at columns h*64), vt [B][hp][vt_ld]; out / dO [B*nq][hp].
 // Writes dq [B*nq][lddq], dk [B*krows][lddk], dv [B*krows][hp] for keys < nk (head-padded lanes come
-// out zero).  Flash-style (no score matrix).  Round 5: Q, K, dO are read where they lie and V as the forward keeps it
+// out zero).  Flash-style (no score matrix): Q, K, dO are read where they lie and V as the forward keeps it
 // (transposed) -- ctta_attention_bwd_inplace takes the operands it needs in the other orientation out of its own LDS tiles
-// through transposing reads; the four whole-tensor transposes per call of rounds 1-4 (CTTA_ATTN_BWD_INPLACE=0) are gone.
+// through transposing reads.
 static ctta_status bwd_attention(BCtx& c, int heads, int dh, const bf16_t* q, int ldq, const bf16_t* k, int ldk, int krows,
                                  const bf16_t* vt, int vt_ld, const float* bias, int nq, int nk, const bf16_t* out,
                                  const bf16_t* dO, int hp, const float* lse, bf16_t* dq, int lddq, bf16_t* dk, int lddk,
                                  bf16_t* dv) {
+  CTTA_REQUIRE(vt_ld % 8 == 0 && vt_ld >= nk, "bwd_attention: vt_ld=%d is not what the forward takes (nk=%d)", vt_ld, nk);
   Arena& A = *c.arena;
   const int B = c.B;
-  const int nk64 = round_up(nk, 64), nq64 = round_up(nq, 64);
   const size_t mk = A.mark();
-  const bool inplace = vt_ld % 8 == 0 && vt_ld >= nk;
-  bf16_t *vn = nullptr, *kt = nullptr, *qt = nullptr, *dot = nullptr;
-  if (!inplace) {
-    vn = A.get<bf16_t>((size_t)B * vt_ld * hp); ALLOC_OR_FAIL(vn);      // V   [B][vt_ld][hp]
-    kt = A.get<bf16_t>((size_t)B * hp * nk64); ALLOC_OR_FAIL(kt);       // K^T [B][hp][nk64]
-    qt = A.get<bf16_t>((size_t)B * hp * nq64); ALLOC_OR_FAIL(qt);       // Q^T
-    dot = A.get<bf16_t>((size_t)B * hp * nq64); ALLOC_OR_FAIL(dot);     // dO^T
-  }
   float* dsum = A.get<float>((size_t)B * heads * nq); ALLOC_OR_FAIL(dsum);
   float* part = nullptr;
   int64_t part_floats = 0;
@@ -115,18 +107,8 @@ static ctta_status bwd_attention(BCtx& c, int heads, int dh, const bf16_t* q, in
     part_floats = (int64_t)32 * 2 * B * krows * hp;
     part = A.get<float>((size_t)part_floats); ALLOC_OR_FAIL(part);
   }
-  if (inplace) {
-    RUN(c, ctta_attention_bwd_inplace(q, ldq, k, ldk, krows, vt, vt_ld, bias, out, hp, dO, hp, lse, dsum, dq, lddq, dk, lddk, dv, hp,
-                                      B, heads, nq, nk, 1.0f / sqrtf((float)dh), part, part_floats, c.stream));
-    A.release(mk);
-    return CTTA_OK;
-  }
-  RUN(c, ctta_transpose_bf16(vt, (int64_t)hp * vt_ld, hp, vt_ld, vt_ld, 0, vn, (int64_t)vt_ld * hp, hp, B, c.stream));
-  RUN(c, ctta_transpose_bf16(k, (int64_t)krows * ldk, nk, hp, ldk, 0, kt, (int64_t)hp * nk64, nk64, B, c.stream));
-  RUN(c, ctta_transpose_bf16(q, (int64_t)nq * ldq, nq, hp, ldq, 0, qt, (int64_t)hp * nq64, nq64, B, c.stream));
-  RUN(c, ctta_transpose_bf16(dO, (int64_t)nq * hp, nq, hp, hp, 0, dot, (int64_t)hp * nq64, nq64, B, c.stream));
-  RUN(c, ctta_attention_bwd(q, ldq, k, ldk, krows, vn, hp, vt_ld, kt, nk64, qt, dot, nq64, bias, out, hp, dO, hp, lse, dsum,
-                            dq, lddq, dk, lddk, dv, hp, B, heads, nq, nk, 1.0f / sqrtf((float)dh), part, part_floats, c.stream));
+  RUN(c, ctta_attention_bwd_inplace(q, ldq, k, ldk, krows, vt, vt_ld, bias, out, hp, dO, hp, lse, dsum, dq, lddq, dk, lddk, dv, hp,
+                                    B, heads, nq, nk, 1.0f / sqrtf((float)dh), part, part_floats, c.stream));
   A.release(mk);
   return CTTA_OK;
 }

@@ -422,8 +422,6 @@ __global__ __launch_bounds__(256) void gn_finalize_wide_kernel(const float* __re
   }
 }
 
-static constexpr bool gn_finalize_wide_on() { return true; }
-
 // Pass 3: apply (+SiLU).  grid = (blocks per sample, batch): a block stays inside one sample, and because its stride
 // (gridDim.x * 256 vectors) is a multiple of the C / 8 vector columns whenever C / 8 divides 256, a thread keeps ONE
 // channel vector for its whole walk -- its 8 scales and 8 shifts are loaded once into registers instead of 64 bytes of
@@ -653,7 +651,7 @@ extern "C" ctta_status ctta_groupnorm_stats_out(const void* x, void* y, int batc
   hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(nchunk, batch), dim3(256), smem, s, (const bf16_t*)x, hw,
                      c, groups, ppc, nchunk, part, (const bf16_t*)nullptr, 0, (bf16_t*)nullptr);
   CTTA_LAUNCH_CHECK();
-  if (gn_finalize_wide_on() && (long long)nchunk * groups > 2048)
+  if ((long long)nchunk * groups > 2048)
     hipLaunchKernelGGL(gn_finalize_wide_kernel, dim3((groups + 3) / 4, batch), dim3(256), 0, s, part, nchunk, groups, c, hw,
                        gamma, beta, eps, ss, stats);
   else
@@ -704,7 +702,7 @@ extern "C" ctta_status ctta_groupnorm_from_partials(const void* x, void* y, int 
     CTTA_LAUNCH_CHECK();
     return CTTA_OK;
   }
-  if (gn_finalize_wide_on() && (long long)nchunk * groups > 2048)
+  if ((long long)nchunk * groups > 2048)
     hipLaunchKernelGGL(gn_finalize_wide_kernel, dim3((groups + 3) / 4, batch), dim3(256), 0, s, partials, nchunk, groups, c, hw,
                        gamma, beta, eps, scratch, stats);
   else

@@ -705,32 +705,20 @@ ctta_status ctta_attention(const void* q, int q_ld, const void* k, int k_ld, int
                            int vt_ld, const float* bias, void* out, int out_ld, int batch,
                            int heads, int nq, int nk, float scale, void* stream);
 /* Same, and (when lse != NULL) also writes the log2-domain log-sum-exp of every query row,
- * lse[b][head][q] = log2(sum_k exp2(s*scale*log2e + bias*log2e)), which ctta_attention_bwd needs. */
+ * lse[b][head][q] = log2(sum_k exp2(s*scale*log2e + bias*log2e)), which ctta_attention_bwd_inplace needs. */
 ctta_status ctta_attention_lse(const void* q, int q_ld, const void* k, int k_ld, int k_rows,
                                const void* vt, int vt_ld, const float* bias, void* out, int out_ld,
                                int batch, int heads, int nq, int nk, float scale, float* lse,
                                void* stream);
 /* Backward of the attention above (autograd of F.scaled_dot_product_attention,
- * attention_processor.py:1127-1129) without materialising the scores.  Operands:
- *   q, k            as in the forward;  out / dout: forward output and its gradient [B*nq][*_ld]
- *   vn [B][vn_rows][vn_ld]   V in natural layout (head h at columns h*64)
- *   kt [B][heads*64][kt_ld]  K^T (keys contiguous, zero beyond nk; kt_ld multiple of 64)
- *   qt, dot [B][heads*64][qt_ld]  Q^T and dout^T (queries contiguous, zero beyond nq)
- *   lse  from ctta_attention_lse;  dsum [B][heads][nq] fp32 scratch (D = rowsum(dout*out))
+ * attention_processor.py:1127-1129) without materialising the scores.  Every operand is read where it lies:
+ *   q, k, vt, bias  exactly as the forward took them (vt [B][heads*64][vt_ld], vt_ld >= nk and a multiple of 8)
+ *   out / dout      forward output and its gradient [B*nq][*_ld]
+ *   lse             from ctta_attention_lse;  dsum [B][heads][nq] fp32 scratch (D = rowsum(dout*out))
  * Writes dq [B*nq][dq_ld], dk / dv [B*k_rows][*_ld] for keys < nk (head h at columns h*64).
  * partial (optional fp32 scratch of partial_floats): with few keys (cross-attention) the query walk of
  * the dk/dv kernel is split over up to 32 workgroups whose fp32 partial sums are folded afterwards;
  * needs 2 * splits * batch * k_rows * heads*64 floats, fewer splits are used if it is smaller. */
-ctta_status ctta_attention_bwd(const void* q, int q_ld, const void* k, int k_ld, int k_rows,
-                               const void* vn, int vn_ld, int vn_rows, const void* kt, int kt_ld,
-                               const void* qt, const void* dot, int qt_ld, const float* bias,
-                               const void* out, int out_ld, const void* dout, int do_ld,
-                               const float* lse, float* dsum, void* dq, int dq_ld, void* dk, int dk_ld,
-                               void* dv, int dv_ld, int batch, int heads, int nq, int nk, float scale,
-                               float* partial, int64_t partial_floats, void* stream);
-/* The same backward with every operand read where it lies (replaces the four whole-tensor transposes per call that fed
- * ctta_attention_bwd): q / k / dout as above, vt = V TRANSPOSED exactly as ctta_attention[_lse] took it
- * ([B][heads*64][vt_ld], vt_ld >= nk, a multiple of 8).  Same results (autograd of attention_processor.py:1127-1129). */
 ctta_status ctta_attention_bwd_inplace(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vt,
                                        int vt_ld, const float* bias, const void* out, int out_ld, const void* dout,
                                        int do_ld, const float* lse, float* dsum, void* dq, int dq_ld, void* dk, int dk_ld,
@@ -740,16 +728,16 @@ ctta_status ctta_attention_bwd_inplace(const void* q, int q_ld, const void* k, i
 /* Window attention of the CLAP audio tower (Swin, laion_clap/clap_module/htsat.py:336-361): the flash kernels above with a
  * FULL additive bias table full_bias_log2 [n_bias_batches][heads][nq][nk] (already multiplied by log2 e; relative-position
  * bias per head plus the shifted-window mask, one table per window position); batch item b reads table b % n_bias_batches.
- * Heads are padded to 64 lanes like everywhere else.  lse may be NULL in the forward. */
+ * Heads are padded to 64 lanes like everywhere else.  lse may be NULL in the forward.  The backward takes the operands of
+ * ctta_attention_bwd_inplace with the table in place of the per-key bias; it has no split path. */
 ctta_status ctta_attention_fullbias(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vt,
                                     int vt_ld, const float* full_bias_log2, int n_bias_batches, void* out, int out_ld,
                                     int batch, int heads, int nq, int nk, float scale, float* lse, void* stream);
-ctta_status ctta_attention_fullbias_bwd(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vn,
-                                        int vn_ld, int vn_rows, const void* kt, int kt_ld, const void* qt,
-                                        const void* dot, int qt_ld, const float* full_bias_log2, int n_bias_batches,
-                                        const void* out, int out_ld, const void* dout, int do_ld, const float* lse,
-                                        float* dsum, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld,
-                                        int batch, int heads, int nq, int nk, float scale, void* stream);
+ctta_status ctta_attention_fullbias_bwd_inplace(const void* q, int q_ld, const void* k, int k_ld, int k_rows, const void* vt,
+                                                int vt_ld, const float* full_bias_log2, int n_bias_batches,
+                                                const void* out, int out_ld, const void* dout, int do_ld, const float* lse,
+                                                float* dsum, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld,
+                                                int batch, int heads, int nq, int nk, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
  * CLAP fine-tuning stage (tools/losses.py:259-316): glue kernels of the audio tower.

@@ -1,6 +1,6 @@
 """The CLAP tower's front-end and glue kernels one by one, each against a float64 reference on the CPU
 (tests/clap_ops_ref.py), element by element: `ctta_wav_to_logmel_db[_bwd]`, `ctta_htsat_image[_bwd]`,
-`ctta_attention_fullbias[_bwd]`, `ctta_gather_rows`, `ctta_gelu[_bwd]`, `ctta_mean_tokens[_bwd]`,
+`ctta_attention_fullbias[_bwd_inplace]`, `ctta_gather_rows`, `ctta_gelu[_bwd]`, `ctta_mean_tokens[_bwd]`,
 `ctta_resample_poly[_bwd]`.  The tower tests (tests/test_clap_gpu.py) hold whole-model outputs to a few percent; a wrong
 halo term of the STFT adjoint, a wrong bias batch or a wrong fold row stays below that.
 
@@ -263,6 +263,35 @@ def test_window_attention_fullbias_per_element(heads, hd, n, nw, nbb):
             b, k0 = dead
             assert float(ref[b, :, k0:].abs().max()) < 1e-30
             assert float(got[b, :, k0:].abs().max()) <= R.ATTN_BWD[name] * float(ref.abs().max()), name
+
+
+@pytest.mark.parametrize("heads,hd,n,nw,nbb", [(2, 32, 12, 5, 2),     # vt_ld = 16: a 16-byte vector of V^T straddles nk
+                                               (3, 16, 20, 4, 4)])    # vt_ld = 24
+def test_fullbias_bwd_inplace_reads_no_vt_column_beyond_the_keys(heads, hd, n, nw, nbb):
+    """`ctta_attention_fullbias_bwd_inplace` through the C ABI where n is no multiple of 8: the V^T columns >= n are NaN."""
+    q, k, v, go, bias, _ = R.attention_inputs(heads, hd, n, nw, nbb)
+    scale = hd ** -0.5
+    grads_ref = R.window_attention_bwd_ref(q, k, v, bias, scale, go)
+    L, st, hp, vt_ld = lib(), N.stream_ptr(), heads * 64, (n + 7) // 8 * 8
+    qd, kd, vd, dod = (_pad_heads(t, heads, hd).to(torch.bfloat16).to(DEV) for t in (q, k, v, go))
+    vt = torch.full((nw, hp, vt_ld), float("nan"), dtype=torch.bfloat16, device=DEV)
+    vt[:, :, :n] = vd.view(nw, n, hp).transpose(1, 2)
+    bias_log2 = (bias.to(torch.float32) * C.LOG2E).contiguous().to(DEV)
+    out = torch.empty(nw * n, hp, dtype=torch.bfloat16, device=DEV)
+    lse = torch.empty(nw, heads, n, dtype=torch.float32, device=DEV)
+    N.check(L.ctta_attention_fullbias(N.ptr(qd), hp, N.ptr(kd), hp, n, N.ptr(vt), vt_ld, N.ptr(bias_log2), nbb, N.ptr(out), hp,
+                                      nw, heads, n, n, float(scale), N.ptr(lse), st))
+    dsum = torch.empty(nw, heads, n, dtype=torch.float32, device=DEV)
+    grads = [torch.full((nw * n, hp), POISON, dtype=torch.bfloat16, device=DEV) for _ in range(3)]
+    N.check(L.ctta_attention_fullbias_bwd_inplace(
+        N.ptr(qd), hp, N.ptr(kd), hp, n, N.ptr(vt), vt_ld, N.ptr(bias_log2), nbb, N.ptr(out), hp, N.ptr(dod), hp, N.ptr(lse),
+        N.ptr(dsum), N.ptr(grads[0]), hp, N.ptr(grads[1]), hp, N.ptr(grads[2]), hp, nw, heads, n, n, float(scale), st))
+    sync()
+    tag = "attn abi %s" % ((heads, hd, n, nw, nbb),)
+    for name, g, ref in zip(("dq", "dk", "dv"), grads, grads_ref):
+        got, pad = _unpad_heads(g, nw, n, heads, hd)
+        assert float(pad.abs().max()) == 0.0, name
+        assert worst_rel(got, ref, "%s %s" % (tag, name)) <= R.ATTN_BWD[name], name     # worst_rel: finite, too
 
 
 # ------------------------------------------------------------------------------------------------ 6: glue
