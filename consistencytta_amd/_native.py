@@ -360,6 +360,13 @@ SIGNATURES = {
     "ctta_adamw_ema2_zero": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_double, c_void_p, c_double, c_int,
                                      c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
     "ctta_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
+    "ctta_lora_down": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ctta_lora_up_add": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "ctta_lora_up_add_t": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float,
+                                   c_void_p]),
+    "ctta_lora_wgrad_scratch_floats": (c_size_t, [c_int64, c_int, c_int]),
+    "ctta_lora_wgrad": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float, c_void_p, c_int64, c_int64, c_void_p,
+                                c_void_p, c_void_p]),
     "ctta_prof_enable": (None, [c_int]),
     "ctta_set_option": (c_int, [c_char_p, c_int]),
     "ctta_get_option": (c_int, [c_char_p, POINTER(c_int)]),

@@ -259,6 +259,7 @@ struct WgradDone { const ctta_wgrad_geom& g; const ctta_wgrad_plan_info& pl; con
 template <typename More>
 static ctta_status layer_wgrad(GradCtx& c, ctta_wgrad_geom g, const PackMap& m, const PackMap* m2, const bf16_t* x,
                                const bf16_t* dy, More more) {
+  if (!c.params) return CTTA_OK;   // the caller wants no parameter gradients of the base network (U-Net: frozen-base mode)
   WgJob job;
   CTTA_TRY(wg_begin(c, &job));
   // the DIRECT form needs the whole slab row to belong to one pack map whose rows the kernel can place itself: the 1x1

@@ -72,6 +72,19 @@ struct Resnet {
 
 struct LNLayer { float* gamma = nullptr; float* beta = nullptr; std::string key; };
 
+// LoRA adapter of one attention projection (lora.hip): y = W x + up(down(x)).  Packed through the maps of the base layer at
+// the same site, zeros in every padded row / column: a = down.weight as [r][k_pad], b = up.weight as [n_pad][r], both fp32.
+// The activations these read carry exact zeros in their padded columns (products with zero weight rows, LayerNorm's
+// explicit zeros), so padding contributes nothing.  kmap / nmap (device) send a padded column back to its place in the
+// parameter, or to -1: the weight-gradient kernel drops padding through them.
+struct LoraSite {
+  std::string key;   // "...attn1.processor.to_q_lora."
+  float *a = nullptr, *b = nullptr;
+  int32_t *kmap = nullptr, *nmap = nullptr;
+  int k = 0, n = 0, k_pad = 0, n_pad = 0;
+  float* d = nullptr;   // down(x) [rows][r] of the training forward, kept for the backward pass
+};
+
 struct Transformer {
   int c = 0, heads = 0, dh = 0, inner = 0, cp = 0, hp = 0, ffh = 0, ffp = 0;
   GNLayer norm;
@@ -83,6 +96,7 @@ struct Transformer {
   bf16_t* front_stream = nullptr;           // ... and attn2.to_out as its front projection
   bf16_t* proj_stream = nullptr;            // ... and proj_out as its tail projection (when its width is the block's padded inner width)
   LinTrain t_proj_in, t_q1, t_k1, t_v1, t_out1, t_q2, t_k2, t_v2, t_out2, t_ff1, t_ff2, t_proj_out;
+  LoraSite lq1, lk1, lv1, lo1, lq2, lk2, lv2, lo2;   // used when the handle has adapters (ctta_unet::lora_r > 0)
   struct Saved {
     const bf16_t *x = nullptr, *g = nullptr, *s0 = nullptr, *n1 = nullptr, *qk = nullptr, *vt = nullptr, *att1 = nullptr,
                  *s1 = nullptr, *n2 = nullptr, *q2 = nullptr, *k2 = nullptr, *vt2 = nullptr, *att2 = nullptr, *s2 = nullptr,
@@ -126,6 +140,7 @@ struct ctta_unet : EngineBase {
   float *g_proj = nullptr, *g_w1 = nullptr, *g_b1 = nullptr, *g_w2 = nullptr, *g_b2 = nullptr;
   float *temb_w = nullptr, *temb_b = nullptr;
   int temb_dim = 0, temb_total = 0, cin_pad = 0, xp = 0;
+  int lora_r = 0;   // rank of the attention-projection adapters; 0: the weight table named none, and no launch differs
   // Text cache: the cross-attention K / V^T projections of the text states (32 small GEMMs per forward) live in
   // persistent buffers; a caller that queries the same handle again with the SAME text states and mask (the second CFG
   // teacher query of a distillation step, every query of the Heun teacher loop) says so with ctta_unet_reuse_text and
@@ -196,6 +211,28 @@ static ctta_status make_ln(WeightStore& ws, const std::string& p, int d, LNLayer
   return CTTA_OK;
 }
 
+static ctta_status make_lora_site(ctta_unet* U, const std::string& key, int n_src, int k_src, const std::vector<int32_t>& rows,
+                                  const std::vector<int32_t>& cols, LoraSite* S) {
+  WeightStore& ws = U->store;
+  const int r = U->lora_r, n_pad = (int)rows.size(), k_pad = (int)cols.size();
+  S->key = key; S->k = k_src; S->n = n_src; S->k_pad = k_pad; S->n_pad = n_pad;
+  std::vector<WeightStore::Seg> sa, sb;
+  auto push = [](std::vector<WeightStore::Seg>& v, int src, int dst, int count) {
+    if (!v.empty() && v.back().src_start + v.back().count == src && v.back().dst_start + v.back().count == dst) v.back().count += count;
+    else v.push_back({src, dst, count});
+  };
+  for (int j = 0; j < r; ++j)
+    for (int k = 0; k < k_pad; ++k)
+      if (cols[k] >= 0) push(sa, j * k_src + cols[k], j * k_pad + k, 1);
+  for (int n = 0; n < n_pad; ++n)
+    if (rows[n] >= 0) push(sb, rows[n] * r, n * r, r);
+  CTTA_TRY(ws.add_vector(key + "down.weight", r * k_src, r * k_pad, sa, &S->a));
+  CTTA_TRY(ws.add_vector(key + "up.weight", n_src * r, n_pad * r, sb, &S->b));
+  CTTA_TRY(ws.upload(cols, &S->kmap));
+  CTTA_TRY(ws.upload(rows, &S->nmap));
+  return CTTA_OK;
+}
+
 static ctta_status make_transformer(ctta_unet* U, const std::string& p, int c, int heads, Transformer* T) {
   WeightStore& ws = U->store;
   const int dh = c / heads, inner = heads * dh;   // unet_2d_blocks.py:873-875
@@ -254,6 +291,17 @@ static ctta_status make_transformer(ctta_unet* U, const std::string& p, int c, i
     bf16_t* dst = T->ffn_stream;
     ws.jobs.push_back([=](const WeightTable&, hipStream_t s) -> ctta_status { return ctta_ffn_pack(w1, k1, w2, k2, cp, ffp, dst, s); });
     T->want_proj_stream = true;
+  }
+  if (U->lora_r > 0) {   // adapters: the output side of q / k / v and the input side of to_out are head padded
+    const auto out_rows = identity_map(inner, cp), x_cols = identity_map(X, xp);
+    CTTA_TRY(make_lora_site(U, t + "attn1.processor.to_q_lora.", inner, inner, hmap, in_cols, &T->lq1));
+    CTTA_TRY(make_lora_site(U, t + "attn1.processor.to_k_lora.", inner, inner, hmap, in_cols, &T->lk1));
+    CTTA_TRY(make_lora_site(U, t + "attn1.processor.to_v_lora.", inner, inner, hmap, in_cols, &T->lv1));
+    CTTA_TRY(make_lora_site(U, t + "attn1.processor.to_out_lora.", inner, inner, out_rows, hmap, &T->lo1));
+    CTTA_TRY(make_lora_site(U, t + "attn2.processor.to_q_lora.", inner, inner, hmap, in_cols, &T->lq2));
+    CTTA_TRY(make_lora_site(U, t + "attn2.processor.to_k_lora.", inner, X, hmap, x_cols, &T->lk2));
+    CTTA_TRY(make_lora_site(U, t + "attn2.processor.to_v_lora.", inner, X, hmap, x_cols, &T->lv2));
+    CTTA_TRY(make_lora_site(U, t + "attn2.processor.to_out_lora.", inner, inner, out_rows, hmap, &T->lo2));
   }
   CTTA_TRY(make_ln(ws, t + "norm1.", inner, &T->ln1));
   CTTA_TRY(make_ln(ws, t + "norm2.", inner, &T->ln2));
@@ -333,12 +381,28 @@ static ctta_status run_attention(UCtx& c, const bf16_t* q, int q_ld, const bf16_
   return CTTA_OK;
 }
 
+// The adapter term of one site, behind its base launch: d = x a^T (kept by the training forward), then y += d b^T, or the
+// same into the transposed V^T [batch][hp][vt_ld] where `vt_tokens` > 0.  Everything comes from the arena.
+static ctta_status lora_forward(UCtx& c, LoraSite& S, const bf16_t* x, int ldx, int64_t rows, bf16_t* y, int ldy,
+                                int vt_tokens = 0) {
+  const int r = c.U->lora_r;
+  float* d = c.arena->get<float>((size_t)rows * r); ALLOC_OR_FAIL(d);
+  RUN(c, ctta_lora_down(x, ldx, rows, S.k_pad, S.a, 0, r, d, c.stream));
+  if (vt_tokens > 0)
+    RUN(c, ctta_lora_up_add_t(y, ldy, (int64_t)S.n_pad * ldy, c.B, vt_tokens, S.n_pad, d, vt_tokens, S.b, r, 1.0f, c.stream));
+  else
+    RUN(c, ctta_lora_up_add(y, ldy, rows, S.n_pad, d, S.b, 0, r, 1.0f, c.stream));
+  if (c.train) S.d = d;
+  return CTTA_OK;
+}
+
 static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int H, int W,
                                    bf16_t** out_p) {
   Arena& A = *c.arena;
   const int N = H * W;
   const size_t M = (size_t)c.B * N;
   const int cp = T.cp, hp = T.hp;
+  const bool lora = c.U->lora_r > 0;
   bf16_t* out = A.get<bf16_t>(M * T.c); ALLOC_OR_FAIL(out);
   const size_t mk = A.mark();
   bf16_t* g = A.get<bf16_t>(M * T.c); ALLOC_OR_FAIL(g);
@@ -350,13 +414,19 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
   // --- self-attention
   bf16_t* qk = A.get<bf16_t>(M * 2 * hp); ALLOC_OR_FAIL(qk);
   CTTA_TRY(run_linear(c, T.qk1, n, cp, M, qk, 2 * hp, nullptr, 0));
+  if (lora) {   // the fused [q | k] GEMM stays one launch; the adapters address their halves through ldy = 2 * hp
+    CTTA_TRY(lora_forward(c, T.lq1, n, cp, M, qk, 2 * hp));
+    CTTA_TRY(lora_forward(c, T.lk1, n, cp, M, qk + hp, 2 * hp));
+  }
   const int vt_ld = round_up(N, 8);
   bf16_t* vt = A.get<bf16_t>((size_t)c.B * hp * vt_ld); ALLOC_OR_FAIL(vt);
   CTTA_TRY(run_vt(c, T.v1, n, c.B, N, N, vt, vt_ld));
+  if (lora) CTTA_TRY(lora_forward(c, T.lv1, n, cp, M, vt, vt_ld, N));
   bf16_t* att = A.get<bf16_t>(M * hp); ALLOC_OR_FAIL(att);
   CTTA_TRY(run_attention(c, qk, 2 * hp, qk + hp, 2 * hp, N, vt, vt_ld, nullptr, att, hp, T.heads, N, N, T.dh, &T.sv.lse1));
   bf16_t* s1 = A.get<bf16_t>(M * cp); ALLOC_OR_FAIL(s1);
   CTTA_TRY(run_linear(c, T.out1, att, hp, M, s1, cp, s0, cp));
+  if (lora) CTTA_TRY(lora_forward(c, T.lo1, att, hp, M, s1, cp));
   // --- cross-attention against the text states
   bf16_t* const n1 = n;
   bf16_t* const att1 = att;
@@ -368,6 +438,7 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
   bf16_t* const n2 = n;
   bf16_t* q2 = A.get<bf16_t>(M * hp); ALLOC_OR_FAIL(q2);
   CTTA_TRY(run_linear(c, T.q2, n, cp, M, q2, hp, nullptr, 0));
+  if (lora) CTTA_TRY(lora_forward(c, T.lq2, n, cp, M, q2, hp));
   bf16_t* k2 = T.k2c;
   bf16_t* vt2 = T.vt2c;
   if (!k2 || c.dry) {   // sizing pass / no text cache: arena buffers
@@ -377,15 +448,23 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
   if (!c.reuse_text) {
     CTTA_TRY(run_linear(c, T.k2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp, k2, hp, nullptr, 0));
     CTTA_TRY(run_vt(c, T.v2, c.enc_bf, c.B, c.Lp, c.Lp, vt2, c.Lp));
+    if (lora) {   // into the text cache where there is one: it holds K / V^T with the adapter term
+      CTTA_TRY(lora_forward(c, T.lk2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp, k2, hp));
+      CTTA_TRY(lora_forward(c, T.lv2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp, vt2, c.Lp, c.Lp));
+    }
   }
   CTTA_TRY(run_attention(c, q2, hp, k2, hp, c.Lp, vt2, c.Lp, c.mask_bias, att, hp, T.heads, N, c.L, T.dh, &T.sv.lse2));
   bf16_t* s2 = A.get<bf16_t>(M * cp); ALLOC_OR_FAIL(s2);
   // the fused feed-forward (inference forward, widths 256 / 512, enough rows to fill its tiles) also takes attn2.to_out + residual
   // and norm3 in front and proj_out + residual behind: five launches in one, s2 the only intermediate that reaches HBM
-  const bool ffn_fused = !c.train && T.ffn_stream && ctta_ffn_geglu_wanted(cp, T.ffp, (int64_t)M);
-  const bool ffn_front = ffn_fused && T.front_stream;
+  // With adapters attn2.to_out is its own launch (its adapter term has to land before norm3), so the fused feed-forward
+  // runs without its front projection; and the sizing pass of such a handle takes the unfused branch, the larger one
+  // (ctta_ffn_geglu_wanted is not monotone in M: a smaller batch may take it).
+  const bool ffn_fused = !c.train && T.ffn_stream && !(lora && c.dry) && ctta_ffn_geglu_wanted(cp, T.ffp, (int64_t)M);
+  const bool ffn_front = ffn_fused && T.front_stream && !lora;
   if (!ffn_front) {
     CTTA_TRY(run_linear(c, T.out2, att, hp, M, s2, cp, s1, cp));
+    if (lora) CTTA_TRY(lora_forward(c, T.lo2, att, hp, M, s2, cp));
     // --- GEGLU feed-forward
     if (c.train) { n = A.get<bf16_t>(M * cp); ALLOC_OR_FAIL(n); }
     RUN(c, ctta_layernorm(s2, n, M, T.inner, cp, T.ln3.gamma, T.ln3.beta, 1e-5f, c.stream));
@@ -813,6 +892,21 @@ extern "C" ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_
   hipStream_t s = (hipStream_t)stream;
   ctta_unet* U = new ctta_unet();
   U->cfg = *cfg;
+  // A weight table that names adapter tensors ("..._lora.down.weight" / "..._lora.up.weight") gives the handle adapters at
+  // every attention projection; the rank is read from the first one's shape.  A table that lacks one of the eight tensors
+  // of an attention fails in load_weights with that key named.
+  for (int i = 0; i < n_weights && U->lora_r == 0; ++i) {
+    const char* nm = weights[i].name;
+    if (!nm || !strstr(nm, "_lora.") || weights[i].ndim != 2) continue;
+    const size_t len = strlen(nm);
+    if (len > 11 && !strcmp(nm + len - 11, "down.weight")) U->lora_r = (int)weights[i].shape[0];
+    else if (len > 9 && !strcmp(nm + len - 9, "up.weight")) U->lora_r = (int)weights[i].shape[1];
+  }
+  if (U->lora_r < 0 || U->lora_r > 16) {
+    ctta_set_error("unet_create: adapter rank %d outside [1,16]", U->lora_r);
+    delete U;
+    return CTTA_ERR_INVALID;
+  }
   ctta_status st = U->store.init(cfg->enable_training ? estimate_store_bytes_training(weights, n_weights)
                                                       : estimate_store_bytes(weights, n_weights));
   if (st == CTTA_OK) st = unet_build(U);

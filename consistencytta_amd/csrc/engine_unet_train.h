@@ -43,17 +43,61 @@ static ctta_status conv1_wgrad(BCtx& c, const Resnet& R, const bf16_t* x, int H,
 static ctta_status ln_backward(BCtx& c, const LNLayer& l, const bf16_t* x, const bf16_t* dy, const bf16_t* dx_add, bf16_t* dx,
                                int64_t rows, int d, int ld) {
   float *dg, *db;
+  Arena& A = *c.arena;
+  const size_t mk = A.mark();
+  if (!c.params) {
+    // frozen base: the kernel forms d gamma / d beta on its way to dx whatever the caller wants; they go to a throwaway row
+    // of the arena (never read), without the partial table and so without the fold launch
+    dg = A.get<float>((size_t)2 * ld); ALLOC_OR_FAIL(dg);
+    db = dg + ld;
+    RUN(c, ctta_layernorm_bwd_ws(x, dy, dx_add, dx, rows, d, ld, l.gamma, 1e-5f, dg, db, nullptr, 0, c.stream));
+    A.release(mk);
+    return CTTA_OK;
+  }
   CTTA_TRY(grad_ptr(c, l.key + "weight", &dg));
   CTTA_TRY(grad_ptr(c, l.key + "bias", &db));
   // the partial table of d gamma / d beta comes from THIS handle's arena and goes back at once: everything that may later
   // be placed on top of it is written by kernels enqueued on c.stream behind the fold
-  Arena& A = *c.arena;
-  const size_t mk = A.mark();
   const size_t nf = ctta_layernorm_bwd_scratch_floats(rows, ld);
   float* part = nf ? A.get<float>(nf) : nullptr;
   if (nf && !part) { ctta_set_error("arena exhausted (layernorm backward partials)"); return CTTA_ERR_NOMEM; }
   RUN(c, ctta_layernorm_bwd_ws(x, dy, dx_add, dx, rows, d, ld, l.gamma, 1e-5f, dg, db, part, nf, c.stream));
   A.release(mk);
+  return CTTA_OK;
+}
+
+// Adapter backward of one projection site y = W x + up(down(x)), behind the base layer's own data gradient:
+//   dD = dY B,  dB += dY^T D,  dA += dD^T X,  dX += dD A  (dx NULL: the input carries no gradient -- the text states).
+// The parameter gradients are formed when the gradient table names the site's two tensors.  All launches run on the main
+// stream out of the handle's arena.
+static ctta_status lora_backward(BCtx& c, LoraSite& S, const bf16_t* x, int ldx, const bf16_t* dy, int lddy, int64_t rows,
+                                 bf16_t* dx, int lddx) {
+  const int r = c.U->lora_r;
+  Arena& A = *c.arena;
+  float *ga = nullptr, *gb = nullptr;
+  bool want = c.dry;
+  if (!c.dry) {
+    auto ia = c.grads->map.find(S.key + "down.weight"), ib = c.grads->map.find(S.key + "up.weight");
+    const bool ha = ia != c.grads->map.end() && ia->second, hb = ib != c.grads->map.end() && ib->second;
+    if (ha != hb) {
+      ctta_set_error("%s: no gradient tensor for '%s%s'", c.who, S.key.c_str(), ha ? "up.weight" : "down.weight");
+      return CTTA_ERR_MISSING_KEY;
+    }
+    want = ha;
+    if (want) { ga = ia->second; gb = ib->second; }
+  }
+  if (!want && !dx) return CTTA_OK;
+  float* dd = A.get<float>((size_t)rows * r); ALLOC_OR_FAIL(dd);
+  RUN(c, ctta_lora_down(dy, lddy, rows, S.n_pad, S.b, 1, r, dd, c.stream));
+  if (want) {
+    size_t nf = ctta_lora_wgrad_scratch_floats(rows, S.n_pad, r);
+    const size_t nk = ctta_lora_wgrad_scratch_floats(rows, S.k_pad, r);
+    if (nk > nf) nf = nk;
+    float* part = A.get<float>(nf); ALLOC_OR_FAIL(part);
+    RUN(c, ctta_lora_wgrad(S.d, dy, lddy, rows, S.n_pad, r, 1.0f, gb, 1, r, S.nmap, part, c.stream));
+    RUN(c, ctta_lora_wgrad(dd, x, ldx, rows, S.k_pad, r, 1.0f, ga, S.k, 1, S.kmap, part, c.stream));
+  }
+  if (dx) RUN(c, ctta_lora_up_add(dx, lddx, rows, S.k_pad, dd, S.a, 1, r, 1.0f, c.stream));
   return CTTA_OK;
 }
 
@@ -122,6 +166,7 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
   const int64_t M = (int64_t)c.B * N;
   const int cp = T.cp, hp = T.hp, ffp = T.ffp;
   const int vt_ld = round_up(N, 8);
+  const bool lora = c.U->lora_r > 0;
   bf16_t* dx = A.get<bf16_t>((size_t)M * T.c); ALLOC_OR_FAIL(dx);
   const size_t mk = A.mark();
   // out = proj_out(s3) + x
@@ -149,6 +194,7 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     const int Lp = c.Lp;
     bf16_t* datt = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(datt);
     CTTA_TRY(linear_dgrad(c, T.t_out2.d, ds, cp, cp, M, datt, hp, hp, false));
+    if (lora) CTTA_TRY(lora_backward(c, T.lo2, S.att2, hp, ds, cp, M, datt, hp));
     CTTA_TRY(linear_wgrad(c, T.t_out2.m, nullptr, S.att2, hp, M, ds, cp));
     bf16_t* dq = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(dq);
     const size_t kv = (size_t)c.B * Lp * hp;
@@ -162,6 +208,11 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
                            dq, hp, dk, hp, dv));
     bf16_t* dn = A.get<bf16_t>((size_t)M * cp); ALLOC_OR_FAIL(dn);
     CTTA_TRY(linear_dgrad(c, T.t_q2.d, dq, hp, hp, M, dn, cp, cp, false));
+    if (lora) {   // dn has its one owner (the line above) before the adapter adds into it; the text states take no gradient
+      CTTA_TRY(lora_backward(c, T.lq2, S.n2, cp, dq, hp, M, dn, cp));
+      CTTA_TRY(lora_backward(c, T.lk2, c.enc_bf, c.U->xp, dk, hp, (int64_t)c.B * Lp, nullptr, 0));
+      CTTA_TRY(lora_backward(c, T.lv2, c.enc_bf, c.U->xp, dv, hp, (int64_t)c.B * Lp, nullptr, 0));
+    }
     CTTA_TRY(linear_wgrad(c, T.t_q2.m, nullptr, S.n2, cp, M, dq, hp));
     CTTA_TRY(linear_wgrad(c, T.t_k2.m, nullptr, c.enc_bf, c.U->xp, (int64_t)c.B * Lp, dk, hp));
     CTTA_TRY(linear_wgrad(c, T.t_v2.m, nullptr, c.enc_bf, c.U->xp, (int64_t)c.B * Lp, dv, hp));
@@ -173,6 +224,7 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     const size_t m2 = A.mark();
     bf16_t* datt = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(datt);
     CTTA_TRY(linear_dgrad(c, T.t_out1.d, ds, cp, cp, M, datt, hp, hp, false));
+    if (lora) CTTA_TRY(lora_backward(c, T.lo1, S.att1, hp, ds, cp, M, datt, hp));
     CTTA_TRY(linear_wgrad(c, T.t_out1.m, nullptr, S.att1, hp, M, ds, cp));
     bf16_t* dqk = A.get<bf16_t>((size_t)M * 2 * hp); ALLOC_OR_FAIL(dqk);
     bf16_t* dv = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(dv);
@@ -182,6 +234,11 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     CTTA_TRY(linear_dgrad(c, T.t_q1.d, dqk, hp, 2 * hp, M, dn, cp, cp, false));
     CTTA_TRY(linear_dgrad(c, T.t_k1.d, dqk + hp, hp, 2 * hp, M, dn, cp, cp, true));
     CTTA_TRY(linear_dgrad(c, T.t_v1.d, dv, hp, hp, M, dn, cp, cp, true));
+    if (lora) {   // behind the owner (q, accumulate = false) and the two accumulating data gradients
+      CTTA_TRY(lora_backward(c, T.lq1, S.n1, cp, dqk, 2 * hp, M, dn, cp));
+      CTTA_TRY(lora_backward(c, T.lk1, S.n1, cp, dqk + hp, 2 * hp, M, dn, cp));
+      CTTA_TRY(lora_backward(c, T.lv1, S.n1, cp, dv, hp, M, dn, cp));
+    }
     CTTA_TRY(linear_wgrad(c, T.t_q1.m, &T.t_k1.m, S.n1, cp, M, dqk, 2 * hp));
     CTTA_TRY(linear_wgrad(c, T.t_v1.m, nullptr, S.n1, cp, M, dv, hp));
     CTTA_TRY(ln_backward(c, T.ln1, S.s0, dn, ds, ds_next[2], M, T.inner, cp));
@@ -206,6 +263,7 @@ static ctta_status bwd_embeddings(BCtx& c) {
   const ctta_unet::TrainSaved& S = U->ts;
   const int B = c.B, T = U->temb_dim, total = U->temb_total, c0 = U->cfg.block_out_channels[0];
   // temb_all = Linear(SiLU(emb)) over the concatenated time_emb_proj table (its weight gradients were taken per resnet)
+  if (!c.params) return CTTA_OK;   // frozen base: d emb feeds parameter gradients only
   float* demb = A.get<float>((size_t)B * T); ALLOC_OR_FAIL(demb);
   RUN(c, ctta_linear_f32_bwd(S.emb_silu, U->temb_w, c.dtemb_all, total, S.emb, demb, nullptr, nullptr, B, total, T, 0, 0,
                              c.stream));
@@ -236,7 +294,14 @@ static void bctx_init(BCtx& c, ctta_unet* U, bool dry, const GradTable* grads, h
   U->bind(c, stream, dry, false, 0);   // the backward emits no fused GroupNorm statistics
   c.U = U; c.B = S.B; c.L = S.L; c.Lp = S.Lp; c.train = true;
   c.enc_bf = S.enc_bf; c.mask_bias = S.mask_bias;
-  c.grads = grads; c.params = true; c.who = "unet_backward"; c.norm_groups = U->cfg.norm_num_groups;
+  c.grads = grads; c.who = "unet_backward"; c.norm_groups = U->cfg.norm_num_groups;
+  // Per parameter kind: a table that names no base parameter (adapter tensors only) is the frozen-base mode -- no base
+  // weight-gradient job is launched anywhere in the network (convolutions, linears, norms, embeddings); one that names any
+  // base parameter asks for all of them, as ever.  Adapter gradients follow their own names (lora_backward).
+  c.params = dry || U->lora_r == 0;
+  if (!c.params)
+    for (const auto& kv : grads->map)
+      if (kv.first.find("_lora.") == std::string::npos) { c.params = true; break; }
   c.side = &U->wg; c.policy = &kWgradPolicyUnet;
   c.dtemb_all = U->bw.dtemb_all;
 }

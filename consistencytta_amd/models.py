@@ -115,8 +115,10 @@ def do_ema_update(source_model, shadow_models, decay_consts):
                                     float(decay_consts[1]) if b is not None else 0.0, n, N.stream_ptr()))
 
     def launch_flats():       # every network lives in one flat buffer with the same layout: one launch for the whole model
+        # (with LoRA adapters: for the adapter segment, the prefix of the buffers; the frozen base is not walked)
+        n = source_model.n_trainable() if getattr(source_model, "lora_rank", 0) else flats[0].numel()
         with torch.cuda.device(flats[0].device):
-            launch(flats[0], flats[1:], flats[0].numel())
+            launch(flats[0], flats[1:], n)
         for m in shadow_models:
             m.mark_weights_changed()
 
@@ -288,7 +290,7 @@ class AudioDistilledModel(nn.Module):
                  teacher_guidance_scale=3, unet_config=None, text_encoder=None, tokenizer=None, **kwargs):
         super().__init__()
         assert unet_model_name is None, "pretrained hub U-Nets need network access"
-        assert not use_lora, "LoRA is unused by train.sh and not built"
+        self.use_lora = use_lora
         self.text_encoder_name = text_encoder_name
         self.scheduler_name = scheduler_name
         self.unet_model_config_path = unet_model_config_path
@@ -316,6 +318,16 @@ class AudioDistilledModel(nn.Module):
     @property
     def device(self):
         return next(self.student_unet.parameters()).device
+
+    def setup_lora(self):
+        """audio_distilled_model.py:116-145: freezes the student and gives each of its attention layers a rank-4
+        LoRAAttnProcessor; the adapters are then the student's only trainable parameters."""
+        self.student_unet.enable_lora_(rank=4)
+
+    def _lora_single_process_only(self, what):
+        if self.student_unet.lora_rank:
+            raise NotImplementedError("%s is not built for a student with LoRA adapters: LoRA steps run eagerly in one "
+                                      "process" % what)
 
     def _require_text_encoder(self):
         if self.text_encoder is None or self.tokenizer is None:
@@ -402,6 +414,8 @@ class AudioDistilledModel(nn.Module):
         """Flat parameter buffers for the student family, rank-0 weights on every rank (DDP's wrap-time
         broadcast) and the fused AdamW over the student (tools/train_utils.py:59-63)."""
         from .optim import FusedAdamW
+        if dist_util.dist.is_initialized() and dist_util.dist.get_world_size() > 1:
+            self._lora_single_process_only("data-parallel training (a process group of more than one rank)")
         self.student_unet.enable_training = True
         for m in [self.student_unet] + list(self._ema_shadows()[0]):
             flat = m.flatten_parameters_()
@@ -474,6 +488,13 @@ class AudioLCM(AudioDistilledModel):
                  snr_gamma=None, freeze_text_encoder=True, uncondition=False, use_edm=False, use_karras=False,
                  use_lora=False, target_ema_decay=.95, ema_decay=.999, num_diffusion_steps=18,
                  teacher_guidance_scale=1, vae=None, loss_type="mse", clap_module=None, **kwargs):
+        if use_lora:
+            # setup_lora runs on the student only (audio_consistency_model.py:151-157), so the reference's first
+            # update_ema() fails: student and shadows no longer have the same parameter keys
+            raise NotImplementedError(
+                "use_lora is built for stage 1 (AudioGDM) only: the reference's stage-2 LoRA stops at its first update_ema() "
+                "on `assert model_params.keys() == shadow_params.keys()` (tools/train_utils.py:274), so there is no "
+                "behaviour to reproduce")
         super().__init__(text_encoder_name=text_encoder_name, scheduler_name=scheduler_name,
                          unet_model_name=unet_model_name, unet_model_config_path=unet_model_config_path,
                          snr_gamma=snr_gamma, freeze_text_encoder=freeze_text_encoder, use_lora=use_lora,
@@ -887,6 +908,42 @@ class AudioGDM(AudioDistilledModel):
     def _ema_shadows(self):
         return [self.student_ema_unet], [self.ema_decay]
 
+    def _rebuild_ema_student(self):
+        self.student_ema_unet = deepcopy(self.student_unet)
+        self.student_ema_unet.eval().requires_grad_(False)
+
+    def load_state_dict_from_tango(self, tango_state_dict, **kwargs):
+        """audio_guided_model.py:53-85: TANGO's `unet.*` becomes the teacher and seeds the student and its EMA copy; every
+        other key passes through.  A strict load first, then a non-strict one that refuses unknown keys.  With `use_lora`
+        the adapters are set up afterwards and the EMA student is rebuilt as a copy, adapters included."""
+        new_sd = OrderedDict()
+        for key, val in tango_state_dict.items():
+            if "unet" in key and "_unet" not in key:
+                for m in ("teacher", "student", "student_ema"):
+                    new_sd[m + "_" + key] = val
+            else:
+                new_sd[key] = val
+        try:
+            info = self.load_state_dict(new_sd, strict=True)
+        except Exception:
+            print("Strict loading failed. The loaded state_dict may not match the target model.")
+            info = self.load_state_dict(new_sd, strict=False)
+            print(f"Keys that are not loaded: {info.missing_keys}")
+            assert len(info.unexpected_keys) == 0, f"Redundant keys in state_dict: {info.unexpected_keys}"
+        if self.use_lora:
+            self.setup_lora()
+        self._rebuild_ema_student()
+        return info
+
+    def load_pretrained(self, state_dict, strict=True):
+        """Loads a stage-1 checkpoint (this model's own `state_dict()` keys).  On a model built with `use_lora=True`, a
+        state dict that carries adapter keys sets the adapters up (student and EMA copy) before loading.  The reference
+        cannot do this: its placeholder is a strict load into a model without processors."""
+        if self.use_lora and not self.student_unet.lora_rank and any("_lora." in k for k in state_dict):
+            self.setup_lora()
+            self._rebuild_ema_student()
+        return self.load_state_dict(state_dict, strict=strict)
+
     def compute_snr(self, timesteps):
         """alpha^2 / sigma^2 with alpha = sqrt(alphas_cumprod[t]) (audio_distilled_model.py:165-191), host side."""
         ac = self.noise_scheduler.alphas_cumprod[torch.as_tensor(timesteps).reshape(-1).to("cpu", torch.int64)]
@@ -961,6 +1018,8 @@ class AudioGDM(AudioDistilledModel):
     def train_step(self, z_0, prompt, optimizer, lr_scheduler=None, skip_nan=True, **fw):
         """loss -> backward (+ overlapped RCCL gradient all-reduce) -> AdamW -> schedule -> zero_grad -> EMA."""
         assert self.training, "train_step needs model.train()"
+        if self.student_unet.lora_rank and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            self._lora_single_process_only("a captured training step")
         with torch.no_grad():
             loss, *saved = self._forward_impl(z_0, prompt, True, fw.pop("time_inds", None), fw.pop("gaussian_noise", None),
                                               fw.pop("guidance_scale", None))

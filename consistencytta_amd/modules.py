@@ -273,6 +273,75 @@ class _UNetBase(_ParamTree):
         self._engine = N.EngineHandle("ctta_unet_destroy")
         self.debug_taps = False
         self.enable_training = False   # True: the native handle also carries the backward pass
+        self.lora_rank = 0             # > 0: adapters at the attention projections (enable_lora_)
+
+    # ---- LoRA (audio_distilled_model.py:116-145 -> diffusers LoRAAttnProcessor, attention_processor.py:508-613)
+    def enable_lora_(self, rank=4, generator=None):
+        """Gives every attention projection (to_q / to_k / to_v / to_out of attn1 and attn2) a rank-`rank` adapter,
+        y = W x + up(down(x)), and freezes every base parameter: what `setup_lora` does to the reference's student.
+        The adapters are registered under the reference's key names (`...attn1.processor.to_q_lora.down.weight`), so the
+        state dict has the reference's keys in its order; init as LoRALinearLayer: down ~ N(0, 1 / rank^2), up = 0.
+        They are the only trainable parameters and therefore the prefix `[0, n_trainable())` of the flat parameter /
+        gradient buffers (`_flat_order`), which is all the fused optimizer and EMA passes walk.  In place; returns self."""
+        rank = int(rank)
+        if self.lora_rank:
+            if rank != self.lora_rank:
+                raise ValueError("adapters of rank %d are already set up (asked for rank %d)" % (self.lora_rank, rank))
+            return self
+        if not 1 <= rank <= 16:
+            raise ValueError("LoRA rank %d is outside what the HIP kernels take (1..16)" % rank)
+        dev = self.device
+        base = [k for k, _ in self.named_parameters()]
+        for p in self.parameters():
+            p.requires_grad_(False)
+            p.grad = None
+        for key, shape in spec.lora_param_spec(self._cfg, rank, self._guided).items():
+            mod = self
+            parts = key.split(".")
+            for q in parts[:-1]:
+                if q not in mod._modules:
+                    mod.add_module(q, nn.Module())
+                mod = mod._modules[q]
+            if parts[-2] == "down":
+                w = (torch.randn(*shape, generator=generator, dtype=torch.float32) / rank).to(dev)
+            else:
+                w = torch.zeros(*shape, dtype=torch.float32, device=dev)
+            mod.register_parameter(parts[-1], nn.Parameter(w, requires_grad=True))
+        self._frozen_keys = tuple(base)
+        self.lora_rank = rank
+        self._drop_flat_()
+        return self
+
+    def _drop_flat_(self):
+        """The parameter set changed: the flat buffers, their caches and the packed copy in the handle are stale."""
+        self._flat = self._flat_grad = self._trainable_cache = None
+        self._rehome_count = getattr(self, "_rehome_count", 0) + 1
+        self.mark_weights_changed()
+
+    def lora_keys(self):
+        return [k for k, _ in self.named_parameters() if "_lora." in k]
+
+    def merge_lora_(self):
+        """Folds every adapter into its base weight, W += up @ down (fp32, in place), and drops the adapters: the module
+        is a plain U-Net again and serves at the plain U-Net's cost.  `requires_grad` stays as it is (all False)."""
+        if not self.lora_rank:
+            return self
+        params = dict(self.named_parameters())
+        with torch.no_grad():
+            for key in spec.lora_param_spec(self._cfg, self.lora_rank, self._guided):
+                if not key.endswith("down.weight"):
+                    continue
+                site = key[:-len("down.weight")]                        # "...attn1.processor.to_q_lora."
+                attn, layer = site.split("processor.")
+                wkey = attn + layer[:-len("_lora.")] + (".0.weight" if layer.startswith("to_out") else ".weight")
+                params[wkey].add_(params[site + "up.weight"] @ params[key])
+        for k, m in list(self.named_modules()):
+            if "processor" in m._modules:
+                del m._modules["processor"]
+        self._frozen_keys = ("guidance_proj.weight",)
+        self.lora_rank = 0
+        self._drop_flat_()
+        return self
 
     # ---- config plumbing (configuration_utils.py:161,256)
     @classmethod
@@ -319,7 +388,7 @@ class _UNetBase(_ParamTree):
         """Capacity (max_batch, max_text_len) only grows at a fixed (H, W); max_text_len is never below 32 and survives
         an extent change, max_batch does not.  Changed weights are re-packed into the SAME handle."""
         L_, e = N.lib(), self._engine
-        key = (H, W, self.debug_taps, self.enable_training, self.device)
+        key = (H, W, self.debug_taps, self.enable_training, self.device) + ((self.lora_rank,) if self.lora_rank else ())
         ver = self._weights_version()
         if not e.fits((B, L), key, e.version):
             Bm = max(B, e.capacity[0]) if e.key and e.key[:2] == (H, W) else B

@@ -21,6 +21,9 @@ class FusedAdamW:
         self.flat = module.flatten_parameters_()
         self.grad = module.flat_grad_()
         self.n = module.n_trainable()
+        # what zero_grad and the fused tail's EMA walk: the whole buffer, or -- LoRA adapters, the frozen base behind them
+        # never moves and never gets a gradient -- the trainable prefix alone
+        self.n_tail = self.n if getattr(module, "lora_rank", 0) else self.flat.numel()
         self.exp_avg = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self.exp_avg_sq = torch.zeros(self.n, dtype=torch.float32, device=self.flat.device)
         self.param_groups = [dict(lr=float(lr), betas=tuple(betas), eps=float(eps), weight_decay=float(weight_decay))]
@@ -39,7 +42,7 @@ class FusedAdamW:
         return t
 
     def zero_grad(self, set_to_none=False):
-        self.grad.zero_()
+        self.grad[:self.n_tail].zero_()
 
     def step(self, grad_scale=1.0):
         """One update; `grad_scale` multiplies the gradient inside the kernel (1/world_size after a
@@ -64,7 +67,7 @@ class FusedAdamW:
         """Whether `step_zero_ema` may replace step() + zero_grad() + the EMA launch: shadows with this optimizer's flat
         layout, vector-aligned extents (the fused kernel has no scalar tail)."""
         n_all = self.flat.numel()
-        return (self.n % 4 == 0 and n_all % 4 == 0 and self.grad.numel() == n_all and 1 <= len(shadow_flats) <= 2
+        return (self.n % 4 == 0 and n_all % 4 == 0 and self.n_tail % 4 == 0 and self.grad.numel() == n_all and 1 <= len(shadow_flats) <= 2
                 and all(f is not None and f.numel() == n_all and f.device == self.flat.device and f.dtype == torch.float32
                         and f.data_ptr() % 16 == 0 for f in shadow_flats)
                 and all(t.data_ptr() % 16 == 0 for t in (self.flat, self.grad, self.exp_avg, self.exp_avg_sq)))
@@ -87,7 +90,7 @@ class FusedAdamW:
             self.step_count += 1
         with torch.cuda.device(self.flat.device):
             N.check(N.lib().ctta_adamw_ema2_zero(
-                N.ptr(self.flat), N.ptr(self.grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq), self.n, self.flat.numel(),
+                N.ptr(self.flat), N.ptr(self.grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq), self.n, self.n_tail,
                 N.ptr(shadow_flats[0]), float(decays[0]), N.ptr(shadow_flats[1]) if len(shadow_flats) > 1 else N.c_void_p(0),
                 float(decays[1]) if len(shadow_flats) > 1 else 0.0, 1 if do_step else 0, g["lr"], g["betas"][0], g["betas"][1],
                 g["eps"], g["weight_decay"], max(1, self.step_count), float(grad_scale), N.stream_ptr()))

@@ -175,6 +175,30 @@ def unet_param_spec(cfg, guided=True):
     return sd
 
 
+LORA_LAYERS = ("to_q_lora", "to_k_lora", "to_v_lora", "to_out_lora")
+
+
+def lora_param_spec(cfg, rank=4, guided=True):
+    """OrderedDict name -> shape of the attention-projection adapters that `AudioDistilledModel.setup_lora` gives the
+    student (audio_distilled_model.py:116-145: one LoRAAttnProcessor per attention, attention_processor.py:508-613):
+    `...attn{1,2}.processor.to_{q,k,v,out}_lora.{down,up}.weight`, down (rank, in), up (out, rank).  `in` / `out` are the
+    attention's inner width `heads * (C // heads)` -- what the reference's `hidden_size` equals in every configuration its
+    adapters run in -- except `in` of the cross-attention k / v layers, which is cross_attention_dim.  The order is the
+    one the keys take inside each attention; a module's state dict interleaves them behind that attention's `to_out`."""
+    sd = OrderedDict()
+    for key, shape in unet_param_spec(cfg, guided).items():
+        if not key.endswith(".to_q.weight"):
+            continue
+        attn = key[:-len("to_q.weight")]                    # "...transformer_blocks.0.attn1."
+        inner = shape[0]
+        kv_in = cfg["cross_attention_dim"] if attn.endswith("attn2.") else inner
+        for layer in LORA_LAYERS:
+            fan_in = kv_in if layer in ("to_k_lora", "to_v_lora") else inner
+            sd[attn + "processor.%s.down.weight" % layer] = (rank, fan_in)
+            sd[attn + "processor.%s.up.weight" % layer] = (inner, rank)
+    return sd
+
+
 def _vae_resblock(sd, p, cin, cout):
     sd[p + "norm1.weight"] = (cin,)
     sd[p + "norm1.bias"] = (cin,)

@@ -93,6 +93,11 @@ typedef struct {
 
 typedef struct ctta_unet ctta_unet;
 
+/* LoRA: a weight table that names adapter tensors (`...attn{1,2}.processor.to_{q,k,v,out}_lora.{down,up}.weight`, diffusers
+ * LoRAAttnProcessor) gives the handle adapters at every attention projection, y = W x + up(down(x)); the rank (1..16) is
+ * read from their shapes, and a table that lacks one of an attention's eight tensors fails with that key named.
+ * ctta_unet_load_weights repacks them with the rest.  In ctta_unet_backward*, a gradient table that names adapter tensors
+ * only is the frozen-base mode: no base weight gradient is formed.  A handle without adapters runs what it always ran. */
 ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_tensor* weights,
                              int n_weights, void* stream, ctta_unet** out);
 void ctta_unet_destroy(ctta_unet* h);
@@ -1053,6 +1058,32 @@ ctta_status ctta_adamw_ema2_zero(float* param, float* grad, float* exp_avg, floa
                                  float* shadow_a, double decay_a, float* shadow_b, double decay_b, int do_step, float lr,
                                  float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                                  void* stream);
+
+/* LoRA adapters of the attention projections (csrc/lora.hip; diffusers LoRAAttnProcessor): y = W x + scale * up(down(x)) with
+ * rank r in [1, 16].  The base product stays a conv_gemm launch; these add the rank-r term, forward and backward.  Adapter
+ * matrices are fp32 and taken in either orientation, so one packed A [r][k] and one packed B [n][r] serve both passes.
+ * Activations are bf16 in the engines' padded layouts: k, n and the leading dimensions are multiples of 8, the pointers
+ * 16-byte aligned.  The kernels read every column they are given; the packed adapter holds zeros in its padded rows and
+ * columns and the activations' padded columns are finite, so padding contributes exactly 0.  No float atomics: results are
+ * bit-reproducible.
+ *   down     : d[m][r] (fp32) = x[m][k] * a^T; a is [r][k], or [k][r] when a_kmajor (the backward's dD = dY * B)
+ *   up_add   : y[m][n] = bf16(float(y) + scale * d * b^T); b is [n][r], or [r][n] when b_rmajor (the backward's
+ *              dX += dD * A).  Elements whose added term is zero keep their bits.
+ *   up_add_t : the same into a transposed result yt[batch][n][tokens] (row stride ldt, batch stride batch_stride), the
+ *              rows of d being (batch, d_tokens >= tokens); b is [n][r]
+ *   wgrad    : g[j * g_stride_r + col(kk) * g_stride_k] += scale * sum_m d[m][j] * x[m][kk], col = col_map[kk] (device
+ *              int32, -1 = padded column, dropped) or kk when col_map is NULL.  g is any fp32 address (no alignment
+ *              rule).  dA = dD^T X: strides (K, 1); dB = dY^T D: strides (1, r).  Per-slab partial sums in `scratch`
+ *              (ctta_lora_wgrad_scratch_floats floats) are folded in slab order. */
+ctta_status ctta_lora_down(const void* x, int ldx, int64_t m, int k, const float* a, int a_kmajor, int r, float* d,
+                           void* stream);
+ctta_status ctta_lora_up_add(void* y, int ldy, int64_t m, int n, const float* d, const float* b, int b_rmajor, int r,
+                             float scale, void* stream);
+ctta_status ctta_lora_up_add_t(void* yt, int ldt, int64_t batch_stride, int batch, int tokens, int n, const float* d,
+                               int d_tokens, const float* b, int r, float scale, void* stream);
+size_t ctta_lora_wgrad_scratch_floats(int64_t m, int k, int r);
+ctta_status ctta_lora_wgrad(const float* d, const void* x, int ldx, int64_t m, int k, int r, float scale, float* g,
+                            int64_t g_stride_r, int64_t g_stride_k, const int32_t* col_map, float* scratch, void* stream);
 
 /* Opt-in launch profiler (bench.py's live roofline leg): when enabled, every conv_gemm (kind 0)
  * and attention (kind 1) launch is bracketed by hipEvents on its own stream.  collect() waits
