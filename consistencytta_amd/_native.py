@@ -127,6 +127,18 @@ class WgradPlanInfo(Structure):
                [(n, c_int64) for n in ("slabs", "q", "pt", "xu")]
 
 
+class LoraFwdSite(Structure):
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("y", c_void_p), ("d", c_void_p), ("ldy", c_int), ("n_pad", c_int),
+                ("tokens", c_int), ("batch_stride", c_int64)]
+
+
+class LoraBwdSite(Structure):
+    _fields_ = [("dy", c_void_p), ("a", c_void_p), ("b", c_void_p), ("d", c_void_p), ("dd", c_void_p), ("ga", c_void_p),
+                ("gb", c_void_p), ("k_map", c_void_p), ("n_map", c_void_p), ("ga_stride_r", c_int64),
+                ("ga_stride_k", c_int64), ("gb_stride_r", c_int64), ("gb_stride_k", c_int64), ("lddy", c_int),
+                ("n_pad", c_int)]
+
+
 class ResampleClip(Structure):
     """ctta_resample_clip (include/ctta.h)"""
     _fields_ = [("x_off", c_int64), ("y_off", c_int64), ("n_in", c_int32), ("n_out", c_int32), ("time_increment", c_double),
@@ -367,6 +379,13 @@ SIGNATURES = {
     "ctta_lora_wgrad_scratch_floats": (c_size_t, [c_int64, c_int, c_int]),
     "ctta_lora_wgrad": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float, c_void_p, c_int64, c_int64, c_void_p,
                                 c_void_p, c_void_p]),
+    "ctta_lora_sites_supported": (c_int, [c_int, POINTER(c_int), c_int, c_int, c_int, c_int, c_int64]),
+    "ctta_lora_sites_fwd": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_float, POINTER(LoraFwdSite), c_int, c_void_p]),
+    "ctta_lora_sites_bwd_scratch_floats": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    "ctta_lora_sites_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_float, POINTER(LoraBwdSite),
+                                    c_int, c_void_p, c_void_p]),
+    "ctta_unet_set_lora": (c_int, [c_void_p, c_int, c_float]),
+    "ctta_unet_load_adapters": (c_int, [c_void_p, POINTER(Tensor), c_int, c_void_p]),
     "ctta_prof_enable": (None, [c_int]),
     "ctta_set_option": (c_int, [c_char_p, c_int]),
     "ctta_get_option": (c_int, [c_char_p, POINTER(c_int)]),

@@ -1025,13 +1025,15 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   }
 }
 // dgamma[c] += sum_b part[b][0][c], dbeta[c] += sum_b part[b][1][c].  grid (column blocks of 64, row slices): a block folds
-// its slice of the table with 4 row lanes per column (8 loads in flight each), then adds ONE value per column and slice.
+// its slice of the table with 4 row lanes per column (8 loads in flight each) and parks ONE value per column and slice in
+// `slice_sums` [slice][2][ld]; ln_bwd_final_kernel adds the slices in slice order.  One slice: the sum goes straight into
+// dgamma / dbeta (this thread is the only writer of its column).  No float atomics: two runs give the same bits.
 // (Round 3: the kernel above used to add every block's 2 d partials straight into dgamma / dbeta -- 1536 blocks x 2 x 320
 // global atomics on 640 addresses per call, which the L2 serialises per address: 65-70 us per launch on a tensor whose
-// HBM time is 14, tools/ln_bwd_bench.py.  Now <= 32 atomics per address.)
+// HBM time is 14, tools/ln_bwd_bench.py.  Then <= 32 atomics per address; now none.)
 __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restrict__ part, int nblocks, int ld, int d,
                                                             int rows_per_slice, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta) {
+                                                            float* __restrict__ dbeta, float* __restrict__ slice_sums) {
   __shared__ float red[2][4][64];
   const int col = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
   const int r_lo = blockIdx.y * rows_per_slice, r_hi = min(nblocks, r_lo + rows_per_slice);
@@ -1055,10 +1057,30 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restr
   __syncthreads();
   if (rl == 0 && col < d) {
     const int t = threadIdx.x & 63;
-    atomicAdd(&dgamma[col], (red[0][0][t] + red[0][1][t]) + (red[0][2][t] + red[0][3][t]));
-    atomicAdd(&dbeta[col], (red[1][0][t] + red[1][1][t]) + (red[1][2][t] + red[1][3][t]));
+    const float sg = (red[0][0][t] + red[0][1][t]) + (red[0][2][t] + red[0][3][t]);
+    const float sb = (red[1][0][t] + red[1][1][t]) + (red[1][2][t] + red[1][3][t]);
+    if (slice_sums) {
+      slice_sums[(size_t)blockIdx.y * 2 * ld + col] = sg;
+      slice_sums[(size_t)blockIdx.y * 2 * ld + ld + col] = sb;
+    } else {
+      dgamma[col] += sg;
+      dbeta[col] += sb;
+    }
   }
 }
+__global__ __launch_bounds__(256) void ln_bwd_final_kernel(const float* __restrict__ slice_sums, int slices, int ld, int d,
+                                                           float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= d) return;
+  float g = 0.f, b = 0.f;
+  for (int s = 0; s < slices; ++s) {
+    g += slice_sums[(size_t)s * 2 * ld + col];
+    b += slice_sums[(size_t)s * 2 * ld + ld + col];
+  }
+  dgamma[col] += g;
+  dbeta[col] += b;
+}
+constexpr int LN_BWD_MAX_SLICES = 32;
 // Launch geometry of ctta_layernorm_bwd*: rows per block.  64 amortises the per-block dgamma / dbeta atomics on long
 // matrices, but the distillation step's token matrices are short (9 216 .. 36 864 rows): aim for >= ~2000 blocks so that
 // every CU holds several.
@@ -1068,12 +1090,13 @@ static int ln_bwd_rows_per_block(int64_t rows) {
 }
 // The per-block partial table of d gamma / d beta belongs to the CALLER (an engine handle's arena, a torch tensor): the
 // library keeps no table of its own (round 4 kept a process-global one keyed by (device, stream) that could only ever
-// grow -- SURVEY 8b: no global state, one handle per (device, model)).  0 = this shape takes the atomics-only path.
+// grow -- SURVEY 8b: no global state, one handle per (device, model)).  The table is followed by one row per slice of the
+// fold.  0 = this shape needs no table: fewer than 16 blocks' worth of rows run as ONE block, or the table would be too large.
 extern "C" size_t ctta_layernorm_bwd_scratch_floats(int64_t rows, int ld) {
   if (rows <= 0 || ld <= 0) return 0;
   const int64_t blocks = cdiv64(rows, ln_bwd_rows_per_block(rows));
   const size_t floats = (size_t)blocks * 2 * (size_t)ld;
-  return (blocks >= 16 && floats * sizeof(float) <= ((size_t)64 << 20)) ? floats : 0;
+  return (blocks >= 16 && floats * sizeof(float) <= ((size_t)64 << 20)) ? floats + (size_t)LN_BWD_MAX_SLICES * 2 * ld : 0;
 }
 extern "C" ctta_status ctta_layernorm_bwd(const void* x, const void* dy, void* dx, int64_t rows, int d, int ld,
                                           const float* gamma, float eps, int accumulate_dx, float* dgamma, float* dbeta,
@@ -1087,14 +1110,17 @@ extern "C" ctta_status ctta_layernorm_bwd_add(const void* x, const void* dy, con
   return ctta_layernorm_bwd_ws(x, dy, dx_add, dx, rows, d, ld, gamma, eps, dgamma, dbeta, nullptr, 0, stream);
 }
 // `scratch` (>= ctta_layernorm_bwd_scratch_floats(rows, ld) floats, caller-owned, free again once the call's kernels have
-// run on `stream`): per-block partial sums of d gamma / d beta + a sliced fold (<= 32 atomics per address).  NULL / too
-// small: one atomic per block and column straight into dgamma / dbeta (same result up to the order of the fp32 atomics).
+// run on `stream`): per-block partial sums of d gamma / d beta, a sliced fold and a fold of the slices, all in a fixed
+// order: d gamma / d beta are bit-reproducible.  So they are where fewer than 16 blocks' worth of rows run as one block.
+// NULL / too small on a larger matrix: one atomic per block and column straight into dgamma / dbeta (same result up to the
+// order of the fp32 atomics).
 extern "C" ctta_status ctta_layernorm_bwd_ws(const void* x, const void* dy, const void* dx_add, void* dx, int64_t rows, int d,
                                              int ld, const float* gamma, float eps, float* dgamma, float* dbeta,
                                              float* scratch, size_t scratch_floats, void* stream) {
   CTTA_REQUIRE(x && dy && dx && gamma && dgamma && dbeta, "layernorm_bwd: null pointer (dgamma/dbeta must be zeroed or hold the running sum)");
   CTTA_REQUIRE(ld % 8 == 0 && d <= ld && ld <= 2048, "layernorm_bwd: d=%d ld=%d", d, ld);
-  const int rpb = ln_bwd_rows_per_block(rows);
+  int rpb = ln_bwd_rows_per_block(rows);
+  if (rows > 0 && cdiv64(rows, rpb) < 16) rpb = (int)rows;   // a short matrix is one block: one writer per column, no atomics race
   const dim3 grid((unsigned)cdiv64(rows, rpb));
   const size_t smem = (size_t)(ld <= 256 ? 8 : 4) * 2 * ld * sizeof(float);      // one copy per row group (<= 64 KB at ld = 2048)
   hipStream_t s = (hipStream_t)stream;
@@ -1108,9 +1134,15 @@ extern "C" ctta_status ctta_layernorm_bwd_ws(const void* x, const void* dy, cons
   if (part) {
     const int slices = (int)grid.x >= 32 * 8 ? 32 : ((int)grid.x + 7) / 8;          // >= 8 table rows per slice
     const int rps = ((int)grid.x + slices - 1) / slices;
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((d + 63) / 64, ((int)grid.x + rps - 1) / rps), dim3(256), 0, s, part,
-                       (int)grid.x, ld, d, rps, dgamma, dbeta);
+    const int n_slices = ((int)grid.x + rps - 1) / rps;   // <= LN_BWD_MAX_SLICES
+    float* slice_sums = n_slices > 1 ? part + (size_t)grid.x * 2 * ld : nullptr;
+    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((d + 63) / 64, n_slices), dim3(256), 0, s, part, (int)grid.x, ld, d, rps, dgamma,
+                       dbeta, slice_sums);
     CTTA_LAUNCH_CHECK();
+    if (slice_sums) {
+      hipLaunchKernelGGL(ln_bwd_final_kernel, dim3((d + 255) / 256), dim3(256), 0, s, slice_sums, n_slices, ld, d, dgamma, dbeta);
+      CTTA_LAUNCH_CHECK();
+    }
   }
   return CTTA_OK;
 }
@@ -1331,20 +1363,25 @@ extern "C" ctta_status ctta_softmax_bwd_rows(const void* p, const float* dp, int
 // ------------------------------------------------------------------------------ fp32 embedding-MLP backward
 // y = x W^T + b (W [N][K]);  given dy [M][N]:  dx[m][k] = sum_n dy[m][n] W[n][k] (* silu'(xpre) when xpre given),
 // dW[n][k] (+)= sum_m dy[m][n] x[m][k], db[n] (+)= sum_m dy[m][n]
-// grid (K/64, M, n-chunks): 64 k-columns x 4 n-lanes per block, partial sums land with one atomicAdd per (m, k)
-__global__ __launch_bounds__(256) void linear_f32_bwd_dx_kernel(const float* __restrict__ dy, int ldy,
-                                                                const float* __restrict__ w, float* __restrict__ dx, int N,
-                                                                int K, int n_chunk) {
-  __shared__ float red[4][64];
+// grid (K/64, M): 64 k-columns x 16 n-lanes per block; the n-lanes' sums meet in LDS and are added in lane order by the one
+// thread that owns (m, k) -- no float atomics, so d emb and everything behind it is bit-reproducible
+__global__ __launch_bounds__(1024) void linear_f32_bwd_dx_kernel(const float* __restrict__ dy, int ldy,
+                                                                 const float* __restrict__ w, float* __restrict__ dx, int N,
+                                                                 int K) {
+  __shared__ float red[16][64];
   const int kk = threadIdx.x & 63, part = threadIdx.x >> 6;
   const int k = blockIdx.x * 64 + kk, m = blockIdx.y;
-  const int n0 = blockIdx.z * n_chunk, n1 = min(N, n0 + n_chunk);
   float acc = 0.f;
   if (k < K)
-    for (int n = n0 + part; n < n1; n += 4) acc += dy[(size_t)m * ldy + n] * w[(size_t)n * K + k];
+    for (int n = part; n < N; n += 16) acc += dy[(size_t)m * ldy + n] * w[(size_t)n * K + k];
   red[part][kk] = acc;
   __syncthreads();
-  if (part == 0 && k < K) atomicAdd(&dx[(size_t)m * K + k], red[0][kk] + red[1][kk] + red[2][kk] + red[3][kk]);
+  if (part == 0 && k < K) {
+    float t = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) t += red[q][kk];
+    dx[(size_t)m * K + k] += t;
+  }
 }
 __global__ void silu_grad_scale_kernel(float* __restrict__ dx, const float* __restrict__ xpre, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1376,11 +1413,7 @@ extern "C" ctta_status ctta_linear_f32_bwd(const float* x, const float* w, const
   if (dx) {
     CTTA_REQUIRE(!(accumulate_dx && xpre_silu), "linear_f32_bwd: accumulate_dx with a SiLU pre-activation is not supported");
     if (!accumulate_dx) CTTA_CHECK_HIP(ctta_zero_async(dx, (size_t)m * k * sizeof(float), s));
-    int chunks = (n + 255) / 256;
-    if (chunks > 64) chunks = 64;
-    const int n_chunk = (n + chunks - 1) / chunks;
-    hipLaunchKernelGGL(linear_f32_bwd_dx_kernel, dim3((k + 63) / 64, m, chunks), dim3(256), 0, s, dy, dy_ld, w, dx, n, k,
-                       n_chunk);
+    hipLaunchKernelGGL(linear_f32_bwd_dx_kernel, dim3((k + 63) / 64, m), dim3(1024), 0, s, dy, dy_ld, w, dx, n, k);
     CTTA_LAUNCH_CHECK();
     if (xpre_silu) {
       hipLaunchKernelGGL(silu_grad_scale_kernel, dim3((m * k + 255) / 256), dim3(256), 0, s, dx, xpre_silu, m * k);

@@ -157,6 +157,9 @@ struct WeightStore {
     int blocks = 0, lds_floats = 0;
   } rowc[2];
   std::vector<ctta_copy_seg> h_copy, h_copy_prev;
+  std::vector<ctta_copy_seg> h_acopy, h_acopy_prev;   // the adapter tensors' share of `copies` (run_adapters)
+  ctta_copy_seg* d_acopy = nullptr;
+  size_t d_acopy_cap = 0;
   ctta_pack_job* d_pack = nullptr;
   ctta_copy_seg* d_copy = nullptr;
   size_t d_pack_cap = 0, d_copy_cap = 0;
@@ -174,6 +177,8 @@ struct WeightStore {
     if (d_pack) (void)hipFree(d_pack);
     for (RowClass& c : rowc) { if (c.d) (void)hipFree(c.d); c.d = nullptr; c.cap = 0; }
     if (d_copy) (void)hipFree(d_copy);
+    if (d_acopy) (void)hipFree(d_acopy);
+    d_acopy = nullptr;
     if (d_tpose) (void)hipFree(d_tpose);
     arena.base = nullptr; d_pack = nullptr; d_copy = nullptr; d_tpose = nullptr;
   }
@@ -264,6 +269,32 @@ struct WeightStore {
     }
     for (auto& j : jobs) CTTA_TRY(j(wt, s));
     return CTTA_OK;
+  }
+
+  // The fp32 copies whose key names an adapter tensor ("_lora."), from a table of their own: what moves when only the
+  // adapters changed.  Nothing else of the store is touched; a key the table lacks fails with that key named.
+  ctta_status run_adapters(const WeightTable& wt, hipStream_t s) {
+    h_acopy.clear();
+    for (const CopySpec& c : copies) {
+      if (c.key.find("_lora.") == std::string::npos) continue;
+      const ctta_tensor* t;
+      CTTA_TRY(find_checked(wt, c.key, &t));
+      if (tensor_numel(t) != c.numel) {
+        ctta_set_error("size mismatch for '%s': %lld elements, expected %lld", c.key.c_str(),
+                       (long long)tensor_numel(t), (long long)c.numel);
+        return CTTA_ERR_INVALID;
+      }
+      for (int off = 0; off < c.count; off += CTTA_COPY_ELEMS_PER_BLOCK) {
+        ctta_copy_seg g;
+        memset(&g, 0, sizeof(g));
+        g.src = t->data + c.src_start + off; g.dst = c.dst + off;
+        g.count = c.count - off < CTTA_COPY_ELEMS_PER_BLOCK ? c.count - off : CTTA_COPY_ELEMS_PER_BLOCK;
+        h_acopy.push_back(g);
+      }
+    }
+    if (h_acopy.empty()) { ctta_set_error("the handle has no adapter tensors"); return CTTA_ERR_INVALID; }
+    CTTA_TRY(sync_table(h_acopy, h_acopy_prev, (void**)&d_acopy, &d_acopy_cap, sizeof(ctta_copy_seg)));
+    return ctta_copy_segments_multi(d_acopy, (int)h_acopy.size(), s);
   }
 
   // dst[c][r] = src[r][c] (r < rows, c < cols), columns [rows, wcols) of each dst row zero; runs after the packs

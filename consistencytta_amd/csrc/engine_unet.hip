@@ -141,6 +141,12 @@ struct ctta_unet : EngineBase {
   float *temb_w = nullptr, *temb_b = nullptr;
   int temb_dim = 0, temb_total = 0, cin_pad = 0, xp = 0;
   int lora_r = 0;   // rank of the attention-projection adapters; 0: the weight table named none, and no launch differs
+  // ctta_unet_set_lora: which passes take the fused site kernels (lora.hip) where those take the shapes -- bit 0 the
+  // backward groups, bit 1 the forward groups -- and the adapter strength y = W x + lora_scale * up(down(x)); read by the
+  // next forward, whose values its backward uses (ts below).  The forward groups are off by default: ctta_lora_sites_fwd
+  // measured slower than the launches it replaces (profiles/lora_step.txt).
+  int lora_fused = 1;
+  float lora_scale = 1.0f;
   // Text cache: the cross-attention K / V^T projections of the text states (32 small GEMMs per forward) live in
   // persistent buffers; a caller that queries the same handle again with the SAME text states and mask (the second CFG
   // teacher query of a distillation step, every query of the Heun teacher loop) says so with ctta_unet_reuse_text and
@@ -159,6 +165,8 @@ struct ctta_unet : EngineBase {
                 *g_h1 = nullptr, *emb = nullptr, *emb_silu = nullptr;
     const bf16_t *enc_bf = nullptr, *xin = nullptr, *h_last = nullptr, *a_out = nullptr;
     const float *mask_bias = nullptr, *st_out = nullptr;
+    int lora_fused = 1;
+    float lora_scale = 1.0f;
   } ts;
   WgradSide wg;   // the weight-gradient side stream and its scratch slots (engine_backward.h)
   struct BackwardState {   // between ctta_unet_backward_begin / _next calls
@@ -178,6 +186,8 @@ struct UCtx : GradCtx {
   const bf16_t* enc_bf;
   const float* mask_bias;
   bool train = false;
+  bool lora_fused = false;   // the forward groups (bit 1 of the handle's setting)
+  float lora_scale = 1.0f;
 };
 
 static ctta_status make_resnet(ctta_unet* U, const std::string& p, int cin, int cout, Resnet* R) {
@@ -381,18 +391,50 @@ static ctta_status run_attention(UCtx& c, const bf16_t* q, int q_ld, const bf16_
   return CTTA_OK;
 }
 
-// The adapter term of one site, behind its base launch: d = x a^T (kept by the training forward), then y += d b^T, or the
-// same into the transposed V^T [batch][hp][vt_ld] where `vt_tokens` > 0.  Everything comes from the arena.
-static ctta_status lora_forward(UCtx& c, LoraSite& S, const bf16_t* x, int ldx, int64_t rows, bf16_t* y, int ldy,
-                                int vt_tokens = 0) {
+// The adapter term of one site, behind its base launch: d = x a^T (kept by the training forward), then y += scale * d b^T,
+// or the same into the transposed V^T [batch][hp][vt_ld] where `vt_tokens` > 0.  Everything comes from the arena.
+struct LoraDst { LoraSite* S; bf16_t* y; int ldy; int vt_tokens; };
+
+static ctta_status lora_forward_one(UCtx& c, const LoraDst& D, const bf16_t* x, int ldx, int64_t rows, float* d) {
   const int r = c.U->lora_r;
-  float* d = c.arena->get<float>((size_t)rows * r); ALLOC_OR_FAIL(d);
+  LoraSite& S = *D.S;
   RUN(c, ctta_lora_down(x, ldx, rows, S.k_pad, S.a, 0, r, d, c.stream));
-  if (vt_tokens > 0)
-    RUN(c, ctta_lora_up_add_t(y, ldy, (int64_t)S.n_pad * ldy, c.B, vt_tokens, S.n_pad, d, vt_tokens, S.b, r, 1.0f, c.stream));
+  if (D.vt_tokens > 0)
+    RUN(c, ctta_lora_up_add_t(D.y, D.ldy, (int64_t)S.n_pad * D.ldy, c.B, D.vt_tokens, S.n_pad, d, D.vt_tokens, S.b, r, c.lora_scale,
+                              c.stream));
   else
-    RUN(c, ctta_lora_up_add(y, ldy, rows, S.n_pad, d, S.b, 0, r, 1.0f, c.stream));
-  if (c.train) S.d = d;
+    RUN(c, ctta_lora_up_add(D.y, D.ldy, rows, S.n_pad, d, S.b, 0, r, c.lora_scale, c.stream));
+  return CTTA_OK;
+}
+
+// One to three sites on one input: ONE ctta_lora_sites_fwd launch where the fused kernels take the shapes (rank <= 4; a
+// V^T destination of 8 | tokens), the per-site launches otherwise -- a V^T site the fused kernel refuses (always the last of
+// its group) leaves the group and runs alone.  Either route allocates the same d buffers, and the values are bit-identical.
+static ctta_status lora_forward(UCtx& c, const LoraDst* dst, int n, const bf16_t* x, int ldx, int64_t rows) {
+  const int r = c.U->lora_r;
+  float* d[3];
+  int np[3];
+  for (int i = 0; i < n; ++i) {
+    d[i] = c.arena->get<float>((size_t)rows * r); ALLOC_OR_FAIL(d[i]);
+    if (c.train) dst[i].S->d = d[i];
+    np[i] = dst[i].S->n_pad;
+  }
+  const int k_pad = dst[0].S->k_pad;
+  int nf = 0;   // sites [0, nf) go through the fused launch
+  if (c.lora_fused) {
+    const LoraDst& T = dst[n - 1];
+    if (ctta_lora_sites_supported(k_pad, np, n, r, T.vt_tokens, T.ldy, (int64_t)T.S->n_pad * T.ldy)) nf = n;
+    else if (n > 1 && T.vt_tokens > 0 && ctta_lora_sites_supported(k_pad, np, n - 1, r, 0, 0, 0)) nf = n - 1;
+  }
+  if (nf > 0) {
+    ctta_lora_fwd_site fs[3];
+    for (int i = 0; i < nf; ++i) {
+      LoraSite& S = *dst[i].S;
+      fs[i] = {S.a, S.b, dst[i].y, d[i], dst[i].ldy, S.n_pad, dst[i].vt_tokens, (int64_t)S.n_pad * dst[i].ldy};
+    }
+    RUN(c, ctta_lora_sites_fwd(x, ldx, rows, k_pad, r, c.lora_scale, fs, nf, c.stream));
+  }
+  for (int i = nf; i < n; ++i) CTTA_TRY(lora_forward_one(c, dst[i], x, ldx, rows, d[i]));
   return CTTA_OK;
 }
 
@@ -414,19 +456,18 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
   // --- self-attention
   bf16_t* qk = A.get<bf16_t>(M * 2 * hp); ALLOC_OR_FAIL(qk);
   CTTA_TRY(run_linear(c, T.qk1, n, cp, M, qk, 2 * hp, nullptr, 0));
-  if (lora) {   // the fused [q | k] GEMM stays one launch; the adapters address their halves through ldy = 2 * hp
-    CTTA_TRY(lora_forward(c, T.lq1, n, cp, M, qk, 2 * hp));
-    CTTA_TRY(lora_forward(c, T.lk1, n, cp, M, qk + hp, 2 * hp));
-  }
   const int vt_ld = round_up(N, 8);
   bf16_t* vt = A.get<bf16_t>((size_t)c.B * hp * vt_ld); ALLOC_OR_FAIL(vt);
   CTTA_TRY(run_vt(c, T.v1, n, c.B, N, N, vt, vt_ld));
-  if (lora) CTTA_TRY(lora_forward(c, T.lv1, n, cp, M, vt, vt_ld, N));
+  if (lora) {   // q, k, v read n once; the [q | k] buffer is addressed by halves through ldy = 2 * hp
+    const LoraDst g1[3] = {{&T.lq1, qk, 2 * hp, 0}, {&T.lk1, qk + hp, 2 * hp, 0}, {&T.lv1, vt, vt_ld, N}};
+    CTTA_TRY(lora_forward(c, g1, 3, n, cp, M));
+  }
   bf16_t* att = A.get<bf16_t>(M * hp); ALLOC_OR_FAIL(att);
   CTTA_TRY(run_attention(c, qk, 2 * hp, qk + hp, 2 * hp, N, vt, vt_ld, nullptr, att, hp, T.heads, N, N, T.dh, &T.sv.lse1));
   bf16_t* s1 = A.get<bf16_t>(M * cp); ALLOC_OR_FAIL(s1);
   CTTA_TRY(run_linear(c, T.out1, att, hp, M, s1, cp, s0, cp));
-  if (lora) CTTA_TRY(lora_forward(c, T.lo1, att, hp, M, s1, cp));
+  if (lora) { const LoraDst g = {&T.lo1, s1, cp, 0}; CTTA_TRY(lora_forward(c, &g, 1, att, hp, M)); }
   // --- cross-attention against the text states
   bf16_t* const n1 = n;
   bf16_t* const att1 = att;
@@ -438,7 +479,7 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
   bf16_t* const n2 = n;
   bf16_t* q2 = A.get<bf16_t>(M * hp); ALLOC_OR_FAIL(q2);
   CTTA_TRY(run_linear(c, T.q2, n, cp, M, q2, hp, nullptr, 0));
-  if (lora) CTTA_TRY(lora_forward(c, T.lq2, n, cp, M, q2, hp));
+  if (lora) { const LoraDst g = {&T.lq2, q2, hp, 0}; CTTA_TRY(lora_forward(c, &g, 1, n, cp, M)); }
   bf16_t* k2 = T.k2c;
   bf16_t* vt2 = T.vt2c;
   if (!k2 || c.dry) {   // sizing pass / no text cache: arena buffers
@@ -449,8 +490,8 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
     CTTA_TRY(run_linear(c, T.k2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp, k2, hp, nullptr, 0));
     CTTA_TRY(run_vt(c, T.v2, c.enc_bf, c.B, c.Lp, c.Lp, vt2, c.Lp));
     if (lora) {   // into the text cache where there is one: it holds K / V^T with the adapter term
-      CTTA_TRY(lora_forward(c, T.lk2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp, k2, hp));
-      CTTA_TRY(lora_forward(c, T.lv2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp, vt2, c.Lp, c.Lp));
+      const LoraDst g2[2] = {{&T.lk2, k2, hp, 0}, {&T.lv2, vt2, c.Lp, c.Lp}};
+      CTTA_TRY(lora_forward(c, g2, 2, c.enc_bf, c.U->xp, (int64_t)c.B * c.Lp));
     }
   }
   CTTA_TRY(run_attention(c, q2, hp, k2, hp, c.Lp, vt2, c.Lp, c.mask_bias, att, hp, T.heads, N, c.L, T.dh, &T.sv.lse2));
@@ -464,7 +505,7 @@ static ctta_status run_transformer(UCtx& c, Transformer& T, const bf16_t* x, int
   const bool ffn_front = ffn_fused && T.front_stream && !lora;
   if (!ffn_front) {
     CTTA_TRY(run_linear(c, T.out2, att, hp, M, s2, cp, s1, cp));
-    if (lora) CTTA_TRY(lora_forward(c, T.lo2, att, hp, M, s2, cp));
+    if (lora) { const LoraDst g = {&T.lo2, s2, cp, 0}; CTTA_TRY(lora_forward(c, &g, 1, att, hp, M)); }
     // --- GEGLU feed-forward
     if (c.train) { n = A.get<bf16_t>(M * cp); ALLOC_OR_FAIL(n); }
     RUN(c, ctta_layernorm(s2, n, M, T.inner, cp, T.ln3.gamma, T.ln3.beta, 1e-5f, c.stream));
@@ -537,6 +578,7 @@ static ctta_status unet_forward_impl(ctta_unet* U, bool dry, const float* sample
   U->tape.clear();
   U->bind(c, stream, dry, cfg.debug_taps != 0, cfg.norm_num_groups);
   c.U = U; c.B = B; c.L = L; c.Lp = round_up(L, 8);
+  c.lora_fused = (U->lora_fused & 2) != 0; c.lora_scale = U->lora_scale;
   c.reuse_text = !dry && !train && U->tc_reuse_next && U->tc_valid && U->tc_base && U->tc_B == B && U->tc_L == L;
   U->tc_reuse_next = false;
   // a forward that re-projects the text states overwrites the cache as it goes: the cache is valid again only when this
@@ -732,6 +774,7 @@ static ctta_status unet_forward_impl(ctta_unet* U, bool dry, const float* sample
   if (train) {
     U->ts.h_last = h; U->ts.a_out = a; U->ts.st_out = st_out;
     U->ts.B = B; U->ts.L = L; U->ts.Lp = c.Lp; U->ts.n_skips = n_skips; U->ts.arena_off = A.off;
+    U->ts.lora_fused = U->lora_fused; U->ts.lora_scale = U->lora_scale;
     U->ts.valid = !dry;
   }
   if (gn_need) *gn_need = c.gn_need;
@@ -994,6 +1037,36 @@ extern "C" ctta_status ctta_unet_load_weights(ctta_unet* U, const ctta_tensor* w
   CTTA_REQUIRE(U && weights, "unet_load_weights: null pointer");
   U->tc_valid = false;   // the cached K / V^T were projected with the old weights
   return U->load_weights(weights, n_weights, (hipStream_t)stream);
+}
+
+// Re-packs the adapter tensors alone: the fp32 copies make_lora_site registered (keys with "_lora."); every base pack stays.
+extern "C" ctta_status ctta_unet_load_adapters(ctta_unet* U, const ctta_tensor* weights, int n_weights, void* stream) {
+  CTTA_REQUIRE(U && weights, "unet_load_adapters: null pointer");
+  CTTA_REQUIRE(U->lora_r > 0, "unet_load_adapters: the handle has no adapters (its weight table named none at creation)");
+  WeightTable wt;
+  wt.map.clear();
+  for (int i = 0; i < n_weights; ++i) {
+    const char* nm = weights[i].name;
+    if (!nm || !strstr(nm, "_lora.")) continue;
+    const size_t len = strlen(nm);
+    int r = U->lora_r;
+    if (weights[i].ndim == 2 && len > 11 && !strcmp(nm + len - 11, "down.weight")) r = (int)weights[i].shape[0];
+    else if (weights[i].ndim == 2 && len > 9 && !strcmp(nm + len - 9, "up.weight")) r = (int)weights[i].shape[1];
+    CTTA_REQUIRE(r == U->lora_r, "unet_load_adapters: '%s' has rank %d, the handle's adapters have rank %d", nm, r, U->lora_r);
+    wt.map[nm] = &weights[i];
+  }
+  U->tc_valid = false;   // the cached K / V^T hold the old adapters' term
+  return U->store.run_adapters(wt, (hipStream_t)stream);
+}
+
+extern "C" ctta_status ctta_unet_set_lora(ctta_unet* U, int fused, float scale) {
+  CTTA_REQUIRE(U, "unet_set_lora: null handle");
+  CTTA_REQUIRE(scale == scale && scale - scale == 0.f, "unet_set_lora: scale must be finite");
+  CTTA_REQUIRE(fused >= 0 && fused <= 3, "unet_set_lora: fused=%d (bit 0: backward groups, bit 1: forward groups)", fused);
+  if (scale != U->lora_scale) U->tc_valid = false;   // the cached K / V^T hold scale * the adapter term
+  U->lora_fused = fused;
+  U->lora_scale = scale;
+  return CTTA_OK;
 }
 
 extern "C" ctta_status ctta_unet_reuse_text(ctta_unet* U, int reuse) {

@@ -66,38 +66,78 @@ static ctta_status ln_backward(BCtx& c, const LNLayer& l, const bf16_t* x, const
   return CTTA_OK;
 }
 
-// Adapter backward of one projection site y = W x + up(down(x)), behind the base layer's own data gradient:
-//   dD = dY B,  dB += dY^T D,  dA += dD^T X,  dX += dD A  (dx NULL: the input carries no gradient -- the text states).
-// The parameter gradients are formed when the gradient table names the site's two tensors.  All launches run on the main
-// stream out of the handle's arena.
-static ctta_status lora_backward(BCtx& c, LoraSite& S, const bf16_t* x, int ldx, const bf16_t* dy, int lddy, int64_t rows,
-                                 bf16_t* dx, int lddx) {
+// Adapter backward of one to three projection sites y = W x + scale * up(down(x)) on ONE input x, behind the base layers' own
+// data gradients:  dD = dY B,  dB += scale dY^T D,  dA += scale dD^T X,  dX += scale dD A  (dx NULL: the input carries no
+// gradient -- the text states); dD stays unscaled.  The parameter gradients are formed when the gradient table names the
+// site's two tensors.  Where the fused kernels take the shapes (ctta_lora_sites_supported) the group is ONE
+// ctta_lora_sites_bwd call -- one read-modify-write of dx with the per-site launches' rounding sequence, so every data
+// gradient downstream keeps its bits; otherwise each site runs down + 2 x wgrad + up_add.  All launches run on the main
+// stream out of ONE arena block whose size covers both routes (the route may change between the sizing pass and a call).
+struct LoraGrad { LoraSite* S; const bf16_t* dy; int lddy; };
+
+static ctta_status lora_backward(BCtx& c, const LoraGrad* sites, int n, const bf16_t* x, int ldx, int64_t rows, bf16_t* dx,
+                                 int lddx) {
   const int r = c.U->lora_r;
+  const float scale = c.U->ts.lora_scale;
   Arena& A = *c.arena;
-  float *ga = nullptr, *gb = nullptr;
-  bool want = c.dry;
-  if (!c.dry) {
-    auto ia = c.grads->map.find(S.key + "down.weight"), ib = c.grads->map.find(S.key + "up.weight");
-    const bool ha = ia != c.grads->map.end() && ia->second, hb = ib != c.grads->map.end() && ib->second;
-    if (ha != hb) {
-      ctta_set_error("%s: no gradient tensor for '%s%s'", c.who, S.key.c_str(), ha ? "up.weight" : "down.weight");
-      return CTTA_ERR_MISSING_KEY;
+  float *ga[3] = {nullptr, nullptr, nullptr}, *gb[3] = {nullptr, nullptr, nullptr};
+  bool want[3], any = dx != nullptr;
+  int np[3];
+  for (int i = 0; i < n; ++i) {
+    LoraSite& S = *sites[i].S;
+    want[i] = c.dry;
+    if (!c.dry) {
+      auto ia = c.grads->map.find(S.key + "down.weight"), ib = c.grads->map.find(S.key + "up.weight");
+      const bool ha = ia != c.grads->map.end() && ia->second, hb = ib != c.grads->map.end() && ib->second;
+      if (ha != hb) {
+        ctta_set_error("%s: no gradient tensor for '%s%s'", c.who, S.key.c_str(), ha ? "up.weight" : "down.weight");
+        return CTTA_ERR_MISSING_KEY;
+      }
+      want[i] = ha;
+      if (ha) { ga[i] = ia->second; gb[i] = ib->second; }
     }
-    want = ha;
-    if (want) { ga = ia->second; gb = ib->second; }
+    any = any || want[i];
+    np[i] = S.n_pad;
   }
-  if (!want && !dx) return CTTA_OK;
-  float* dd = A.get<float>((size_t)rows * r); ALLOC_OR_FAIL(dd);
-  RUN(c, ctta_lora_down(dy, lddy, rows, S.n_pad, S.b, 1, r, dd, c.stream));
-  if (want) {
+  if (!any) return CTTA_OK;
+  const int k_pad = sites[0].S->k_pad;
+  // per-site route: dD and the larger of the two partial tables per site, each rounded up to 64 floats
+  auto up64 = [](size_t v) { return (v + 63) / 64 * 64; };
+  size_t per_site = 0;
+  for (int i = 0; i < n; ++i) {
+    size_t nf = ctta_lora_wgrad_scratch_floats(rows, np[i], r);
+    const size_t nk = ctta_lora_wgrad_scratch_floats(rows, k_pad, r);
+    if (nk > nf) nf = nk;
+    per_site += up64((size_t)rows * r) + up64(nf);
+  }
+  const bool can_fuse = ctta_lora_sites_supported(k_pad, np, n, r, 0, 0, 0) != 0;
+  const size_t fused_floats = can_fuse ? ctta_lora_sites_bwd_scratch_floats(rows, k_pad, np[0], n, r) : 0;
+  float* block = A.get<float>(per_site > fused_floats ? per_site : fused_floats); ALLOC_OR_FAIL(block);
+  if (can_fuse && (c.U->ts.lora_fused & 1)) {
+    ctta_lora_bwd_site bs[3];
+    for (int i = 0; i < n; ++i) {
+      LoraSite& S = *sites[i].S;
+      bs[i] = {sites[i].dy, S.a, S.b, S.d, nullptr, ga[i], gb[i], S.kmap, S.nmap, (int64_t)S.k, 1, 1, (int64_t)r, sites[i].lddy, S.n_pad};
+    }
+    RUN(c, ctta_lora_sites_bwd(x, ldx, dx, lddx, rows, k_pad, r, scale, bs, n, block, c.stream));
+    return CTTA_OK;
+  }
+  float* q = block;
+  for (int i = 0; i < n; ++i) {
+    LoraSite& S = *sites[i].S;
+    if (!want[i] && !dx) continue;
+    float* dd = q; q += up64((size_t)rows * r);
+    float* part = q;
     size_t nf = ctta_lora_wgrad_scratch_floats(rows, S.n_pad, r);
     const size_t nk = ctta_lora_wgrad_scratch_floats(rows, S.k_pad, r);
-    if (nk > nf) nf = nk;
-    float* part = A.get<float>(nf); ALLOC_OR_FAIL(part);
-    RUN(c, ctta_lora_wgrad(S.d, dy, lddy, rows, S.n_pad, r, 1.0f, gb, 1, r, S.nmap, part, c.stream));
-    RUN(c, ctta_lora_wgrad(dd, x, ldx, rows, S.k_pad, r, 1.0f, ga, S.k, 1, S.kmap, part, c.stream));
+    q += up64(nk > nf ? nk : nf);
+    RUN(c, ctta_lora_down(sites[i].dy, sites[i].lddy, rows, S.n_pad, S.b, 1, r, dd, c.stream));
+    if (want[i]) {
+      RUN(c, ctta_lora_wgrad(S.d, sites[i].dy, sites[i].lddy, rows, S.n_pad, r, scale, gb[i], 1, r, S.nmap, part, c.stream));
+      RUN(c, ctta_lora_wgrad(dd, x, ldx, rows, S.k_pad, r, scale, ga[i], S.k, 1, S.kmap, part, c.stream));
+    }
+    if (dx) RUN(c, ctta_lora_up_add(dx, lddx, rows, S.k_pad, dd, S.a, 1, r, scale, c.stream));
   }
-  if (dx) RUN(c, ctta_lora_up_add(dx, lddx, rows, S.k_pad, dd, S.a, 1, r, 1.0f, c.stream));
   return CTTA_OK;
 }
 
@@ -194,7 +234,7 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     const int Lp = c.Lp;
     bf16_t* datt = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(datt);
     CTTA_TRY(linear_dgrad(c, T.t_out2.d, ds, cp, cp, M, datt, hp, hp, false));
-    if (lora) CTTA_TRY(lora_backward(c, T.lo2, S.att2, hp, ds, cp, M, datt, hp));
+    if (lora) { const LoraGrad g = {&T.lo2, ds, cp}; CTTA_TRY(lora_backward(c, &g, 1, S.att2, hp, M, datt, hp)); }
     CTTA_TRY(linear_wgrad(c, T.t_out2.m, nullptr, S.att2, hp, M, ds, cp));
     bf16_t* dq = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(dq);
     const size_t kv = (size_t)c.B * Lp * hp;
@@ -209,9 +249,10 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     bf16_t* dn = A.get<bf16_t>((size_t)M * cp); ALLOC_OR_FAIL(dn);
     CTTA_TRY(linear_dgrad(c, T.t_q2.d, dq, hp, hp, M, dn, cp, cp, false));
     if (lora) {   // dn has its one owner (the line above) before the adapter adds into it; the text states take no gradient
-      CTTA_TRY(lora_backward(c, T.lq2, S.n2, cp, dq, hp, M, dn, cp));
-      CTTA_TRY(lora_backward(c, T.lk2, c.enc_bf, c.U->xp, dk, hp, (int64_t)c.B * Lp, nullptr, 0));
-      CTTA_TRY(lora_backward(c, T.lv2, c.enc_bf, c.U->xp, dv, hp, (int64_t)c.B * Lp, nullptr, 0));
+      const LoraGrad gq = {&T.lq2, dq, hp};
+      CTTA_TRY(lora_backward(c, &gq, 1, S.n2, cp, M, dn, cp));
+      const LoraGrad gkv[2] = {{&T.lk2, dk, hp}, {&T.lv2, dv, hp}};
+      CTTA_TRY(lora_backward(c, gkv, 2, c.enc_bf, c.U->xp, (int64_t)c.B * Lp, nullptr, 0));
     }
     CTTA_TRY(linear_wgrad(c, T.t_q2.m, nullptr, S.n2, cp, M, dq, hp));
     CTTA_TRY(linear_wgrad(c, T.t_k2.m, nullptr, c.enc_bf, c.U->xp, (int64_t)c.B * Lp, dk, hp));
@@ -224,7 +265,7 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     const size_t m2 = A.mark();
     bf16_t* datt = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(datt);
     CTTA_TRY(linear_dgrad(c, T.t_out1.d, ds, cp, cp, M, datt, hp, hp, false));
-    if (lora) CTTA_TRY(lora_backward(c, T.lo1, S.att1, hp, ds, cp, M, datt, hp));
+    if (lora) { const LoraGrad g = {&T.lo1, ds, cp}; CTTA_TRY(lora_backward(c, &g, 1, S.att1, hp, M, datt, hp)); }
     CTTA_TRY(linear_wgrad(c, T.t_out1.m, nullptr, S.att1, hp, M, ds, cp));
     bf16_t* dqk = A.get<bf16_t>((size_t)M * 2 * hp); ALLOC_OR_FAIL(dqk);
     bf16_t* dv = A.get<bf16_t>((size_t)M * hp); ALLOC_OR_FAIL(dv);
@@ -234,10 +275,9 @@ static ctta_status bwd_transformer(BCtx& c, Transformer& T, const bf16_t* dout, 
     CTTA_TRY(linear_dgrad(c, T.t_q1.d, dqk, hp, 2 * hp, M, dn, cp, cp, false));
     CTTA_TRY(linear_dgrad(c, T.t_k1.d, dqk + hp, hp, 2 * hp, M, dn, cp, cp, true));
     CTTA_TRY(linear_dgrad(c, T.t_v1.d, dv, hp, hp, M, dn, cp, cp, true));
-    if (lora) {   // behind the owner (q, accumulate = false) and the two accumulating data gradients
-      CTTA_TRY(lora_backward(c, T.lq1, S.n1, cp, dqk, 2 * hp, M, dn, cp));
-      CTTA_TRY(lora_backward(c, T.lk1, S.n1, cp, dqk + hp, 2 * hp, M, dn, cp));
-      CTTA_TRY(lora_backward(c, T.lv1, S.n1, cp, dv, hp, M, dn, cp));
+    if (lora) {   // behind the owner (q, accumulate = false) and the two accumulating data gradients: one write of dn
+      const LoraGrad g1[3] = {{&T.lq1, dqk, 2 * hp}, {&T.lk1, dqk + hp, 2 * hp}, {&T.lv1, dv, hp}};
+      CTTA_TRY(lora_backward(c, g1, 3, S.n1, cp, M, dn, cp));
     }
     CTTA_TRY(linear_wgrad(c, T.t_q1.m, &T.t_k1.m, S.n1, cp, M, dqk, 2 * hp));
     CTTA_TRY(linear_wgrad(c, T.t_v1.m, nullptr, S.n1, cp, M, dv, hp));

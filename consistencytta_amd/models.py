@@ -90,8 +90,7 @@ def optimizer_tail(source_model, shadow_models, decay_consts, optimizer, lr_sche
         optimizer.step_zero_ema(flats[1:], decay_consts, grad_scale=grad_scale, do_step=do_step)
         if do_step and lr_scheduler is not None:
             lr_scheduler.step()
-        for m in shadow_models:
-            m.mark_weights_changed()
+        _mark_shadows_changed(source_model, shadow_models)
         return
     if do_step:
         optimizer.step(grad_scale=grad_scale)
@@ -99,6 +98,16 @@ def optimizer_tail(source_model, shadow_models, decay_consts, optimizer, lr_sche
             lr_scheduler.step()
     optimizer.zero_grad()
     do_ema_update(source_model, shadow_models, decay_consts)
+
+
+def _mark_shadows_changed(source_model, shadow_models):
+    """after a fused EMA pass: with LoRA adapters it walked the adapter prefix alone, so the shadows' handles re-pack their
+    adapters and keep every base pack"""
+    for m in shadow_models:
+        if getattr(source_model, "lora_rank", 0) and getattr(m, "lora_rank", 0):
+            m.mark_weights_changed(adapters_only=True)
+        else:
+            m.mark_weights_changed()
 
 
 def do_ema_update(source_model, shadow_models, decay_consts):
@@ -119,8 +128,7 @@ def do_ema_update(source_model, shadow_models, decay_consts):
         n = source_model.n_trainable() if getattr(source_model, "lora_rank", 0) else flats[0].numel()
         with torch.cuda.device(flats[0].device):
             launch(flats[0], flats[1:], n)
-        for m in shadow_models:
-            m.mark_weights_changed()
+        _mark_shadows_changed(source_model, shadow_models)
 
     if _ema_steady(nets, flats, sig):
         for d in decay_consts:

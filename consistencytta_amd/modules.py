@@ -64,12 +64,28 @@ class _ParamTree(nn.Module):
         return self
 
     def _weights_version(self):
-        return sum(p._version for p in self.parameters()) + 1000003 * sum(
-            p.data_ptr() % 1000003 for p in self.parameters()) + 7 * getattr(self, "_manual_version", 0)
+        return sum(self._weights_versions())
 
-    def mark_weights_changed(self):
-        """Call after parameters were updated through raw pointers (fused AdamW / EMA kernels)."""
-        self._manual_version = getattr(self, "_manual_version", 0) + 1
+    def _weights_versions(self):
+        """(base part, adapter part): the adapter part covers the parameters whose key names a LoRA tensor (`_lora.`), so
+        a handle can tell "only the adapters moved" (re-pack them alone) from a change of the base."""
+        base = 7 * getattr(self, "_manual_version", 0)
+        adapters = 7 * getattr(self, "_manual_adapter_version", 0)
+        for k, p in self.named_parameters():
+            v = p._version + 1000003 * (p.data_ptr() % 1000003)
+            if "_lora." in k:
+                adapters += v
+            else:
+                base += v
+        return base, adapters
+
+    def mark_weights_changed(self, adapters_only=False):
+        """Call after parameters were updated through raw pointers (fused AdamW / EMA kernels).  `adapters_only`: the
+        pass walked the LoRA adapters alone (the trainable prefix of a module with `lora_rank`)."""
+        if adapters_only:
+            self._manual_adapter_version = getattr(self, "_manual_adapter_version", 0) + 1
+        else:
+            self._manual_version = getattr(self, "_manual_version", 0) + 1
 
     def flatten_parameters_(self):
         """Re-homes every parameter into ONE contiguous fp32 buffer (views keep names/shapes), so the
@@ -274,6 +290,10 @@ class _UNetBase(_ParamTree):
         self.debug_taps = False
         self.enable_training = False   # True: the native handle also carries the backward pass
         self.lora_rank = 0             # > 0: adapters at the attention projections (enable_lora_)
+        self.lora_scale = 1.0          # y = W x + lora_scale * up(down(x)); pushed to the handle before each call
+        # the fused site kernels where they take the shapes: True (= 1) in the backward groups, 3 in the forward groups too
+        # (measured slower than the launches they replace there, profiles/lora_step.txt), False: per-site launches everywhere
+        self.lora_fused = True
 
     # ---- LoRA (audio_distilled_model.py:116-145 -> diffusers LoRAAttnProcessor, attention_processor.py:508-613)
     def enable_lora_(self, rank=4, generator=None):
@@ -322,8 +342,9 @@ class _UNetBase(_ParamTree):
         return [k for k, _ in self.named_parameters() if "_lora." in k]
 
     def merge_lora_(self):
-        """Folds every adapter into its base weight, W += up @ down (fp32, in place), and drops the adapters: the module
-        is a plain U-Net again and serves at the plain U-Net's cost.  `requires_grad` stays as it is (all False)."""
+        """Folds every adapter into its base weight, W += lora_scale * up @ down (fp32, in place; the strength the module
+        serves with, 1.0 unless `lora_scale` was set), and drops the adapters: the module is a plain U-Net again and
+        serves at the plain U-Net's cost.  `requires_grad` stays as it is (all False)."""
         if not self.lora_rank:
             return self
         params = dict(self.named_parameters())
@@ -334,7 +355,7 @@ class _UNetBase(_ParamTree):
                 site = key[:-len("down.weight")]                        # "...attn1.processor.to_q_lora."
                 attn, layer = site.split("processor.")
                 wkey = attn + layer[:-len("_lora.")] + (".0.weight" if layer.startswith("to_out") else ".weight")
-                params[wkey].add_(params[site + "up.weight"] @ params[key])
+                params[wkey].add_(params[site + "up.weight"] @ params[key], alpha=float(self.lora_scale))
         for k, m in list(self.named_modules()):
             if "processor" in m._modules:
                 del m._modules["processor"]
@@ -389,7 +410,7 @@ class _UNetBase(_ParamTree):
         an extent change, max_batch does not.  Changed weights are re-packed into the SAME handle."""
         L_, e = N.lib(), self._engine
         key = (H, W, self.debug_taps, self.enable_training, self.device) + ((self.lora_rank,) if self.lora_rank else ())
-        ver = self._weights_version()
+        ver = self._weights_versions()
         if not e.fits((B, L), key, e.version):
             Bm = max(B, e.capacity[0]) if e.key and e.key[:2] == (H, W) else B
             Lm = max(L, e.capacity[1], 32) if e.key else max(L, 32)
@@ -398,8 +419,14 @@ class _UNetBase(_ParamTree):
             e.replace(lambda h: L_.ctta_unet_create(cfg, table, len(table), N.stream_ptr(), h), (Bm, Lm), key, ver,
                       self.device)
         elif ver != e.version:  # parameters changed (optimizer / EMA / load_state_dict)
-            table, keep = N.tensor_table(self._table())
-            N.check(L_.ctta_unet_load_weights(e.h, table, len(table), N.stream_ptr()))
+            if self.lora_rank and isinstance(e.version, tuple) and ver[0] == e.version[0]:
+                # only the adapters moved (a LoRA optimizer / EMA step, an adapter-only load_state_dict, a hot swap on a
+                # serving module): their 0.1 % of the parameters is re-packed, every base pack stays
+                table, keep = N.tensor_table(OrderedDict((k, v) for k, v in self._table().items() if "_lora." in k))
+                N.check(L_.ctta_unet_load_adapters(e.h, table, len(table), N.stream_ptr()))
+            else:
+                table, keep = N.tensor_table(self._table())
+                N.check(L_.ctta_unet_load_weights(e.h, table, len(table), N.stream_ptr()))
             e.version = ver
 
     @staticmethod
@@ -432,8 +459,19 @@ class _UNetBase(_ParamTree):
             return True
         return not torch.cuda.is_current_stream_capturing()
 
+    @staticmethod
+    def _call_lora_scale(cross_attention_kwargs):
+        """diffusers' `cross_attention_kwargs={"scale": s}` (LoRAAttnProcessor.__call__(..., scale=)): the adapter strength
+        of THIS call, or None.  Nothing else travels through that dict here."""
+        if not cross_attention_kwargs:
+            return None
+        unknown = sorted(k for k in cross_attention_kwargs if k != "scale")
+        if unknown:
+            raise NotImplementedError("cross_attention_kwargs %s: only 'scale' (the LoRA strength) is supported" % unknown)
+        return float(cross_attention_kwargs["scale"])
+
     def _forward(self, sample, timestep, guidance, encoder_hidden_states, encoder_attention_mask, train=False,
-                 reuse_text=None):
+                 reuse_text=None, lora_scale=None):
         if sample.ndim != 4 or sample.shape[1] != self._cfg["in_channels"]:
             raise ValueError("sample must be (batch, %d, height, width), got %s"
                              % (self._cfg["in_channels"], tuple(sample.shape)))
@@ -462,6 +500,9 @@ class _UNetBase(_ParamTree):
         fn = N.lib().ctta_unet_forward_train if train else N.lib().ctta_unet_forward
         self._text_key = None
         with torch.cuda.device(dev):
+            if self.lora_rank:   # a changed scale drops the handle's text cache (it holds the adapter term)
+                N.check(N.lib().ctta_unet_set_lora(self._h_unet, int(self.lora_fused),
+                                                   float(self.lora_scale if lora_scale is None else lora_scale)))
             if reuse:
                 N.check(N.lib().ctta_unet_reuse_text(self._h_unet, 1))
             N.check(fn(self._h_unet, N.ptr(x), N.ptr(t), N.ptr(g), N.ptr(enc), N.ptr(m), B, L, N.ptr(out),
@@ -585,7 +626,7 @@ class UNet2DConditionGuidedModel(_UNetBase):
             if v is not None:
                 raise NotImplementedError("%s is not used on the ConsistencyTTA path and is not supported" % name)
         out = self._forward(sample, timestep, guidance, encoder_hidden_states, encoder_attention_mask,
-                            reuse_text=kwargs.get("reuse_text"))
+                            reuse_text=kwargs.get("reuse_text"), lora_scale=self._call_lora_scale(cross_attention_kwargs))
         return UNet2DConditionOutput(sample=out) if return_dict else (out,)
 
 
@@ -599,7 +640,7 @@ class UNet2DConditionModel(_UNetBase):
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 encoder_attention_mask=None, return_dict=True, **kwargs):
         out = self._forward(sample, timestep, None, encoder_hidden_states, encoder_attention_mask,
-                            reuse_text=kwargs.get("reuse_text"))
+                            reuse_text=kwargs.get("reuse_text"), lora_scale=self._call_lora_scale(cross_attention_kwargs))
         return UNet2DConditionOutput(sample=out) if return_dict else (out,)
 
 

@@ -61,7 +61,14 @@ class FusedAdamW:
                                             N.ptr(self.exp_avg_sq), self.n, g["lr"], g["betas"][0], g["betas"][1],
                                             g["eps"], g["weight_decay"], self.step_count, float(grad_scale),
                                             N.stream_ptr()))
-        self.module.mark_weights_changed()
+        self._mark_changed()
+
+    def _mark_changed(self):
+        """with LoRA adapters the update walked the adapter prefix alone: the handle re-packs those and keeps every base pack"""
+        if getattr(self.module, "lora_rank", 0):
+            self.module.mark_weights_changed(adapters_only=True)
+        else:
+            self.module.mark_weights_changed()
 
     def can_fuse_tail(self, shadow_flats):
         """Whether `step_zero_ema` may replace step() + zero_grad() + the EMA launch: shadows with this optimizer's flat
@@ -95,7 +102,7 @@ class FusedAdamW:
                 float(decays[1]) if len(shadow_flats) > 1 else 0.0, 1 if do_step else 0, g["lr"], g["betas"][0], g["betas"][1],
                 g["eps"], g["weight_decay"], max(1, self.step_count), float(grad_scale), N.stream_ptr()))
         if do_step:
-            self.module.mark_weights_changed()
+            self._mark_changed()
 
     # checkpoint / resume (accelerator.save_state stores the optimizer state, train.py:497-505): the layout is
     # torch.optim.AdamW.state_dict() over `student_unet.parameters()` (tools/train_utils.py:38-39,59-63), so that

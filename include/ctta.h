@@ -94,16 +94,31 @@ typedef struct {
 typedef struct ctta_unet ctta_unet;
 
 /* LoRA: a weight table that names adapter tensors (`...attn{1,2}.processor.to_{q,k,v,out}_lora.{down,up}.weight`, diffusers
- * LoRAAttnProcessor) gives the handle adapters at every attention projection, y = W x + up(down(x)); the rank (1..16) is
- * read from their shapes, and a table that lacks one of an attention's eight tensors fails with that key named.
- * ctta_unet_load_weights repacks them with the rest.  In ctta_unet_backward*, a gradient table that names adapter tensors
- * only is the frozen-base mode: no base weight gradient is formed.  A handle without adapters runs what it always ran. */
+ * LoRAAttnProcessor) gives the handle adapters at every attention projection, y = W x + scale * up(down(x)); the rank
+ * (1..16) is read from their shapes, and a table that lacks one of an attention's eight tensors fails with that key named.
+ * The adapters are a separately reloadable part of the handle: ctta_unet_load_weights repacks them with the rest,
+ * ctta_unet_load_adapters repacks them alone (an optimizer / EMA step on the adapters, a swap of one adapter set for another
+ * on a serving handle).  `scale` and the choice of kernels are per-handle settings (ctta_unet_set_lora; defaults: the fused
+ * site kernels of csrc/lora.hip in the backward where they take the shapes -- rank <= 4 -- and scale 1).  In ctta_unet_backward*, a gradient
+ * table that names adapter tensors only is the frozen-base mode: no base weight gradient is formed.  A handle without
+ * adapters runs what it always ran. */
 ctta_status ctta_unet_create(const ctta_unet_config* cfg, const ctta_tensor* weights,
                              int n_weights, void* stream, ctta_unet** out);
 void ctta_unet_destroy(ctta_unet* h);
 /* Re-reads (re-packs) all weights from a new table, e.g. after an optimizer/EMA step. */
 ctta_status ctta_unet_load_weights(ctta_unet* h, const ctta_tensor* weights, int n_weights,
                                    void* stream);
+/* Re-packs the adapter tensors only: names without `_lora.` are ignored and every base pack stays as it is; the text cache
+ * is dropped (the cached K / V^T hold the adapter term).  Fails with the key named when one of an attention's eight
+ * tensors is missing, and when the handle has no adapters or a tensor's rank differs from the handle's. */
+ctta_status ctta_unet_load_adapters(ctta_unet* h, const ctta_tensor* weights, int n_weights, void* stream);
+/* Per-handle adapter settings, read by the next ctta_unet_forward / _forward_train (a backward uses the values of the
+ * forward_train it belongs to).  `fused` selects, per pass, one ctta_lora_sites_* launch per group of sites on one input
+ * where ctta_lora_sites_supported says so: bit 0 the backward groups, bit 1 the forward groups; 0: the per-site launches
+ * everywhere.  Forward and data gradients are bit-identical either way; the adapter weight gradients differ in their
+ * summation order only.  A change of `scale` drops the text cache.  Defaults (1, 1.0f): the fused backward measured 3.4x
+ * faster than its launches, the fused forward slower than its own (profiles/lora_step.txt), so it is opt-in (fused = 3). */
+ctta_status ctta_unet_set_lora(ctta_unet* h, int fused, float scale);
 /* sample (B,C,H,W) f32; timesteps (B) f32; guidance (B) f64 or NULL when !guided;
  * enc (B,L,X) f32; mask (B,L) u8 (1 = keep) or NULL; out (B,Cout,H,W) f32. */
 /* One-shot hint for the NEXT ctta_unet_forward / _forward_train on this handle: reuse != 0 promises that its
@@ -1009,15 +1024,17 @@ ctta_status ctta_groupnorm_bwd(const void* x, const void* dy, void* dx, int batc
                                const float* stats, const float* gamma, const float* beta, int silu,
                                int accumulate_dx, float* dgamma, float* dbeta, int accumulate_param,
                                float* scratch, void* stream);
-/* LayerNorm backward (statistics recomputed); dgamma/dbeta are ACCUMULATED into (atomics) */
+/* LayerNorm backward (statistics recomputed); dgamma/dbeta are ACCUMULATED into (one fp32 atomic per block and column; a
+   matrix of fewer than 16 blocks' worth of rows, <= 120, runs as one block and is bit-reproducible) */
 ctta_status ctta_layernorm_bwd(const void* x, const void* dy, void* dx, int64_t rows, int d, int ld,
                                const float* gamma, float eps, int accumulate_dx, float* dgamma, float* dbeta,
                                void* stream);
 /* dx = dx_add + dL/dx with a separate output (dx_add may be NULL, or equal dx = the in-place accumulate above) */
 ctta_status ctta_layernorm_bwd_add(const void* x, const void* dy, const void* dx_add, void* dx, int64_t rows, int d, int ld,
                                    const float* gamma, float eps, float* dgamma, float* dbeta, void* stream);
-/* The same with a CALLER-OWNED partial table for d gamma / d beta (per-block sums + a sliced fold instead of one atomic per
-   block and column); scratch may be NULL (atomics path).  The library holds no workspace of its own for this call. */
+/* The same with a CALLER-OWNED partial table for d gamma / d beta (per-block sums, a sliced fold and a fold of the slices,
+   all in a fixed order and without float atomics: two runs give the same bits); scratch may be NULL (atomics path).  The
+   library holds no workspace of its own for this call. */
 size_t ctta_layernorm_bwd_scratch_floats(int64_t rows, int ld);
 ctta_status ctta_layernorm_bwd_ws(const void* x, const void* dy, const void* dx_add, void* dx, int64_t rows, int d, int ld,
                                   const float* gamma, float eps, float* dgamma, float* dbeta, float* scratch,
@@ -1084,6 +1101,51 @@ ctta_status ctta_lora_up_add_t(void* yt, int ldt, int64_t batch_stride, int batc
 size_t ctta_lora_wgrad_scratch_floats(int64_t m, int k, int r);
 ctta_status ctta_lora_wgrad(const float* d, const void* x, int ldx, int64_t m, int k, int r, float scale, float* g,
                             int64_t g_stride_r, int64_t g_stride_k, const int32_t* col_map, float* scratch, void* stream);
+
+/* Fused forms for rank <= 4: one to three sites that share ONE input (q / k / v of a self-attention on its LayerNorm output,
+ * k / v of a cross-attention on the text states, or a single site).  Same layouts and padded-column contract as above; a is
+ * [r][k_pad], b is [n_pad][r].  Per site the results are BIT FOR BIT those of the per-site launches they replace (same lanes
+ * per row, same fold order, same fmaf chains, the same "store nothing where all eight sums are zero" rule).
+ *   sites_fwd : per site D = X A^T (stored to `d` when given), Y += scale * D B^T; X is read once per call.  A site with
+ *               tokens > 0 writes the transposed yt[batch][n_pad][tokens] (row stride ldy, batch stride batch_stride),
+ *               rows = batch * tokens, as ctta_lora_up_add_t does.
+ *   sites_bwd : per site dD = dY B (kept in `dd` when given, else in scratch); dX += scale * dD A over all sites in ONE
+ *               read-modify-write of dx (sites in order, rounded to bf16 after each: the bits of one ctta_lora_up_add per
+ *               site; dx NULL: the input takes no gradient); gb += scale * dY^T D and ga += scale * dD^T X where the site
+ *               gives both gradient tensors (strides and column maps as ctta_lora_wgrad takes them; `d` is the forward's D),
+ *               through per-slab partial sums in scratch and ONE fold launch, slabs in slab order: two runs give the same
+ *               bits, and into a non-zero G the result is fl(G + what a zeroed G receives).  dY and X are read once each.
+ * ctta_lora_sites_supported: 1 where the fused kernels take the shapes (pure host function): r in [1, 4], 1..3 sites of one
+ * n_pad, k_pad and n_pad multiples of 8 up to 1536, and for a transposed destination (vt_tokens > 0) tokens, row stride and
+ * batch stride multiples of 8.  Callers use the per-site launches otherwise. */
+typedef struct {
+  const float* a;
+  const float* b;
+  void* y;              /* bf16 destination */
+  float* d;             /* fp32 [rows][r] or NULL */
+  int ldy, n_pad;
+  int tokens;           /* > 0: transposed destination */
+  int64_t batch_stride;
+} ctta_lora_fwd_site;
+typedef struct {
+  const void* dy;       /* bf16 [rows][lddy] */
+  const float* a;
+  const float* b;
+  const float* d;       /* the forward's D; read when ga / gb are given */
+  float* dd;            /* fp32 [rows][r] or NULL */
+  float* ga;            /* both or neither */
+  float* gb;
+  const int32_t* k_map; /* ga's column map over k_pad (NULL: identity) */
+  const int32_t* n_map; /* gb's column map over n_pad */
+  int64_t ga_stride_r, ga_stride_k, gb_stride_r, gb_stride_k;
+  int lddy, n_pad;
+} ctta_lora_bwd_site;
+int ctta_lora_sites_supported(int k_pad, const int* n_pad, int n_sites, int r, int vt_tokens, int vt_ldt, int64_t vt_batch_stride);
+ctta_status ctta_lora_sites_fwd(const void* x, int ldx, int64_t rows, int k_pad, int r, float scale,
+                                const ctta_lora_fwd_site* sites, int n_sites, void* stream);
+size_t ctta_lora_sites_bwd_scratch_floats(int64_t rows, int k_pad, int n_pad, int n_sites, int r);
+ctta_status ctta_lora_sites_bwd(const void* x, int ldx, void* dx, int lddx, int64_t rows, int k_pad, int r, float scale,
+                                const ctta_lora_bwd_site* sites, int n_sites, float* scratch, void* stream);
 
 /* Opt-in launch profiler (bench.py's live roofline leg): when enabled, every conv_gemm (kind 0)
  * and attention (kind 1) launch is bracketed by hipEvents on its own stream.  collect() waits

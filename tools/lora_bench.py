@@ -1,14 +1,21 @@
 """What LoRA adapters cost and save at the project's sizes (light U-Net, latent 256 x 16), measured in ONE process on one
-box, every variant built and timed by the same lines and the plain path timed again at the end (drift of the box):
+box, every variant built and timed by the same lines; each adapter line runs as off / on / off with `lora_fused`, and the
+plain path is timed again at the end, so the drift of the box is visible:
 
-  forward  the inference forward at batch 32: plain U-Net / with rank-4 adapters / after merge_lora_() / plain again
-  step     the stage-1 `AudioGDM.train_step` at batch 9: full fine-tuning / LoRA / full fine-tuning again
+  forward  the inference forward at batch 32: plain U-Net / rank-4 adapters, per-site launches / fused site kernels /
+           per-site launches again / after merge_lora_()
+  step     the stage-1 `AudioGDM.train_step` at batch 9: full fine-tuning / LoRA with per-site launches and a full re-pack
+           of the handle after every optimizer step (what the code did before the adapter-only reload) / LoRA with the
+           fused kernels and the adapter-only reload / the first again / full fine-tuning again; and the two reloads alone
+  kernels  ctta_lora_sites_fwd / _bwd for the q / k / v group against the launches they replace, with the bytes each must
+           move and the floor those bytes make at the box's streaming rate (tools/stream_bench.py's EMA pass)
 
 Times are hipEvent brackets around `--steps` calls after `--warmup` calls of the same shapes; random weights.
 
-    python tools/lora_bench.py [--steps 10] [--warmup 3] [--out profiles/lora_step.txt]
+    python tools/lora_bench.py [--steps 10] [--warmup 3] [--out profiles/lora_step.txt]     (--out appends a dated section)
 """
 import argparse
+import datetime
 import os
 import socket
 import sys
@@ -17,6 +24,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 from consistencytta_amd import modules, spec  # noqa: E402
 from consistencytta_amd.models import AudioGDM  # noqa: E402
 
@@ -68,7 +76,10 @@ def forward_rows(a):
     rows = [("plain U-Net", event_ms(run, a.warmup, a.steps))]
     net.enable_lora_(4)
     randomise_up_(net, g)
-    rows.append(("rank-4 adapters", event_ms(run, a.warmup, a.steps)))
+    for name, fused in (("rank-4 adapters, per-site launches", False), ("rank-4 adapters, fused site kernels", True),
+                        ("rank-4 adapters, per-site launches, again", False)):
+        net.lora_fused = 3 if fused else False        # 3: the forward groups too (the default fuses the backward alone)
+        rows.append((name, event_ms(run, a.warmup, a.steps)))
     net.merge_lora_()
     rows.append(("after merge_lora_()", event_ms(run, a.warmup, a.steps)))
     rows.append(("after merge_lora_(), again", event_ms(run, a.warmup, a.steps)))
@@ -99,35 +110,95 @@ def step_ms(a, lora):
     P = {"embeds_cf": torch.cat([unc, enc]), "mask_cf": torch.cat([umask, mask]), "embeds": enc, "mask": mask}
     torch.manual_seed(100)
     losses = []
-    ms = event_ms(lambda: losses.append(m.train_step(z0, P, opt, None)), a.warmup, a.steps)
-    assert all(v == v for v in losses), "NaN loss"
     n_train, n_all = opt.n, opt.flat.numel()
+    stu = m.student_unet
+    rows = []
+    if not lora:
+        rows.append(("", event_ms(lambda: losses.append(m.train_step(z0, P, opt, None)), a.warmup, a.steps)))
+    else:
+        def step(full_reload):
+            losses.append(m.train_step(z0, P, opt, None))
+            if full_reload:                        # a base change: the next call re-packs all 560 M parameters
+                stu.mark_weights_changed()
+        for name, fused in ((", per-site launches + full reload", False), (", fused backward + adapter reload", True),
+                            (", fused forward and backward + adapter reload", 3),
+                            (", per-site launches + full reload, again", False)):
+            stu.lora_fused = fused
+            rows.append((name, event_ms(lambda: step(not fused), a.warmup, a.steps)))
+        # the two reloads alone, on the student's handle
+        from consistencytta_amd import _native as N
+        L = N.lib()
+        full, keep1 = N.tensor_table(stu._table())
+        ad, keep2 = N.tensor_table({k: v for k, v in stu._table().items() if "_lora." in k})
+        rows.append((": ctta_unet_load_weights alone", event_ms(
+            lambda: N.check(L.ctta_unet_load_weights(stu._h_unet, full, len(full), N.stream_ptr())), a.warmup, a.steps)))
+        rows.append((": ctta_unet_load_adapters alone", event_ms(
+            lambda: N.check(L.ctta_unet_load_adapters(stu._h_unet, ad, len(ad), N.stream_ptr())), a.warmup, a.steps)))
+    assert all(v == v for v in losses), "NaN loss"
     del m, opt
     torch.cuda.empty_cache()
-    return ms, n_train, n_all
+    return rows, n_train, n_all
+
+
+def stream_rate():
+    """bytes / us of the two-shadow EMA pass (tools/stream_bench.py: 20 B per element) at 64 M elements"""
+    from consistencytta_amd import _native as N
+    from stream_bench import timed
+    L = N.lib()
+    n = 64 * 1024 * 1024
+    p, sa, sb = (torch.randn(n, device=DEV) * 0.02 for _ in range(3))
+    fn = lambda: N.check(L.ctta_ema_update2(N.ptr(p), N.ptr(sa), 0.95, N.ptr(sb), 0.999, n, N.stream_ptr()))  # noqa: E731
+    fn()
+    torch.cuda.synchronize()
+    return 20.0 * n / (timed(fn) * 1e3)
 
 
 def kernel_rows(a, m, k=256, r=4):
-    """the adapter kernels alone at the level-0 shape of the light U-Net (width 256, m = batch x 4096 tokens), with the
-    bytes each has to move and the rate that makes"""
+    """the q / k / v group at the level-0 shape of the light U-Net (width 256, m = batch x 4096 tokens): the fused calls
+    against the per-site launches they replace, with the bytes each must move"""
     from consistencytta_amd import _native as N
     L = N.lib()
     g = torch.Generator(device="cpu").manual_seed(9)
-    x = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)
-    y = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)
-    wa = (torch.randn(r, k, generator=g) * 0.25).to(DEV)
-    wb = (torch.randn(k, r, generator=g) * 0.02).to(DEV)
-    d = torch.empty(m, r, device=DEV)
-    grad = torch.zeros(r, k, device=DEV)
-    scratch = torch.empty(L.ctta_lora_wgrad_scratch_floats(m, k, r), device=DEV)
     s = N.stream_ptr()
-    calls = (("ctta_lora_down", m * k * 2 + m * r * 4,
-              lambda: N.check(L.ctta_lora_down(N.ptr(x), k, m, k, N.ptr(wa), 0, r, N.ptr(d), s))),
-             ("ctta_lora_up_add", 2 * m * k * 2 + m * r * 4,
-              lambda: N.check(L.ctta_lora_up_add(N.ptr(y), k, m, k, N.ptr(d), N.ptr(wb), 0, r, 1.0, s))),
-             ("ctta_lora_wgrad (2 launches)", m * k * 2 + m * r * 4,
-              lambda: N.check(L.ctta_lora_wgrad(N.ptr(d), N.ptr(x), k, m, k, r, 1.0, N.ptr(grad), k, 1, None, N.ptr(scratch), s))))
-    return [(name, event_ms(fn, a.warmup, 5 * a.steps) * 1e3, nbytes) for name, nbytes, fn in calls]
+    x = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)
+    ys = [torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV) for _ in range(3)]      # Y forward, dY backward
+    dx = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)
+    wa = [(torch.randn(r, k, generator=g) * 0.25).to(DEV) for _ in range(3)]
+    wb = [(torch.randn(k, r, generator=g) * 0.02).to(DEV) for _ in range(3)]
+    d = [torch.randn(m, r, generator=g).to(DEV) for _ in range(3)]
+    dd = [torch.empty(m, r, device=DEV) for _ in range(3)]
+    ga = [torch.zeros(r, k, device=DEV) for _ in range(3)]
+    gb = [torch.zeros(k, r, device=DEV) for _ in range(3)]
+    part = torch.empty(L.ctta_lora_wgrad_scratch_floats(m, k, r), device=DEV)
+    scratch = torch.empty(L.ctta_lora_sites_bwd_scratch_floats(m, k, k, 3, r), device=DEV)
+    fs = (N.LoraFwdSite * 3)()
+    bs = (N.LoraBwdSite * 3)()
+    for i in range(3):
+        fs[i].a, fs[i].b, fs[i].y, fs[i].d, fs[i].ldy, fs[i].n_pad = N.ptr(wa[i]), N.ptr(wb[i]), N.ptr(ys[i]), N.ptr(d[i]), k, k
+        bs[i].dy, bs[i].a, bs[i].b, bs[i].d, bs[i].ga, bs[i].gb = (N.ptr(t) for t in (ys[i], wa[i], wb[i], d[i], ga[i], gb[i]))
+        bs[i].ga_stride_r, bs[i].ga_stride_k, bs[i].gb_stride_r, bs[i].gb_stride_k, bs[i].lddy, bs[i].n_pad = k, 1, 1, r, k, k
+
+    def fwd_unfused():
+        for i in range(3):
+            N.check(L.ctta_lora_down(N.ptr(x), k, m, k, N.ptr(wa[i]), 0, r, N.ptr(d[i]), s))
+            N.check(L.ctta_lora_up_add(N.ptr(ys[i]), k, m, k, N.ptr(d[i]), N.ptr(wb[i]), 0, r, 1.0, s))
+
+    def bwd_unfused():
+        for i in range(3):
+            N.check(L.ctta_lora_down(N.ptr(ys[i]), k, m, k, N.ptr(wb[i]), 1, r, N.ptr(dd[i]), s))
+            N.check(L.ctta_lora_wgrad(N.ptr(d[i]), N.ptr(ys[i]), k, m, k, r, 1.0, N.ptr(gb[i]), 1, r, None, N.ptr(part), s))
+            N.check(L.ctta_lora_wgrad(N.ptr(dd[i]), N.ptr(x), k, m, k, r, 1.0, N.ptr(ga[i]), k, 1, None, N.ptr(part), s))
+            N.check(L.ctta_lora_up_add(N.ptr(dx), k, m, k, N.ptr(dd[i]), N.ptr(wa[i]), 1, r, 1.0, s))
+
+    act = m * k * 2
+    calls = (("forward: 3 x (down + up_add)", fwd_unfused, 3 * act + 6 * act),
+             ("forward: ctta_lora_sites_fwd", lambda: N.check(L.ctta_lora_sites_fwd(N.ptr(x), k, m, k, r, 1.0, fs, 3, s)), act + 6 * act),
+             ("forward: 3 x (down + up_add), again", fwd_unfused, 3 * act + 6 * act),
+             ("backward: 3 x (down + 2 wgrad + up_add)", bwd_unfused, 3 * (2 * act + act + 2 * act)),
+             ("backward: ctta_lora_sites_bwd", lambda: N.check(L.ctta_lora_sites_bwd(
+                 N.ptr(x), k, N.ptr(dx), k, m, k, r, 1.0, bs, 3, N.ptr(scratch), s)), 3 * act + act + 2 * act),
+             ("backward: 3 x (down + 2 wgrad + up_add), again", bwd_unfused, 3 * (2 * act + act + 2 * act)))
+    return [(name, event_ms(fn, a.warmup, 5 * a.steps) * 1e3, nbytes) for name, fn, nbytes in calls]
 
 
 def main():
@@ -140,29 +211,32 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lora_bench needs a GPU: nothing is measured without one")
-    lines = ["# LoRA on the light U-Net, %d timed calls after %d, hipEvent brackets; box %s, %s"
-             % (a.steps, a.warmup, socket.gethostname(), torch.cuda.get_device_name(0)),
+    lines = ["# %s: LoRA on the light U-Net, %d timed calls after %d, hipEvent brackets; box %s, %s"
+             % (datetime.date.today().isoformat(), a.steps, a.warmup, socket.gethostname(), torch.cuda.get_device_name(0)),
              "# inference forward, batch %d, latent 256 x 16, 32 text states" % a.forward_batch,
-             "%-36s %12s" % ("variant", "ms / call")]
+             "%-52s %12s" % ("variant", "ms / call")]
     for name, ms in forward_rows(a):
-        lines.append("%-36s %12.3f" % (name, ms))
+        lines.append("%-52s %12.3f" % (name, ms))
         print(lines[-1], flush=True)
     lines += ["# stage-1 train_step (AudioGDM, eager, one process), batch %d" % a.step_batch,
-              "%-36s %12s %16s" % ("variant", "ms / step", "trained / all")]
+              "%-52s %12s %16s" % ("variant", "ms / step", "trained / all")]
     for name, lora in (("full fine-tuning", False), ("LoRA rank 4", True), ("full fine-tuning, again", False)):
-        ms, n_train, n_all = step_ms(a, lora)
-        lines.append("%-36s %12.2f %16s" % (name, ms, "%d / %d" % (n_train, n_all)))
-        print(lines[-1], flush=True)
+        rows, n_train, n_all = step_ms(a, lora)
+        for tail, ms in rows:
+            lines.append("%-52s %12.2f %16s" % (name + tail, ms, "%d / %d" % (n_train, n_all)))
+            print(lines[-1], flush=True)
+    rate = stream_rate()
+    lines.append("# streaming rate of this box (two-shadow EMA pass, 64 M elements): %.0f GB/s" % (rate * 1e-3))
     for batch in (a.step_batch, a.forward_batch):
-        lines += ["# adapter kernels alone, %d rows (batch %d x 4096 tokens) x 256 columns, rank 4" % (batch * 4096, batch),
-                  "%-36s %12s %12s" % ("kernel", "us / call", "GB/s")]
+        lines += ["# the q / k / v group alone, %d rows (batch %d x 4096 tokens) x 256 columns, rank 4" % (batch * 4096, batch),
+                  "%-52s %12s %12s %12s" % ("launches", "us / call", "GB/s", "floor us")]
         for name, us, nbytes in kernel_rows(a, batch * 4096):
-            lines.append("%-36s %12.1f %12.0f" % (name, us, nbytes / us * 1e-3))
+            lines.append("%-52s %12.1f %12.0f %12.1f" % (name, us, nbytes / us * 1e-3, nbytes / rate))
             print(lines[-1], flush=True)
     text = "\n".join(lines) + "\n"
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+        with open(a.out, "a") as f:
             f.write(text)
 
 
