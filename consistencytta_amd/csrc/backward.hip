@@ -1316,14 +1316,18 @@ __global__ __launch_bounds__(256) void softmax_bias_kernel(const float* __restri
   if (lane == 0) red[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  // exponent = s * scale + (bias - max), ONE rounding: where a whole bias row is -10000, (s * scale + bias) - max rounded every
+  // score to the 2^-10 grid of fp32 at 10^4 before the maximum went off again -- 1e-3 of each probability.  bias - max is
+  // exact there (Sterbenz), and the rounding of the maximum itself shifts the whole row, which the normalisation removes.
+  auto ex = [&](int c) { return __expf(__fmaf_rn(sr[c], scale, (br ? br[c] : 0.f) - mx)); };
   float sum = 0.f;
-  for (int c = tid; c < cols; c += 256) sum += __expf(sr[c] * scale + (br ? br[c] : 0.f) - mx);
+  for (int c = tid; c < cols; c += 256) sum += ex(c);
   sum = wave_sum(sum);
   if (lane == 0) red[4 + wave] = sum;
   __syncthreads();
   const float inv = 1.0f / (red[4] + red[5] + red[6] + red[7]);
   for (int c = tid; c < ldp; c += 256)
-    pr[c] = c < cols ? f2bf(__expf(sr[c] * scale + (br ? br[c] : 0.f) - mx) * inv) : (bf16_t)0;
+    pr[c] = c < cols ? f2bf(ex(c) * inv) : (bf16_t)0;
 }
 extern "C" ctta_status ctta_softmax_bias_rows(const float* s, int lds, const float* bias, int rows_per_bias, void* p,
                                               int64_t rows, int cols, int ldp, float scale, void* stream) {

@@ -255,6 +255,7 @@ extern "C" ctta_status ctta_copy_segments_multi(const ctta_copy_seg* segs, int n
 // part layout: [B][nchunk][G][2] floats (sum, sumsq).
 // CAT: x is the channel concatenation [x (C1 channels) | x2 (C - C1 channels)] (torch.cat([h, skip], 1) of the up blocks),
 // which this pass also WRITES to y while it sums it: the separate concat launch and its re-read disappear.
+#define GN_FOLD_FP32_TERMS 128   // longest per-group fold (lanes * channels per group) still summed in fp32
 template <bool CAT>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const bf16_t* __restrict__ x, int HW, int C,
                                                          int G, int pix_per_chunk, int nchunk,
@@ -311,16 +312,34 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const bf16_t* __restric
   }
   __syncthreads();
   const int cpg = C / G;
-  for (int g = tid; g < G; g += 256) {
-    float s = 0.f, q = 0.f;
-    for (int l = 0; l < PL; ++l)
-      for (int cc = 0; cc < cpg; ++cc) {
-        s += ssum[l * C + g * cpg + cc];
-        q += ssq[l * C + g * cpg + cc];
-      }
-    float* o = part + (((size_t)b * nchunk + chunk) * G + g) * 2;
-    o[0] = s;
-    o[1] = q;
+  // The group's fold is ONE running sum over PL * cpg terms, and the variance E[x^2] - mean^2 multiplies the sums' relative
+  // error by (mean / std)^2.  Up to GN_FOLD_FP32_TERMS terms it runs in fp32 (64 .. 80 terms at the models' 32 groups: 1 .. 6e-4
+  // of rstd on a slab of 16 +- 0.43, and the models' outputs as they were); a longer one -- few groups: 2048 terms for a single group of 64 channels, which
+  // lost 1.3e-3 of rstd in fp32 -- runs in double, with one rounding to the fp32 partial (tests/norm_ref.py: gn_stats_emulated).
+  if (PL * cpg <= GN_FOLD_FP32_TERMS) {
+    for (int g = tid; g < G; g += 256) {
+      float s = 0.f, q = 0.f;
+      for (int l = 0; l < PL; ++l)
+        for (int cc = 0; cc < cpg; ++cc) {
+          s += ssum[l * C + g * cpg + cc];
+          q += ssq[l * C + g * cpg + cc];
+        }
+      float* o = part + (((size_t)b * nchunk + chunk) * G + g) * 2;
+      o[0] = s;
+      o[1] = q;
+    }
+  } else {
+    for (int g = tid; g < G; g += 256) {
+      double s = 0.0, q = 0.0;
+      for (int l = 0; l < PL; ++l)
+        for (int cc = 0; cc < cpg; ++cc) {
+          s += (double)ssum[l * C + g * cpg + cc];
+          q += (double)ssq[l * C + g * cpg + cc];
+        }
+      float* o = part + (((size_t)b * nchunk + chunk) * G + g) * 2;
+      o[0] = (float)s;
+      o[1] = (float)q;
+    }
   }
 }
 
