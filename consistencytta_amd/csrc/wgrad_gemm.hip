@@ -522,9 +522,11 @@ __global__ __launch_bounds__(64) void wgrad_rowsum_kernel(const bf16_t* __restri
   float* out = slabs + (size_t)s * slab_stride + (size_t)n * ld + col0;
   const int lo = s * seg, hi = min(min(lo + seg, mp), M);
   float total = 0.f;
-  const int nparts = nb > 0 ? nb : 1;
+  // nb < batch (the C ABI admits it): the positions behind the last per-sample column still belong to the bias column -- one
+  // more part, [nb * hw, hi), with no column of its own (nb = batch has no such positions: the loop and the bits it had)
+  const int nparts = nb > 0 ? nb + ((long long)nb * hw < hi ? 1 : 0) : 1;
   for (int b = 0; b < nparts; ++b) {
-    const int a = nb > 0 ? max(lo, b * hw) : lo, e = nb > 0 ? min(hi, (b + 1) * hw) : hi;
+    const int a = nb > 0 ? max(lo, b * hw) : lo, e = nb > 0 && b < nb ? min(hi, (b + 1) * hw) : hi;
     float sum = 0.f;
     int m = a + lane * 8;
     for (; m + 8 <= e; m += 512) {
@@ -535,7 +537,7 @@ __global__ __launch_bounds__(64) void wgrad_rowsum_kernel(const bf16_t* __restri
     for (int t = m; t < e && t < m + 8; ++t) sum += __uint_as_float((unsigned)row[t] << 16);     // the ragged tail of M
     sum = wave_sum(sum);
     total += sum;
-    if (nb > 0 && lane == 0) out[1 + b] = sum;
+    if (b < nb && lane == 0) out[1 + b] = sum;
   }
   if (lane == 0) out[0] = total;
 }
@@ -650,7 +652,8 @@ extern "C" ctta_status ctta_wgrad_rowsum(const void* dyt, int n, int mp, int m_v
                                          float* slabs, int64_t slab_stride, int ld, int bias_col, void* stream) {
   CTTA_REQUIRE(dyt && slabs && n >= 1 && splits >= 1 && mp % (8 * splits) == 0 && m_valid >= 1 && m_valid <= mp && bias_col >= 0 &&
                    bias_col + 1 + sample_cols <= ld, "wgrad_rowsum: bad arguments");
-  CTTA_REQUIRE(sample_cols == 0 || hw % 8 == 0, "wgrad_rowsum: per-sample columns need hw %% 8 == 0");
+  CTTA_REQUIRE(sample_cols >= 0 && (sample_cols == 0 || (hw % 8 == 0 && hw >= 8 && (long long)sample_cols * hw <= mp)),
+               "wgrad_rowsum: per-sample columns need hw %% 8 == 0 and sample_cols * hw <= mp");
   hipLaunchKernelGGL(wgrad_rowsum_kernel, dim3((unsigned)n, (unsigned)splits), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)dyt,
                      mp, m_valid, mp / splits, hw, sample_cols, slabs, (long long)slab_stride, ld, bias_col);
   CTTA_LAUNCH_CHECK();
