@@ -133,6 +133,65 @@ __global__ void consistency_renoise_kernel(const float4* __restrict__ c, const f
   }
 }
 
+// The masked sampler's blend (audioldm/latent_diffusion/ddim.py:216, img = img_orig * mask + (1 - mask) * img) on one
+// float4: torch's mul, rsub, mul, add in their order.
+__device__ __forceinline__ float4 keep_blend(float4 k, float4 s, float4 x0) {
+  return make_float4(k.x * s.x + (1.0f - k.x) * x0.x, k.y * s.y + (1.0f - k.y) * x0.y, k.z * s.z + (1.0f - k.z) * x0.z,
+                     k.w * s.w + (1.0f - k.w) * x0.w);
+}
+
+// consistency_renoise_kernel with a source clip: between the post-CFG combine and add_noise, x0 becomes
+// keep * src + (1 - keep) * x0.  `keep` is (B, hw): one plane per row, shared by the nvec_per / hwvec channels of the row.
+// ZERO: there is no query output yet (the sampler's start), x0 = 0 before the blend.  The fp32 operations are those of
+// torch's combine, torch's blend, heun_add_noise_kernel and heun_scale_kernel, in their order.
+template <bool CFG, bool ZERO, int COPIES>
+__global__ void consistency_edit_renoise_kernel(const float4* __restrict__ c, const float4* __restrict__ u,
+                                                const float* __restrict__ w, const float4* __restrict__ src,
+                                                const float4* __restrict__ keep, const float4* __restrict__ nz,
+                                                const float* __restrict__ sigma, float4* __restrict__ out, int nvec_per,
+                                                int hwvec, long long total) {
+  VEC_LOOP(total) {
+    const int b = (int)(i / nvec_per);
+    const int p = (int)(i - (long long)b * nvec_per) % hwvec;
+    const float s = sigma[b];
+    const float d = sqrtf(s * s + 1.0f);
+    float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!ZERO) x0 = c[i];
+    if (CFG) {
+      const float ww = w[b];
+      const float a = 1.0f - ww;
+      const float4 uu = u[i];
+      x0 = make_float4(a * uu.x + ww * x0.x, a * uu.y + ww * x0.y, a * uu.z + ww * x0.z, a * uu.w + ww * x0.w);
+    }
+    x0 = keep_blend(keep[(long long)b * hwvec + p], src[i], x0);
+    const float4 n = nz[i];
+    float4 z = make_float4(x0.x + n.x * s, x0.y + n.y * s, x0.z + n.z * s, x0.w + n.w * s);
+    z.x /= d; z.y /= d; z.z /= d; z.w /= d;
+    out[i] = z;
+    if (COPIES == 2) out[total + i] = z;
+  }
+}
+
+// The last query of the same sampler: cfg_combine_kernel (CFG) followed by the blend.
+template <bool CFG>
+__global__ void cfg_combine_keep_kernel(const float4* __restrict__ u, const float4* __restrict__ c,
+                                        const float* __restrict__ w, const float4* __restrict__ src,
+                                        const float4* __restrict__ keep, float4* __restrict__ out, int nvec_per, int hwvec,
+                                        long long total) {
+  VEC_LOOP(total) {
+    const int b = (int)(i / nvec_per);
+    const int p = (int)(i - (long long)b * nvec_per) % hwvec;
+    float4 x0 = c[i];
+    if (CFG) {
+      const float ww = w[b];
+      const float a = 1.0f - ww;
+      const float4 uu = u[i];
+      x0 = make_float4(a * uu.x + ww * x0.x, a * uu.y + ww * x0.y, a * uu.z + ww * x0.z, a * uu.w + ww * x0.w);
+    }
+    out[i] = keep_blend(keep[(long long)b * hwvec + p], src[i], x0);
+  }
+}
+
 // out = a[b]*x + b_[b]*y per sample (optionally clamped): DDPM/DDIM add_noise and the v-prediction step pieces
 __global__ void lincomb2_kernel(const float4* __restrict__ x, const float4* __restrict__ y, const float* __restrict__ a,
                                 const float* __restrict__ b_, float4* __restrict__ out, long long nvec_per, long long total,
@@ -507,6 +566,55 @@ extern "C" ctta_status ctta_consistency_renoise(const float* cond, const float* 
   if (uncond) { if (copies == 2) RENOISE(true, 2); else RENOISE(true, 1); }
   else        { if (copies == 2) RENOISE(false, 2); else RENOISE(false, 1); }
 #undef RENOISE
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+// the (B, hw) keep plane under a (B, n) row: whole float4s, whole planes, 32-bit positions within a row
+#define REQ_PLANE(what, n, hw)                                                                                        \
+  CTTA_REQUIRE((hw) > 0 && (hw) % 4 == 0, what ": hw=%lld must be a positive multiple of 4", (long long)(hw));         \
+  CTTA_REQUIRE((n) > 0 && (n) % (hw) == 0, what ": n_per_sample=%lld is no multiple of hw=%lld", (long long)(n),       \
+               (long long)(hw));                                                                                      \
+  CTTA_REQUIRE((n) / 4 <= 0x7fffffffLL, what ": n_per_sample=%lld too large", (long long)(n))
+
+extern "C" ctta_status ctta_consistency_edit_renoise(const float* cond, const float* uncond, const float* w_post,
+                                                     const float* src, const float* keep, const float* noise,
+                                                     const float* sigma, float* out, int copies, int batch,
+                                                     int64_t n_per_sample, int64_t hw, void* stream) {
+  CTTA_REQUIRE(noise && sigma && out && (!uncond || (w_post && cond)), "consistency_edit_renoise: null pointer");
+  CTTA_REQUIRE(src && keep, "consistency_edit_renoise: src and keep are both required");
+  CTTA_REQUIRE(copies == 1 || copies == 2, "consistency_edit_renoise: copies=%d (1 or 2)", copies);
+  CTTA_REQUIRE(batch > 0, "consistency_edit_renoise: empty tensor");
+  REQ_PLANE("consistency_edit_renoise", n_per_sample, hw);
+  const int nv = (int)(n_per_sample / 4), hwv = (int)(hw / 4);
+  const long long total = (long long)nv * batch;
+#define EDIT(CFG, ZERO, CP)                                                                                            \
+  hipLaunchKernelGGL((consistency_edit_renoise_kernel<CFG, ZERO, CP>), dim3(grid_for(total)), dim3(256), 0,             \
+                     (hipStream_t)stream, (const float4*)cond, (const float4*)uncond, w_post, (const float4*)src,       \
+                     (const float4*)keep, (const float4*)noise, sigma, (float4*)out, nv, hwv, total)
+  if (!cond)       { if (copies == 2) EDIT(false, true, 2); else EDIT(false, true, 1); }
+  else if (uncond) { if (copies == 2) EDIT(true, false, 2); else EDIT(true, false, 1); }
+  else             { if (copies == 2) EDIT(false, false, 2); else EDIT(false, false, 1); }
+#undef EDIT
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_cfg_combine_keep(const float* uncond, const float* cond, const float* w, const float* src,
+                                             const float* keep, float* out, int batch, int64_t n_per_sample, int64_t hw,
+                                             void* stream) {
+  CTTA_REQUIRE(cond && out && (!uncond || w), "cfg_combine_keep: null pointer");
+  CTTA_REQUIRE(src && keep, "cfg_combine_keep: src and keep are both required");
+  CTTA_REQUIRE(batch > 0, "cfg_combine_keep: empty tensor");
+  REQ_PLANE("cfg_combine_keep", n_per_sample, hw);
+  const int nv = (int)(n_per_sample / 4), hwv = (int)(hw / 4);
+  const long long total = (long long)nv * batch;
+#define COMBINE_KEEP(CFG)                                                                                              \
+  hipLaunchKernelGGL((cfg_combine_keep_kernel<CFG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,          \
+                     (const float4*)uncond, (const float4*)cond, w, (const float4*)src, (const float4*)keep,            \
+                     (float4*)out, nv, hwv, total)
+  if (uncond) COMBINE_KEEP(true); else COMBINE_KEEP(false);
+#undef COMBINE_KEEP
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }

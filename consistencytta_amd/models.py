@@ -290,6 +290,69 @@ def _post_cfg_combine(zh, B, w_post, w_dev):
     return out
 
 
+def _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps):
+    """The host-side rules of `ConsistencyTTA.edit_latent`, raised before anything is launched (they hold on host tensors):
+    `noise` is (B, C, H, W), or (r, B, C, H, W) in the captured form, the source has the sample's shape, the mask is
+    (B, 1, H, W) or (1, 1, H, W), `strength` lies in (0, 1].  Returns r = max(1, int(strength * num_steps)), the number of
+    queries that run (audioldm/pipeline.py:216, t_enc = int(transfer_strength * ddim_steps))."""
+    num_steps = int(num_steps)
+    if num_steps < 1:
+        raise ValueError("num_steps must be at least 1, got %d" % num_steps)
+    if not 0. < float(strength) <= 1.:
+        raise ValueError("strength %r: expected a number in (0, 1]" % (strength,))
+    sample = tuple(noise.shape[-4:])
+    if not torch.is_tensor(src_latent) or len(sample) != 4 or tuple(src_latent.shape) != sample:
+        got = tuple(src_latent.shape) if torch.is_tensor(src_latent) else type(src_latent).__name__
+        raise ValueError("src_latent %s: expected the noise's shape %s" % (got, sample))
+    B, _, H, W = sample
+    if keep_mask is not None and (not torch.is_tensor(keep_mask) or tuple(keep_mask.shape) not in ((B, 1, H, W), (1, 1, H, W))):
+        got = tuple(keep_mask.shape) if torch.is_tensor(keep_mask) else type(keep_mask).__name__
+        raise ValueError("keep_mask %s: expected (%d, 1, %d, %d) or (1, 1, %d, %d)" % (got, B, H, W, H, W))
+    return max(1, int(float(strength) * num_steps))
+
+
+def _ratio_span(extent, ratios, what):
+    """[int(extent * r0), int(extent * r1)) of audioldm/ldm.py:766-767, after the checks the reference leaves out."""
+    r0, r1 = (float(v) for v in ratios)
+    if not (0. <= r0 <= r1 <= 1.):
+        raise ValueError("%s %r: expected 0 <= start <= end <= 1" % (what, tuple(ratios)))
+    return int(extent * r0), int(extent * r1)
+
+
+def _edit_next_input(zh, B, w_post, w_dev, src, keep, draw, sig, z_in):
+    """`_student_next_input` with a source clip: post-CFG combine, the blend keep * src + (1 - keep) * x0, add_noise,
+    scale_model_input and the 2B-row stacking in ONE launch (ctta_consistency_edit_renoise).  `zh` None: the sampler's
+    start, x0 = 0 before the blend.  `keep`: (B, H * W)."""
+    use_cf = w_post > 1.
+    if zh is None:
+        cond, unc = None, None
+    elif use_cf and _post_cfg_fusable(w_post):
+        cond, unc = zh[B:], zh[:B]
+    elif use_cf:
+        cond, unc = (1 - w_post) * zh[:B] + w_post * zh[B:], None
+    else:
+        cond, unc = zh, None
+    N.check(N.lib().ctta_consistency_edit_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
+                                                  N.ptr(src), N.ptr(keep), N.ptr(draw), N.ptr(sig), N.ptr(z_in),
+                                                  2 if use_cf else 1, B, src[0].numel(), keep.shape[1], N.stream_ptr()))
+
+
+def _post_cfg_combine_keep(zh, B, w_post, w_dev, src, keep):
+    """The last query of the edit sampler: `_post_cfg_combine` and the blend in one launch (ctta_cfg_combine_keep)."""
+    use_cf = w_post > 1.
+    if use_cf and _post_cfg_fusable(w_post):
+        cond, unc = zh[B:], zh[:B]
+    elif use_cf:
+        cond, unc = (1 - w_post) * zh[:B] + w_post * zh[B:], None
+    else:
+        cond, unc = zh, None
+    out = torch.empty_like(src)
+    N.check(N.lib().ctta_cfg_combine_keep(N.ptr(unc), N.ptr(cond), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
+                                          N.ptr(src), N.ptr(keep), N.ptr(out), B, src[0].numel(), keep.shape[1],
+                                          N.stream_ptr()))
+    return out
+
+
 class AudioDistilledModel(nn.Module):
     """models/audio_distilled_model.py: text encoding, CFG teacher query, EMA bookkeeping."""
 
@@ -1905,9 +1968,10 @@ class ConsistencyTTA(nn.Module):
     """easy_inference/consistencytta.py: prompts -> int16 waveforms in one module."""
 
     def __init__(self, unet_config=None, vae=None, text_encoder=None, tokenizer=None,
-                 text_encoder_name="google/flan-t5-large"):
+                 text_encoder_name="google/flan-t5-large", stft=None):
         super().__init__()
         from . import spec
+        self.stft = stft      # audio.TacotronSTFT of the editing entries; the AudioLDM front end is created on first use
         self.unet = UNet2DConditionGuidedModel.from_config(unet_config or spec.LIGHT_UNET_CONFIG, subfolder="unet")
         self.vae = vae if vae is not None else AutoencoderKL(embed_dim=8, scale_factor=1.0)
         self.text_encoder, self.tokenizer, self.text_encoder_name = text_encoder, tokenizer, text_encoder_name
@@ -1998,6 +2062,217 @@ class ConsistencyTTA(nn.Module):
             z_in = torch.empty_like(zh)
             _student_next_input(zh, B, cfg_scale_post, w_post, noise[k + 1], sig, z_in)
         return _post_cfg_combine(zh, B, cfg_scale_post, w_post) if use_cf else zh
+
+    # ---- editing: the few-step sampler with a source clip (audioldm/pipeline.py:145-300, ldm.py:718-805, ddim.py:210-216)
+    @staticmethod
+    def latent_keep_mask(batch, latent_hw, time_keep=None, freq_keep=None, time_mask_ratio_start_and_end=None,
+                         freq_mask_ratio_start_and_end=None):
+        """The mask of the masked sampler, (B, 1, H, W) fp32 with 1 = keep the source (audioldm/ldm.py:764-768): ones,
+        zeros over the time rows [int(H * r0), int(H * r1)) and over the frequency columns [int(W * r0), int(W * r1)).
+        (1.0, 1.0) masks nothing.  `time_keep` (H) / `freq_keep` (W): explicit per-row / per-column keep values, multiplied
+        in.  Ratios outside [0, 1] or with start > end raise ValueError."""
+        H, W = (int(v) for v in latent_hw)
+        mask = torch.ones(int(batch), H, W, dtype=torch.float32)
+        if time_mask_ratio_start_and_end is not None:
+            a, b = _ratio_span(H, time_mask_ratio_start_and_end, "time_mask_ratio_start_and_end")
+            mask[:, a:b, :] = 0
+        if freq_mask_ratio_start_and_end is not None:
+            a, b = _ratio_span(W, freq_mask_ratio_start_and_end, "freq_mask_ratio_start_and_end")
+            mask[:, :, a:b] = 0
+        for keep, n, view, what in ((time_keep, H, (1, H, 1), "time_keep"), (freq_keep, W, (1, 1, W), "freq_keep")):
+            if keep is not None:
+                keep = torch.as_tensor(keep, dtype=torch.float32).cpu()
+                if tuple(keep.shape) != (n,):
+                    raise ValueError("%s %s: expected (%d,)" % (what, tuple(keep.shape), n))
+                mask = mask * keep.view(view)
+        return mask[:, None]
+
+    @torch.no_grad()
+    def edit_latent(self, encoder_states, encoder_mask, noise, src_latent, keep_mask=None, strength=1.0, cfg_scale_input=3.,
+                    cfg_scale_post=1., num_steps=1, uncond_states=None, uncond_mask=None, step_noise=None):
+        """The few-step sampler of `generate_latent` started from a source latent -- multistep consistency sampling with
+        the known region blended into x0 between two queries, the reference's masked sampler (ldm.py:718-805,
+        ddim.py:216) and its style transfer (pipeline.py:145-245) in this model's terms.  The query times are
+        `generate_latent`'s; the last r = max(1, int(strength * num_steps)) of them run.  r == num_steps (strength 1):
+        inpainting, the first input is scale(add_noise(keep * src, noise, t_first)) and nothing of the source outside the
+        kept region reaches the sampler.  r < num_steps: a variation, the first input is scale(add_noise(src, noise, t))
+        at the first remaining time.  After every query x0 becomes keep * src + (1 - keep) * x0; `keep_mask`:
+        (B, 1, H, W) or (1, 1, H, W), None keeps nothing.  `step_noise`: (r - 1, B, C, H, W)."""
+        r = _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps)
+        _check_step_noise(step_noise, r - 1, noise)
+
+        def draw(k):
+            if k == 0:
+                return noise
+            return torch.randn_like(noise) if step_noise is None else step_noise[k - 1]
+        return self._edit_loop(encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
+                               num_steps, uncond_states, uncond_mask, static=False)
+
+    def _edit_latent_static(self, encoder_states, encoder_mask, noise, src_latent, keep_mask, cfg_scale_input, cfg_scale_post,
+                            num_steps, strength=1.0, uncond_states=None, uncond_mask=None):
+        """`edit_latent` in the form the captured path records, with `_generate_latent_static`'s rules: `noise` is
+        (r, B, C, H, W) -- row 0 the first draw, rows 1.. the step noise --, queries after the first take the text K / V
+        from the handle's cache, each step is one launch of ctta_consistency_edit_renoise and the end is
+        ctta_cfg_combine_keep."""
+        r = _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps)
+        if noise.ndim != 5 or noise.shape[0] != r:
+            raise ValueError("noise %s: expected %s (row 0 the first draw, rows 1.. the step noise)"
+                             % (tuple(noise.shape), (r,) + tuple(src_latent.shape)))
+        return self._edit_loop(encoder_states, encoder_mask, lambda k: noise[k], src_latent, keep_mask, r, cfg_scale_input,
+                               cfg_scale_post, num_steps, uncond_states, uncond_mask, static=True)
+
+    def _edit_loop(self, encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
+                   num_steps, uncond_states, uncond_mask, static):
+        """The body of `edit_latent` and `_edit_latent_static`: r queries, one launch between two of them.  `draw(k)`: the
+        k-th noise.  `static`: nothing but launches happens (text K / V reuse on the caller's word, as in a capture)."""
+        sch = self.scheduler
+        use_cf = cfg_scale_post > 1.
+        if not src_latent.is_cuda:
+            raise N.CttaError("src_latent is on %s: the HIP sampler has no CPU path" % src_latent.device)
+        dev = src_latent.device
+        B, _, H, W = src_latent.shape
+        src = src_latent.detach().to(torch.float32).contiguous()
+        if keep_mask is None:
+            keep = torch.zeros(B, H * W, dtype=torch.float32, device=dev)
+        else:
+            keep = keep_mask.detach().to(dev, torch.float32).expand(B, 1, H, W).reshape(B, H * W).contiguous()
+        w_post = None
+        if use_cf:
+            encoder_states = torch.cat([uncond_states, encoder_states])
+            encoder_mask = torch.cat([uncond_mask, encoder_mask])
+            w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev)
+        sch.set_timesteps(18, device=dev)
+        t_head = float(sch._timesteps_host[0])
+        sig = sch._sigma_dev(sch.index_for_timestep(t_head), B, dev)
+        sch.set_timesteps(num_steps, device=dev)
+        times = ([t_head] + [float(v) for v in sch._timesteps_host[1::2]])[int(num_steps) - r:]
+        copies = 2 if use_cf else 1
+        z_in = torch.empty((copies * B,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
+        first = sch._check(draw(0))
+        if r == int(num_steps):     # inpainting: keep * src, noised at the head of the 18-step table
+            _edit_next_input(None, B, cfg_scale_post, w_post, src, keep, first, sig, z_in)
+        else:                       # variation: the whole source, noised at the first remaining time
+            sig = sch._sigma_dev(sch.index_for_timestep(times[0]), B, dev)
+            N.check(N.lib().ctta_consistency_renoise(N.ptr(src), N.c_void_p(0), N.c_void_p(0), N.ptr(first), N.ptr(sig),
+                                                     N.ptr(z_in), copies, B, src[0].numel(), N.stream_ptr()))
+        for k, t in enumerate(times):
+            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=encoder_states,
+                           encoder_attention_mask=encoder_mask, reuse_text=(k > 0) if static else None).sample
+            if k == r - 1:
+                break
+            sig = sch._sigma_dev(sch.index_for_timestep(times[k + 1]), B, dev)
+            z_in = torch.empty_like(zh)
+            _edit_next_input(zh, B, cfg_scale_post, w_post, src, keep, sch._check(draw(k + 1)), sig, z_in)
+        return _post_cfg_combine_keep(zh, B, cfg_scale_post, w_post, src, keep)
+
+    def _source_latent(self, source_wav, latent_hw, sample_posterior=False):
+        """(B, T) waveforms in [-1, 1] at 16 kHz -> the scaled source latent (B, C, H, W): `wav_to_fbank` with
+        target_length = 4 * H, `encode_first_stage`, `get_first_stage_encoding` (pipeline.py:203-210); the posterior's mean
+        unless `sample_posterior`."""
+        from . import audio
+        H, W = latent_hw
+        if self.stft is None:      # the AudioLDM front end (default_audioldm_config): 1024 / 160 / 1024, 64 bins, 0 - 8000 Hz
+            self.stft = audio.TacotronSTFT(1024, 160, 1024, 64, 16000, 0, 8000).to(self.device)
+        s = 1 << (len(self.vae.ddconfig["ch_mult"]) - 1)
+        if self.stft.n_mel_channels != s * W:
+            raise ValueError("a latent of %d frequency bins needs %d mel bins, the front end has %d"
+                             % (W, s * W, self.stft.n_mel_channels))
+        mel, _ = audio.wav_to_fbank(source_wav, target_length=s * H, fn_STFT=self.stft)
+        post = self.vae.encode_first_stage(mel[:, None])
+        return self.vae.get_first_stage_encoding(post if sample_posterior else post.mode())
+
+    @torch.no_grad()
+    def edit_from_embeds(self, encoder_states, encoder_mask, noise, source_wav, keep_mask=None, strength=1.0,
+                         cfg_scale_input=3., cfg_scale_post=1., num_steps=4, sr=16000, step_noise=None,
+                         sample_posterior=False, **kw):
+        """`forward_from_embeds` with a source waveform: the source latent (`_source_latent`), `edit_latent`,
+        `decode_first_stage`, `decode_to_waveform` and the 9.5 s cut.  The kept region of the returned waveform has
+        passed through the VAE and the vocoder; it is not spliced from the source."""
+        self.check_eval_mode()
+        r = _check_edit_inputs(noise, noise, keep_mask, strength, num_steps)
+        _check_step_noise(step_noise, r - 1, noise)
+        src = self._source_latent(source_wav, noise.shape[-2:], sample_posterior)
+        lat = self.edit_latent(encoder_states, encoder_mask, noise, src, keep_mask, strength, cfg_scale_input,
+                               cfg_scale_post, num_steps, step_noise=step_noise, **kw)
+        mel = self.vae.decode_first_stage(lat.float())
+        return self.vae.decode_to_waveform(mel)[:, :int(sr * 9.5)]
+
+    @torch.no_grad()
+    def edit(self, prompt, source_wav, time_mask_ratio_start_and_end=(1., 1.), freq_mask_ratio_start_and_end=(1., 1.),
+             strength=1.0, cfg_scale_input=3., cfg_scale_post=1., num_steps=4, num_samples=1, sr=16000,
+             sample_posterior=False):
+        """Prompts and source waveforms ((B, T) in [-1, 1] at 16 kHz, one per prompt) -> int16 waveforms (numpy), 9.5 s:
+        the clip with the masked time span / frequency band regenerated (pipeline.py:247-300; a frequency band is the
+        reference's super-resolution), or, with `strength` < 1, a text-guided variation of it (pipeline.py:145-245).  The
+        default ratios (1.0, 1.0) mask nothing: at strength 1 everything is kept and the clip comes back through the VAE and
+        the vocoder; with `strength` < 1 there is then no mask at all, as in style_transfer, and the whole clip varies."""
+        self.check_eval_mode()
+        embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
+        B = embeds.shape[0]
+        source_wav = torch.as_tensor(source_wav)
+        if source_wav.ndim != 2 or source_wav.shape[0] * num_samples != B:
+            raise ValueError("source_wav %s: expected (%d, samples), one clip per prompt"
+                             % (tuple(source_wav.shape), B // num_samples))
+        source_wav = source_wav.repeat_interleave(num_samples, 0)
+        noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
+        keep = self.latent_keep_mask(B, (256, 16), time_mask_ratio_start_and_end=time_mask_ratio_start_and_end,
+                                     freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end)
+        if float(strength) < 1. and bool((keep == 1).all()):
+            keep = None       # style_transfer has no mask: a variation without a masked span changes the whole clip
+        kw = {}
+        if cfg_scale_post > 1.:
+            kw = dict(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        return self.edit_from_embeds(embeds, mask, noise, source_wav, keep, strength, cfg_scale_input, cfg_scale_post,
+                                     num_steps, sr, sample_posterior=sample_posterior, **kw)
+
+    @torch.no_grad()
+    def capture_edit_graph(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
+                           num_steps=4, strength=1.0, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None):
+        """`capture_graph` for edits: the r = max(1, int(strength * num_steps)) queries of `edit_latent`, the VAE decoder,
+        HiFi-GAN and the int16 conversion as ONE hipGraph.  Returns `replay(encoder_states, encoder_mask, noise,
+        src_latent, keep_mask) -> pcm`; `noise` is (r, B, C, H, W) (or (B, C, H, W) when r == 1), the source latent and the
+        mask ((B, 1, H, W) or (1, 1, H, W), None keeps nothing) are static inputs owned by the capture: every argument is
+        copied in.  The waveform -> latent half (`_source_latent`) runs eagerly before a replay.  Results are identical to
+        `edit_latent(..., step_noise=noise[1:])` followed by the eager decoder and vocoder."""
+        self.check_eval_mode()
+        dev = self.unet.device
+        src0 = torch.zeros((batch,) + tuple(latent), device=dev)
+        r = _check_edit_inputs(src0, src0, None, strength, num_steps)
+        st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, r, cfg_scale_post, uncond_states,
+                                        uncond_mask, False)
+        st["src"] = src0
+        st["keep"] = torch.zeros(batch, 1, latent[1], latent[2], device=dev)
+        # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
+        st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
+
+        def run():
+            lat = self._edit_latent_static(st["enc"], st["mask"], st["noise"], st["src"], st["keep"], cfg_scale_input,
+                                           cfg_scale_post, num_steps, strength, st.get("unc"), st.get("unc_mask"))
+            mel = self.vae.decode_first_stage(lat)
+            wav = self.vae.vocode(mel)
+            pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
+            N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(st["scratch"]), None, N.ptr(pcm),
+                                              N.stream_ptr()))
+            return lat, mel, pcm
+
+        _warm_up(run, dev)
+        graph, out = _capture(run)
+
+        def replay(encoder_states, encoder_mask, noise, src_latent, keep_mask=None):
+            _check_edit_inputs(st["noise"], src_latent, keep_mask, strength, num_steps)
+            load(encoder_states, encoder_mask, noise)
+            st["src"].copy_(src_latent)
+            if keep_mask is None:
+                st["keep"].zero_()
+            else:
+                st["keep"].copy_(keep_mask)        # (1, 1, H, W) broadcasts over the batch
+            graph.replay()
+            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
+            return out[2]
+
+        replay.graph, replay.outputs, replay.queries = graph, out, r
+        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
+        return replay
 
     def _serving_inputs(self, batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post, uncond_states,
                         uncond_mask, from_tokens):

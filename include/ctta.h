@@ -356,6 +356,24 @@ ctta_status ctta_cfg_combine(const float* uncond, const float* cond, const float
 ctta_status ctta_consistency_renoise(const float* cond, const float* uncond, const float* w_post, const float* noise,
                                      const float* sigma, float* out, int copies, int batch, int64_t n_per_sample,
                                      void* stream);
+/* The same step with a source clip: the masked sampler of audioldm/ldm.py:718-805, whose step ends with
+ * img = img_orig * mask + (1 - mask) * img (audioldm/latent_diffusion/ddim.py:210-216), in the few-step consistency
+ * sampler's terms -- the known region is blended into x0 between two queries.  One pass over (B, n) f32:
+ *   x0  = uncond == NULL ? cond : (1 - w_post[b]) * uncond + w_post[b] * cond      (as ctta_consistency_renoise)
+ *   x0  = keep[b, p] * src + (1 - keep[b, p]) * x0                                 (ddim.py:216; p = position in the plane)
+ *   z   = x0 + noise * sigma[b];   out = z / sqrt(sigma[b]^2 + 1)                  (written `copies` = 1 or 2 times)
+ * keep is (B, hw) f32, 1 = keep the source (ldm.py:764-768), shared by the n_per_sample / hw channels of a row; hw % 4 == 0
+ * and n_per_sample % hw == 0.  src is (B, n); src and keep are both required.  cond == NULL (then uncond must be NULL too)
+ * means x0 = 0 before the blend: the sampler's start, where keep * src plus noise is the first input.  Bit-identical to
+ * torch's (1 - w) * u + w * c, torch's keep * src + (1 - keep) * x0, ctta_heun_add_noise, ctta_heun_scale_model_input
+ * and a concatenation.
+ * ctta_cfg_combine_keep: the last query's post-CFG combine (uncond may be NULL: out is the blend of cond) and the same
+ * blend, without the re-noising. */
+ctta_status ctta_consistency_edit_renoise(const float* cond, const float* uncond, const float* w_post, const float* src,
+                                          const float* keep, const float* noise, const float* sigma, float* out,
+                                          int copies, int batch, int64_t n_per_sample, int64_t hw, void* stream);
+ctta_status ctta_cfg_combine_keep(const float* uncond, const float* cond, const float* w, const float* src,
+                                  const float* keep, float* out, int batch, int64_t n_per_sample, int64_t hw, void* stream);
 /* get_loss with MSELoss('instance') and SNR clamp (models/audio_consistency_model.py:250-266,
  * tools/losses.py:28-33): loss = mean_b( mean((pred-target)^2) * min(sigma^-2, gamma) ).
  * gamma <= 0 disables the weighting.  loss: 1 float on device. */

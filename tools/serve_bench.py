@@ -19,6 +19,11 @@ every form alike; the JSON keeps every window, the median and the ratios of medi
   graph_over_eager / pipeline_over_eager for the few-step forms
 
   python tools/serve_bench.py --out profiles/serve_bench.json
+
+`--edit` runs another leg alone (no text encoder): the captured edit path beside the captured plain few-step path at
+`--edit-steps` queries, and the one-pass step kernel beside the launches it replaces (see `edit_leg`):
+
+  python tools/serve_bench.py --edit --out profiles/edit_serving.json
 """
 import argparse
 import json
@@ -32,8 +37,167 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def edit_leg(args):
+    """`--edit`: the captured edit path (capture_edit_graph: inpainting with a (0.25, 0.75) time mask) beside the captured
+    plain few-step path (capture_graph) at the same num_steps, states in, in alternating windows; and the one-pass step
+    kernel (ctta_consistency_edit_renoise) beside the launches it replaces (torch combine, torch blend,
+    ctta_heun_add_noise, ctta_heun_scale_model_input, torch.cat) on one latent-sized batch.  The source latent is
+    synthetic: the waveform -> latent half runs eagerly before a replay and is not part of either form."""
+    import torch
+    from consistencytta_amd import _native as N
+    from consistencytta_amd import modules, spec
+    from consistencytta_amd.models import ConsistencyTTA
+    dev = "cuda:0"
+    B, L, steps = args.batch, args.text_len, args.edit_steps
+    if args.tiny:
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        import cases
+        ucfg, latent = dict(cases.TINY_UNET), (8, 32, 16)
+        vae = modules.AutoencoderKL(ddconfig=cases.TINY_VAE_DD, embed_dim=8, scale_factor=0.9, hifigan_config=cases.TINY_HIFIGAN)
+    else:
+        ucfg, latent = spec.LIGHT_UNET_CONFIG, (8, 256, 16)
+        vae = modules.AutoencoderKL(ddconfig=spec.VAE_DDCONFIG, embed_dim=8, scale_factor=0.9227914214134216)
+    D = ucfg["cross_attention_dim"]
+    pipe = ConsistencyTTA(unet_config=ucfg, vae=vae)
+    pipe.to(dev)
+    pipe.unet.init_random_(seed=0)
+    vae.init_random_(seed=1)
+    pipe.eval().requires_grad_(False)
+    W_IN = 4.0
+    g = torch.Generator(device="cpu").manual_seed(3)
+    keep = pipe.latent_keep_mask(B, latent[1:], time_mask_ratio_start_and_end=(0.25, 0.75)).to(dev)
+    batches = []
+    for _ in range(2):
+        lens = torch.randint(min(6, L), L + 1, (B,), generator=g)
+        batches.append({"enc": (torch.randn(B, L, D, generator=g) * 0.25).to(dev),
+                        "mask": (torch.arange(L)[None, :] < lens[:, None]).to(dev),
+                        "noise": torch.randn((steps, B) + latent, generator=g).to(dev),
+                        "src": (torch.randn((B,) + latent, generator=g) * 0.8).to(dev)})
+    scratch = torch.empty(4, dtype=torch.float32, device=dev)
+
+    def to_pcm(lat):
+        wav = vae.vocode(vae.decode_first_stage(lat))
+        pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
+        N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
+        return pcm
+
+    def eager_plain(b):
+        return to_pcm(pipe.generate_latent(b["enc"], b["mask"], b["noise"][0], W_IN, 1.0, steps, step_noise=b["noise"][1:]))
+
+    def eager_edit(b):
+        return to_pcm(pipe.edit_latent(b["enc"], b["mask"], b["noise"][0], b["src"], keep, 1.0, W_IN, 1.0, steps,
+                                       step_noise=b["noise"][1:]))
+
+    ref_plain, ref_edit = eager_plain(batches[0]).clone(), eager_edit(batches[0]).clone()
+    torch.cuda.synchronize()
+    kw0 = dict(cfg_scale_input=W_IN, cross_attention_dim=D, latent=latent, num_steps=steps)
+    gen_plain = pipe.capture_graph(B, L, **kw0)
+    gen_edit = pipe.capture_edit_graph(B, L, **kw0)
+    b0 = batches[0]
+    parity = {"plain_graph": bool(torch.equal(gen_plain(b0["enc"], b0["mask"], b0["noise"]), ref_plain)),
+              "edit_graph": bool(torch.equal(gen_edit(b0["enc"], b0["mask"], b0["noise"], b0["src"], keep), ref_edit))}
+    if not all(parity.values()):
+        raise SystemExit("a captured form differs from its eager counterpart: %s" % parity)
+
+    turn = [0]
+
+    def nxt():
+        turn[0] ^= 1
+        return batches[turn[0]]
+
+    def plain_call():
+        b = nxt()
+        return gen_plain(b["enc"], b["mask"], b["noise"])
+
+    def edit_call():
+        b = nxt()
+        return gen_edit(b["enc"], b["mask"], b["noise"], b["src"], keep)
+    forms = {"plain_graph": plain_call, "edit_graph": edit_call, "plain_eager": lambda: eager_plain(nxt()),
+             "edit_eager": lambda: eager_edit(nxt())}
+    for fn in forms.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    windows = {k: [] for k in forms}
+    for _ in range(args.rounds):
+        for k, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            windows[k].append((time.perf_counter() - t0) / args.steps * 1e3)
+    med = {k: statistics.median(v) for k, v in windows.items()}
+
+    # ---- the step between two queries alone: one launch against the chain it replaces, device time by events
+    n, hw = latent[0] * latent[1] * latent[2], latent[1] * latent[2]
+    c, u, nz, src = (torch.randn(B, n, generator=g).to(dev) for _ in range(4))
+    sig = torch.full((B,), 0.7, device=dev)
+    w = torch.full((B,), 2.0, device=dev)
+    keep2 = keep.reshape(B, hw).contiguous()
+    keep_rows = keep2[:, None, :].expand(B, latent[0], hw).reshape(B, n).contiguous()
+    L_ = N.lib()
+
+    def chain(cfg):
+        x0 = ((1 - 2.0) * u + 2.0 * c) if cfg else c
+        x0 = keep_rows * src + (1 - keep_rows) * x0
+        z, out = torch.empty_like(x0), torch.empty_like(x0)
+        N.check(L_.ctta_heun_add_noise(N.ptr(x0), N.ptr(nz), N.ptr(sig), N.ptr(z), B, n, N.stream_ptr()))
+        N.check(L_.ctta_heun_scale_model_input(N.ptr(z), N.ptr(sig), N.ptr(out), B, n, N.stream_ptr()))
+        return torch.cat([out] * 2) if cfg else out
+
+    def fused(cfg):
+        out = torch.empty((2 * B if cfg else B, n), device=dev)
+        N.check(L_.ctta_consistency_edit_renoise(N.ptr(c), N.ptr(u) if cfg else N.c_void_p(0),
+                                                 N.ptr(w) if cfg else N.c_void_p(0), N.ptr(src), N.ptr(keep2), N.ptr(nz),
+                                                 N.ptr(sig), N.ptr(out), 2 if cfg else 1, B, n, hw, N.stream_ptr()))
+        return out
+    step_parity = {("cfg" if cfg else "cond"): bool(torch.equal(chain(cfg).view(torch.int32), fused(cfg).view(torch.int32)))
+                   for cfg in (False, True)}
+    step_forms = {"chain_cond": lambda: chain(False), "fused_cond": lambda: fused(False),
+                  "chain_cfg": lambda: chain(True), "fused_cfg": lambda: fused(True)}
+    step_us = {k: [] for k in step_forms}
+    reps = 200
+    for _ in range(args.rounds + 1):           # the first round warms up and is dropped
+        for k, fn in step_forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            step_us[k].append(e0.elapsed_time(e1) / reps * 1e3)
+    step_med = {k: statistics.median(v[1:]) for k, v in step_us.items()}
+    result = {
+        "tool": "tools/serve_bench.py --edit", "device": torch.cuda.get_device_name(0), "tiny": bool(args.tiny),
+        "batch": B, "text_len": L, "latent": list(latent), "num_steps": steps, "time_mask_ratio_start_and_end": [0.25, 0.75],
+        "steps_per_window": args.steps, "rounds": args.rounds, "warmup_calls": args.warmup,
+        "unit": "ms per call of one batch; step kernels: us per step, stream time by events over %d back-to-back steps "
+                "(launch cost included)" % reps,
+        "timing": "host clock around a window of calls ending in a device synchronise; forms alternate within a round",
+        "parity_bit_identical_to_eager": parity, "step_parity_bit_identical": step_parity,
+        "ms_per_call_median": {k: round(v, 3) for k, v in med.items()},
+        "ms_per_call_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()},
+        "ratios_of_medians": {"edit_graph_over_plain_graph": round(med["edit_graph"] / med["plain_graph"], 4),
+                              "edit_eager_over_plain_eager": round(med["edit_eager"] / med["plain_eager"], 4),
+                              "edit_graph_over_edit_eager": round(med["edit_graph"] / med["edit_eager"], 4)},
+        "step_us_median": {k: round(v, 2) for k, v in step_med.items()},
+        "step_us_windows": {k: [round(x, 2) for x in v[1:]] for k, v in step_us.items()},
+        "step_fused_over_chain": {"cond": round(step_med["fused_cond"] / step_med["chain_cond"], 4),
+                                  "cfg": round(step_med["fused_cfg"] / step_med["chain_cfg"], 4)},
+    }
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--edit", action="store_true", help="only the editing leg: the captured edit path beside the captured "
+                    "plain few-step path, and the one-pass step kernel beside the chain it replaces")
+    ap.add_argument("--edit-steps", type=int, default=4, help="num_steps of the editing leg")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--text-len", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10, help="calls per timed window")
@@ -49,6 +213,8 @@ def main():
     from consistencytta_amd.models import ConsistencyTTA
     if not torch.cuda.is_available():
         raise SystemExit("serve_bench needs a GPU: there is no CPU path and no number without one")
+    if args.edit:
+        return edit_leg(args)
     dev = "cuda:0"
     B, L = args.batch, args.text_len
 
