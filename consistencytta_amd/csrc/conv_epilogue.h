@@ -118,11 +118,10 @@ __device__ __forceinline__ void epilogue_wide4(const ConvParams& p, const float4
   pk.x = pack2bf(v[0], v[1]);
   pk.y = pack2bf(v[2], v[3]);
   *reinterpret_cast<uint2*>(o) = pk;
-  if (gn_acc) {   // statistics of the values as stored (bf16-rounded), like a separate pass over the tensor would see them
-    const float r0 = __uint_as_float(pk.x << 16), r1 = __uint_as_float(pk.x & 0xffff0000u);
-    const float r2 = __uint_as_float(pk.y << 16), r3 = __uint_as_float(pk.y & 0xffff0000u);
-    gn_acc->x += (r0 + r1) + (r2 + r3);
-    gn_acc->y += (r0 * r0 + r1 * r1) + (r2 * r2 + r3 * r3);
+  if (gn_acc) {   // statistics of the fp32 values BEFORE the bf16 rounding: the contract of ctta_conv_desc.gn_part, and what
+                  // wide_epilogue_fast<GN> sums for the other waves of the same launch
+    gn_acc->x += (v[0] + v[1]) + (v[2] + v[3]);
+    gn_acc->y += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
   }
   if (p.out2) {   // leaky_relu of the SAME (bf16-rounded) values
     float w2[4] = {__uint_as_float(pk.x << 16), __uint_as_float(pk.x & 0xffff0000u), __uint_as_float(pk.y << 16),

@@ -211,7 +211,9 @@ __device__ __forceinline__ void wide_epilogue_fast(const ConvParams& p, f32x4_t 
 // i (even) holds the values and fragment i+1 the gates of the same 16 hidden units for the same lane positions:
 // out[m][h] = (val + bias_v) * gelu(gate + bias_g), h = (n / 32) * 16 + n % 16, written to a matrix of HALF the
 // GEMM width.  Replaces attention.py:430-432 (proj -> chunk(2) -> value * gelu(gate)) without the round trip.
-__device__ __forceinline__ void epilogue_geglu(const ConvParams& p, const f32x4_t av, const f32x4_t ag, int m, int n) {
+// `row`: element offset of the output row (the caller applies the per-sample stride: this form runs when the destination is
+// not plain).
+__device__ __forceinline__ void epilogue_geglu(const ConvParams& p, const f32x4_t av, const f32x4_t ag, size_t row, int n) {
   float v[4] = {av[0], av[1], av[2], av[3]}, g[4] = {ag[0], ag[1], ag[2], ag[3]};
   if (p.bias) {
     const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
@@ -226,7 +228,7 @@ __device__ __forceinline__ void epilogue_geglu(const ConvParams& p, const f32x4_
   uint2 pk;
   pk.x = pack2bf(o[0], o[1]);
   pk.y = pack2bf(o[2], o[3]);
-  *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.out) + (size_t)m * p.ldc + h) = pk;
+  *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.out) + row + h) = pk;
 }
 
 // orders a wave's own LDS writes before its LDS reads (other lanes of the SAME wave) without a workgroup barrier
@@ -1050,10 +1052,13 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, unsigned char* sm
 #pragma unroll
       for (int j = 0; j < FM; ++j) {
         const int m = m0 + wm * TM + j * 16 + frow;
+        const bool m_ok = m < p.M;
+        const int b = m_ok ? m / p.howo : 0;          // sample b starts at b * obs (out_batch_stride), as in epilogue_store
+        const size_t row = (size_t)((long long)b * p.obs + (long long)(m - b * p.howo) * p.ldc);
 #pragma unroll
         for (int i = 0; i < FN; i += 2) {
           const int n = n0 + wn * TN + i * 16 + nsub;
-          if (m < p.M && n < p.n) epilogue_geglu(p, acc[i][j], acc[i + 1][j], m, n);
+          if (m_ok && n < p.n) epilogue_geglu(p, acc[i][j], acc[i + 1][j], row, n);
         }
       }
       return;

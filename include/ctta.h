@@ -443,7 +443,8 @@ typedef struct {
   const void* res; int res_ld;          /* + res[m*ld + n] bf16 or NULL */
   int in_act;                 /* on the A operand: 0 none, 1 leaky_relu(in_slope) */
   float in_slope;
-  int out_act;                /* 0 none, 1 silu, 2 tanh, 3 leaky_relu(out_slope) */
+  int out_act;                /* 0 none, 1 silu, 2 tanh, 3 leaky_relu(out_slope), 4 fused GEGLU (bias only, n % 32 == 0,
+                                 out of half the width; out_batch_stride is honoured, out_offset / out_limit are not taken) */
   float out_slope;
   float alpha;                /* v = alpha*(acc + bias + rowvec + res [+ old out]) */
   int accumulate;             /* 1: add the existing output before scaling */
@@ -462,7 +463,12 @@ typedef struct {
    * gn_part != NULL, gn_groups divides n and gn_hw (rows per sample) divides the row count, every workgroup writes
    * (sum, sum of squares) per channel group of its tile to gn_part [batch][chunks][gn_groups][2] fp32, chunks = gn_hw /
    * tile rows.  Only some launches can do it (plain bf16 output through the wide-store epilogue, whole tiles per sample,
-   * no split-K): ctta_conv_last_gn_chunks() tells the caller whether -- and with how many chunks -- it happened. */
+   * no split-K): ctta_conv_last_gn_chunks() tells the caller whether -- and with how many chunks -- it happened.
+   * CONTRACT of the partials: they are the sums of the output values in fp32 BEFORE their rounding to bf16 (after alpha and
+   * the output activation), i.e. what a GroupNorm computed in fp32 on the unrounded convolution result sees -- not the sums
+   * of the stored bf16 numbers, from which they differ by zero-mean rounding noise of 2^-9 relative per element.  Every
+   * epilogue code that writes partials (the straight-line waves and the generic column-edge waves of one launch) sums the
+   * same quantity; tests/test_conv_forms_gpu.py holds each entry to the float64 sums of it. */
   void* gn_part; int gn_groups; int gn_hw;
   int64_t gn_part_floats;     /* capacity of gn_part; launches whose partials would not fit write none */
 } ctta_conv_desc;
