@@ -4,6 +4,7 @@ the export of the two kernels, and the restatement tests/edit_ref.py on a linear
 import pytest
 import torch
 
+import abi
 import cases
 import edit_ref
 from consistencytta_amd import _native as N
@@ -104,13 +105,7 @@ def test_edit_latent_refuses_bad_arguments_before_any_launch():
 
 
 def test_edit_kernels_are_exported_and_bound():
-    with open(N.os.path.join(N._HERE, "..", "include", "ctta.h")) as f:
-        header = f.read()
-    for name, arity in (("ctta_consistency_edit_renoise", 13), ("ctta_cfg_combine_keep", 10)):
-        assert name in N.SIGNATURES
-        fn = getattr(N.lib(), name)
-        assert fn.restype is N.c_int and len(fn.argtypes) == arity
-        assert name + "(" in header
+    abi.assert_bound(("ctta_consistency_edit_renoise", "ctta_cfg_combine_keep"))
 
 
 # ------------------------------------------------------------------------------------- the restatement on a dummy query

@@ -175,21 +175,9 @@ def test_lrelu_bwd_refuses_a_ragged_length():
 
 
 # ------------------------------------------------------------------------------------ table-driven transposes / copies
-class TposeJob(ctypes.Structure):
-    """ctta_tpose_job (include/ctta.h)"""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
-                ("src_ld", ctypes.c_int), ("dst_ld", ctypes.c_int), ("wcols", ctypes.c_int), ("block0", ctypes.c_int),
-                ("tiles_r", ctypes.c_int)]
-
-
-class CopySeg(ctypes.Structure):
-    """ctta_copy_seg (include/ctta.h)"""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("count", ctypes.c_int)]
-
-
 def _run_transposes(specs):
     """specs: (rows, cols, src_ld, wcols, dst_ld); the table is built as WeightPacker::add_transpose builds it."""
-    jobs = (TposeJob * len(specs))()
+    jobs = (N.TposeJob * len(specs))()
     keep, blocks = [], 0
     for i, (rows, cols, src_ld, wcols, dst_ld) in enumerate(specs):
         src = torch.full((rows, src_ld), POISON)
@@ -217,7 +205,7 @@ def test_transpose_multi():
              (1, 8, 8, 8, 8),             # one row: wcols > rows
              (70, 136, 144, 72, 72),      # ragged both ways, wcols > rows, source rows longer than cols
              (200, 72, 72, 200, 208)]     # several row tiles, dst_ld > wcols
-    assert ctypes.sizeof(TposeJob) == 48
+    assert ctypes.sizeof(N.TposeJob) == 48
     _run_transposes(specs)
     _run_transposes(specs[2:3])           # a single-job table (the binary search over one entry)
     _run_transposes(list(reversed(specs)))
@@ -230,14 +218,14 @@ def test_copy_segments_multi():
     total = sum(c + gap for c in counts) + gap
     want = torch.full((total,), POISON)
     srcd, dstd = src.to(DEV), want.clone().to(DEV)
-    segs = (CopySeg * len(counts))()
+    segs = (N.CopySeg * len(counts))()
     s_off, d_off = 3, gap                 # sources start 12 bytes into the buffer: no 16-byte alignment is promised
     for i, c in enumerate(counts):
         segs[i].src, segs[i].dst, segs[i].count = srcd.data_ptr() + 4 * s_off, dstd.data_ptr() + 4 * d_off, c
         want[d_off:d_off + c] = src[s_off:s_off + c]
         s_off += c
         d_off += c + gap
-    assert ctypes.sizeof(CopySeg) == 24
+    assert ctypes.sizeof(N.CopySeg) == 24
     table = upload_table(segs)
     N.check(lib().ctta_copy_segments_multi(N.ptr(table), len(counts), N.stream_ptr()))
     sync()

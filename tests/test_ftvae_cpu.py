@@ -3,19 +3,17 @@ summary, the train / eval / requires_grad pattern, `load_pretrained`'s key routi
 decoder, and the C ABI of the two new engine entries."""
 import json
 import os
-import re
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import cases
-from consistencytta_amd import _native as N
 from consistencytta_amd import checkpoint as ck
 from consistencytta_amd import modules
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEC = ("decoder.", "post_quant_conv.")
 
 
@@ -40,12 +38,7 @@ def _ftvae(**kw):
 
 
 def test_header_and_signatures_agree_on_the_engine_entries():
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ctta.h")).read(), flags=re.S)
-    for name, nargs in (("ctta_vae_decode_backward_params", 7), ("ctta_vae_load_weights", 4)):
-        m = re.search(r"ctta_status %s\s*\(([^)]*)\)" % name, header)
-        assert m and len(m.group(1).split(",")) == nargs, name
-        res, args = N.SIGNATURES[name]
-        assert res is N.c_int and len(args) == nargs
+    abi.assert_bound(("ctta_vae_decode_backward_params", "ctta_vae_load_weights"))
 
 
 def test_modes_and_frozen_sets_follow_the_reference():

@@ -3,23 +3,16 @@ include/ctta.h declares, the nn.Module mirrors carry the reference's state-dict 
 scheduler's host tables match the reference, and the product path fails LOUDLY (no CPU
 fallback) when it is handed CPU tensors or the library is missing."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import cases
 from consistencytta_amd import _native as N
 from consistencytta_amd import modules, scheduler, spec
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared_symbols():
-    text = open(os.path.join(ROOT, "include", "ctta.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ctta_[a-z0-9_]+)\s*\(", text)))
 
 
 @pytest.fixture(scope="module")
@@ -30,7 +23,7 @@ def built_lib():
 
 
 def test_library_exports_every_declared_symbol(built_lib):
-    declared = _declared_symbols()
+    declared = abi.declared_symbols()
     assert len(declared) >= 45
     for name in declared:
         assert hasattr(built_lib, name), "libctta_hip.so does not export %s" % name
@@ -38,40 +31,6 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert sorted(N.SIGNATURES) == declared
     assert built_lib.ctta_version() == 100
     assert built_lib.ctta_conv_gemm_num_variants() >= 4
-
-
-def test_struct_layouts_match_header_field_order():
-    text = open(os.path.join(ROOT, "include", "ctta.h")).read()
-    end = text.index("} ctta_conv_desc;")
-    body = text[text.rindex("typedef struct {", 0, end) + len("typedef struct {"):end]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        decl = re.sub(r"^(const\s+)?(void|float|int64_t|int)\s*\*?", "", decl).strip()
-        names += [n.strip().lstrip("*") for n in decl.split(",")]
-    assert names == [f[0] for f in N.ConvDesc._fields_]
-    # ctta_ffn_desc (round 6): same field order, and the same byte size as the C compiler gives it
-    end = text.index("} ctta_ffn_desc;")
-    body = re.sub(r"/\*.*?\*/", "", text[text.rindex("typedef struct {", 0, end) + len("typedef struct {"):end], flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = re.sub(r"^(const\s+)?(void|float|int64_t|int)\s*\*?", "", decl.strip()).strip()
-        if decl:
-            names += [n.strip().lstrip("*") for n in decl.split(",")]
-    assert names == [f[0] for f in N.FfnDesc._fields_]
-    import ctypes
-    import subprocess
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "s.c")
-        open(src, "w").write('#include <stdio.h>\n#include "ctta.h"\nint main(void) { printf("%zu %zu\\n", sizeof(ctta_ffn_desc), sizeof(ctta_conv_desc)); return 0; }\n')
-        exe = os.path.join(td, "s")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        ffn_size, conv_size = (int(v) for v in subprocess.check_output([exe]).split())
-    assert ffn_size == ctypes.sizeof(N.FfnDesc) and conv_size == ctypes.sizeof(N.ConvDesc)
 
 
 def test_mirror_state_dict_keys_are_the_references(golden):

@@ -9,12 +9,12 @@ import pytest
 import torch
 from torch import nn
 
+import abi
 import cases
 import lora_cases as LC
 from consistencytta_amd import _native as N
 from consistencytta_amd import checkpoint, models, modules, spec
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ctta_lora_down", "ctta_lora_up_add", "ctta_lora_up_add_t", "ctta_lora_wgrad", "ctta_lora_wgrad_scratch_floats")
 _KW = dict(text_encoder_name="google/flan-t5-large", scheduler_name="stabilityai/stable-diffusion-2-1",
            unet_model_config_path="tiny_light.json", unet_config=LC.LORA_TINY_LIGHT, snr_gamma=5.0,
@@ -202,19 +202,7 @@ def L():
 
 
 def test_header_signatures_and_library_agree_on_the_new_entries(L):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ctta.h")).read(), flags=re.S)
-    ctype = {"int": N.c_int, "int64_t": N.c_int64, "float": N.c_float, "size_t": N.c_size_t}
-    for name in NEW:
-        m = re.search(r"(\w+)\s+%s\s*\(([^)]*)\)" % name, header)
-        assert m, "%s is not declared in include/ctta.h" % name
-        assert name in N.SIGNATURES and hasattr(L, name)
-        res, args = N.SIGNATURES[name]
-        assert res is (N.c_size_t if m.group(1) == "size_t" else N.c_int)
-        decl = [a.strip() for a in m.group(2).split(",")]
-        assert len(args) == len(decl), name
-        for a, d in zip(args, decl):
-            want = N.c_void_p if "*" in d else ctype[d.split()[-2]]
-            assert a is want, (name, d)
+    abi.assert_bound(NEW, L)
 
 
 def test_wgrad_scratch_is_one_slab_per_256_rows(L):

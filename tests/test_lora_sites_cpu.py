@@ -4,6 +4,7 @@ module's weight version into a base and an adapter part, and `cross_attention_kw
 import pytest
 import torch
 
+import abi
 import lora_cases as LC
 from consistencytta_amd import _native as N
 from consistencytta_amd import modules, spec
@@ -43,9 +44,7 @@ def site_shapes(cfg, r):
 
 
 def test_the_new_symbols_are_exported():
-    L = N.lib()
-    for name in NEW:
-        assert name in N.SIGNATURES and hasattr(L, name), name
+    abi.assert_bound(NEW)
 
 
 @pytest.mark.parametrize("cfg", [spec.LIGHT_UNET_CONFIG, FULL], ids=["light", "full"])

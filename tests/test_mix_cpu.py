@@ -6,6 +6,7 @@ import random
 import numpy as np
 import pytest
 
+import abi
 from consistencytta_amd import _native as N
 from consistencytta_amd import data
 
@@ -92,7 +93,5 @@ def test_library_rejects_invalid_mixer_arguments(built_lib):
 
 
 def test_mixer_entry_points_are_declared_and_exported(built_lib):
-    for name in MIX_SYMBOLS:
-        assert name in N.SIGNATURES
-        assert hasattr(built_lib, name)
+    abi.assert_bound(MIX_SYMBOLS, built_lib)
     assert built_lib.ctta_version() == 100

@@ -1294,14 +1294,6 @@ def test_errors_are_loud():
         N.check(lib().ctta_conv_gemm(ctypes.byref(d), N.stream_ptr()))
 
 
-class _PackJob(ctypes.Structure):
-    """ctta_pack_job of include/ctta.h."""
-    _fields_ = [("src", ctypes.c_void_p), ("row_off", ctypes.c_void_p), ("col_off", ctypes.c_void_p),
-                ("row_aux", ctypes.c_void_p), ("col_aux", ctypes.c_void_p), ("aux_limit", ctypes.c_int),
-                ("n_rows", ctypes.c_int), ("k_pad", ctypes.c_int), ("block0", ctypes.c_int),
-                ("dst", ctypes.c_void_p), ("src_row_len", ctypes.c_int), ("rows_per_block", ctypes.c_int)]
-
-
 def _pack_case(name, cout, cin, taps, n_rows, aux_limit, seed):
     """A conv-weight-like job: src (cout, cin, taps) fp32 -> dst [n_rows][k_pad] with k = (tap, cin); some rows
     are zero rows (row_off < 0), the K tail is padding (col_off < 0), optional aux masking."""
@@ -1346,7 +1338,7 @@ def test_pack_weight_tables_match_gather(threads, lds_floats):
              _pack_case("pk.d", 3, lds_floats // 9, 9, 3, 0, 4)]   # one row per block, LDS filled
     keep = []
     for variant in ("rows", "generic"):
-        jobs = (_PackJob * len(cases))()
+        jobs = (N.PackJob * len(cases))()
         blocks = 0
         outs = []
         for i, c in enumerate(cases):

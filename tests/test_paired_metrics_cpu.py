@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import abi
 import cases  # noqa: E402
 import paired_metrics_ref as R  # noqa: E402
 from consistencytta_amd import _native as N  # noqa: E402
@@ -163,12 +164,8 @@ def test_helper_arguments_and_unpaired_result():
 
 
 def test_paired_entry_points_are_declared_and_exported(built_lib):
-    header = open(os.path.join(os.path.dirname(N.CSRC), "..", "include", "ctta.h")).read()
-    for name in PAIRED_SYMBOLS:
-        assert name in N.SIGNATURES
-        assert hasattr(built_lib, name)
-        assert ("ctta_status %s(" % name) in header
-    assert "ctta_ssim_tiles" in N.SIGNATURES and "int64_t ctta_ssim_tiles(" in header
+    abi.assert_bound(tuple(PAIRED_SYMBOLS) + ("ctta_ssim_tiles",), built_lib)
+    assert N.FUNCTIONS["ctta_ssim_tiles"].c_restype == "int64_t"
     assert built_lib.ctta_ssim_tiles(7, 7, 7) == 1 and built_lib.ctta_ssim_tiles(30, 38, 7) == 1
     assert built_lib.ctta_ssim_tiles(31, 39, 7) == 4 and built_lib.ctta_ssim_tiles(6, 9, 7) == 0
-    assert "#define CTTA_PAIR_MAX 256" in header
+    assert N.CONSTANTS["CTTA_PAIR_MAX"] == 256

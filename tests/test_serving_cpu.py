@@ -3,8 +3,8 @@ range checks for `capture_graph(from_tokens=True)`, the `step_noise` shape check
 import pytest
 import torch
 
+import abi
 import cases
-from consistencytta_amd import _native as N
 from consistencytta_amd.text_encoder import check_tokens
 
 VOCAB, B, L = cases.TINY_T5["vocab_size"], 2, 8
@@ -75,8 +75,4 @@ def test_step_noise_with_the_wrong_leading_dimension_raises_before_any_launch():
 
 
 def test_renoise_kernel_is_exported_and_bound():
-    assert "ctta_consistency_renoise" in N.SIGNATURES
-    fn = N.lib().ctta_consistency_renoise
-    assert fn.restype is N.c_int and len(fn.argtypes) == 10
-    with open(N.os.path.join(N._HERE, "..", "include", "ctta.h")) as f:
-        assert "ctta_consistency_renoise(" in f.read()
+    abi.assert_bound(("ctta_consistency_renoise",))

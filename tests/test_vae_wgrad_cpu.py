@@ -2,13 +2,12 @@
 new entries, the implicit kernel's range grew by width 64 and by nothing else, and the scratch sizes are what the launchers
 use."""
 import os
-import re
 
 import pytest
 
+import abi
 from consistencytta_amd import _native as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ctta_conv_cout1_wgrad", "ctta_conv_cout1_wgrad_scratch_floats", "ctta_post_quant_wgrad",
        "ctta_post_quant_wgrad_scratch_floats", "ctta_upsample2_nearest")
 
@@ -21,12 +20,7 @@ def L():
 
 
 def test_header_signatures_and_library_agree_on_the_new_entries(L):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ctta.h")).read(), flags=re.S)
-    for name in NEW:
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, header)
-        assert m, "%s is not declared in include/ctta.h" % name
-        assert name in N.SIGNATURES and hasattr(L, name)
-        assert len(N.SIGNATURES[name][1]) == len(m.group(1).split(",")), name
+    abi.assert_bound(NEW, L)
 
 
 def test_implicit_range_grew_by_width_64_only(L):

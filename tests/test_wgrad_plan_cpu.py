@@ -15,10 +15,10 @@ some layer launches, or what scratch it takes, changes one of these."""
 import ctypes
 import json
 import os
-import re
 
 import pytest
 
+import abi
 from consistencytta_amd import _native as N
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,15 +75,4 @@ def test_plan_equals_recorded_decision(lib, case):
 
 
 def test_header_signatures_and_library_agree_on_the_new_entries(lib):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ctta.h")).read(), flags=re.S)
-    for name in ("ctta_wgrad_plan", "ctta_wgrad_engine_policy"):
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, header)
-        assert m, "%s is not declared in include/ctta.h" % name
-        assert name in N.SIGNATURES and hasattr(lib, name)
-        assert len(N.SIGNATURES[name][1]) == len(m.group(1).split(",")), name
-    # the ctypes structs have the header's fields, in the header's order
-    for struct, cls in (("ctta_wgrad_geom", N.WgradGeom), ("ctta_wgrad_policy", N.WgradPolicy), ("ctta_wgrad_plan_info", N.WgradPlanInfo)):
-        body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, header).group(1)
-        fields = [f.strip() for decl in body.split(";") for f in re.sub(r"^\s*(int64_t|int)\s", "", decl).split(",") if f.strip()]
-        assert fields == [f for f, _ in cls._fields_], struct
-        assert all((t is ctypes.c_int64) == bool(re.search(r"int64_t[^;]*\b%s\b" % f, body)) for f, t in cls._fields_), struct
+    abi.assert_bound(("ctta_wgrad_plan", "ctta_wgrad_engine_policy"), lib)
