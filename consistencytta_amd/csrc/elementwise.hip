@@ -192,6 +192,70 @@ __global__ void cfg_combine_keep_kernel(const float4* __restrict__ u, const floa
   }
 }
 
+// consistency_renoise_kernel for a clip longer than the student's window: the queries ran on n_windows overlapping windows
+// of window_h rows of ONE long latent (row b * n_windows + k of the query batch is window k of clip b), and the step between
+// two queries gathers the windows' x0 estimates under each long row, fuses them with the plan's weights (a weighted
+// overlap-add whose weights sum to 1 per long row), re-noises the long x0 with one long draw and scatters the result back
+// into the next windows.  One thread walks LONG float4s, so every window element is written exactly once, by the thread
+// that owns its long element: no atomics, no second pass.  The window starts travel in the launch arguments (a capture's
+// layout is static); a thread visits the windows in ascending k.  The fp32 operations are those of torch's combine, torch's
+// mul per window, torch's add per further window, heun_add_noise_kernel and heun_scale_kernel, in their order.
+// MODE 0: cond alone; 1: uncond + cond; 2: no query output yet, x0 = 0 (the sampler's start).  COPIES 0: the sampler's end,
+// nothing is re-noised and only x0_long is written.
+#define CTTA_MAX_WINDOWS 16
+struct WindowStarts { int s[CTTA_MAX_WINDOWS]; };
+
+template <int MODE, int COPIES>
+__global__ void window_fuse_renoise_kernel(const float4* __restrict__ c, const float4* __restrict__ u,
+                                           const float* __restrict__ w, const WindowStarts st,
+                                           const float* __restrict__ wt, const float4* __restrict__ nz,
+                                           const float* __restrict__ sigma, float4* __restrict__ x0_long,
+                                           float4* __restrict__ out, int n_windows, int channels, int window_h, int latent_h,
+                                           int wv, long long total, long long out_total) {
+  VEC_LOOP(total) {
+    const int xv = (int)(i % wv);
+    long long r = i / wv;
+    const int h = (int)(r % latent_h);
+    r /= latent_h;
+    const int ch = (int)(r % channels);
+    const int b = (int)(r / channels);
+    float ww = 0.f, a = 0.f;
+    if (MODE == 1) { ww = w[b]; a = 1.0f - ww; }
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool first = true;
+    for (int k = 0; k < n_windows; ++k) {
+      const int j = h - st.s[k];
+      if ((unsigned)j >= (unsigned)window_h) continue;
+      const long long p = ((((long long)b * n_windows + k) * channels + ch) * window_h + j) * wv + xv;
+      const float g = wt[k * window_h + j];
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (MODE != 2) x = c[p];
+      if (MODE == 1) {
+        const float4 uu = u[p];
+        x = make_float4(a * uu.x + ww * x.x, a * uu.y + ww * x.y, a * uu.z + ww * x.z, a * uu.w + ww * x.w);
+      }
+      const float4 t = make_float4(g * x.x, g * x.y, g * x.z, g * x.w);
+      acc = first ? t : make_float4(acc.x + t.x, acc.y + t.y, acc.z + t.z, acc.w + t.w);
+      first = false;
+    }
+    if (x0_long) x0_long[i] = acc;
+    if (COPIES > 0) {
+      const float s = sigma[b];
+      const float d = sqrtf(s * s + 1.0f);
+      const float4 n = nz[i];
+      float4 z = make_float4(acc.x + n.x * s, acc.y + n.y * s, acc.z + n.z * s, acc.w + n.w * s);
+      z.x /= d; z.y /= d; z.z /= d; z.w /= d;
+      for (int k = 0; k < n_windows; ++k) {
+        const int j = h - st.s[k];
+        if ((unsigned)j >= (unsigned)window_h) continue;
+        const long long p = ((((long long)b * n_windows + k) * channels + ch) * window_h + j) * wv + xv;
+        out[p] = z;
+        if (COPIES == 2) out[out_total + p] = z;
+      }
+    }
+  }
+}
+
 // out = a[b]*x + b_[b]*y per sample (optionally clamped): DDPM/DDIM add_noise and the v-prediction step pieces
 __global__ void lincomb2_kernel(const float4* __restrict__ x, const float4* __restrict__ y, const float* __restrict__ a,
                                 const float* __restrict__ b_, float4* __restrict__ out, long long nvec_per, long long total,
@@ -615,6 +679,54 @@ extern "C" ctta_status ctta_cfg_combine_keep(const float* uncond, const float* c
                      (float4*)out, nv, hwv, total)
   if (uncond) COMBINE_KEEP(true); else COMBINE_KEEP(false);
 #undef COMBINE_KEEP
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_window_fuse_renoise(const float* cond, const float* uncond, const float* w_post,
+                                                const int32_t* starts, const float* weights, const float* noise,
+                                                const float* sigma, float* x0_long, float* out, int copies, int batch,
+                                                int n_windows, int channels, int window_h, int latent_h, int width,
+                                                void* stream) {
+  CTTA_REQUIRE(starts && weights, "window_fuse_renoise: starts and weights are both required");
+  CTTA_REQUIRE((uncond != nullptr) == (w_post != nullptr),
+               "window_fuse_renoise: uncond and w_post are given together or not at all");
+  CTTA_REQUIRE(!uncond || cond, "window_fuse_renoise: uncond without cond");
+  CTTA_REQUIRE((noise != nullptr) == (out != nullptr),
+               "window_fuse_renoise: noise and out are given together (a step) or not at all (the end)");
+  CTTA_REQUIRE(out ? sigma != nullptr : x0_long != nullptr,
+               "window_fuse_renoise: a step needs sigma, the end (noise == out == NULL) needs x0_long");
+  CTTA_REQUIRE(copies == 1 || copies == 2, "window_fuse_renoise: copies=%d (1 or 2)", copies);
+  CTTA_REQUIRE(batch > 0 && channels > 0 && window_h > 0 && latent_h > 0 && width > 0, "window_fuse_renoise: empty tensor");
+  CTTA_REQUIRE(width % 4 == 0, "window_fuse_renoise: width=%d must be a multiple of 4", width);
+  CTTA_REQUIRE(n_windows >= 1 && n_windows <= CTTA_MAX_WINDOWS, "window_fuse_renoise: n_windows=%d (1 .. %d)", n_windows,
+               CTTA_MAX_WINDOWS);
+  CTTA_REQUIRE(starts[0] == 0, "window_fuse_renoise: starts[0]=%d must be 0", (int)starts[0]);
+  CTTA_REQUIRE(starts[n_windows - 1] == latent_h - window_h,
+               "window_fuse_renoise: the last start %d must be latent_h - window_h = %d", (int)starts[n_windows - 1],
+               latent_h - window_h);
+  WindowStarts st;
+  for (int k = 0; k < CTTA_MAX_WINDOWS; ++k) st.s[k] = k < n_windows ? (int)starts[k] : 0;
+  for (int k = 0; k + 1 < n_windows; ++k) {
+    CTTA_REQUIRE(st.s[k + 1] > st.s[k], "window_fuse_renoise: starts[%d]=%d, starts[%d]=%d are not strictly increasing", k,
+                 st.s[k], k + 1, st.s[k + 1]);
+    CTTA_REQUIRE(st.s[k + 1] <= st.s[k] + window_h, "window_fuse_renoise: a gap between starts[%d]=%d + window_h=%d and "
+                 "starts[%d]=%d", k, st.s[k], window_h, k + 1, st.s[k + 1]);
+  }
+  // starts[0] = 0, strictly increasing without gaps up to latent_h - window_h >= 0: every long row lies under a window and
+  // every window lies inside the clip
+  const int wv = width / 4;
+  const long long total = (long long)batch * channels * latent_h * wv;
+  const long long out_total = (long long)batch * n_windows * channels * window_h * wv;
+#define FUSE(MODE, CP)                                                                                                 \
+  hipLaunchKernelGGL((window_fuse_renoise_kernel<MODE, CP>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,  \
+                     (const float4*)cond, (const float4*)uncond, w_post, st, weights, (const float4*)noise, sigma,      \
+                     (float4*)x0_long, (float4*)out, n_windows, channels, window_h, latent_h, wv, total, out_total)
+#define FUSE_MODE(CP)                                                                                                  \
+  do { if (!cond) FUSE(2, CP); else if (uncond) FUSE(1, CP); else FUSE(0, CP); } while (0)
+  if (!out) FUSE_MODE(0); else if (copies == 2) FUSE_MODE(2); else FUSE_MODE(1);
+#undef FUSE_MODE
+#undef FUSE
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
 }

@@ -353,6 +353,53 @@ def _post_cfg_combine_keep(zh, B, w_post, w_dev, src, keep):
     return out
 
 
+LONG_MAX_WINDOWS = 16          # ctta_window_fuse_renoise carries the window starts in its launch arguments
+LONG_MAX_LATENT_H = 1024       # the VAE mid-block keeps a (16 H)^2 fp32 score slab per sample: 1 GiB here, nothing taller has run
+LONG_DECODE_ROWS = 32 * 256    # rows * latent_h of one decoder / vocoder call of the long-clip entries
+
+
+def _long_latent_h(duration):
+    """Seconds -> latent rows of the long-clip entries: `duration_to_latent_t_size` (audioldm/pipeline.py:49-50, 25.6 rows
+    per second) rounded up to a multiple of 8, the U-Net's three halvings.  `duration` lies in [2.5, 40] s (64 .. 1024
+    rows)."""
+    d = float(duration)
+    if not 2.5 <= d <= 40.0:
+        raise ValueError("duration %r: expected seconds in [2.5, 40.0]" % (duration,))
+    return 8 * int(math.ceil(round(d * 25.6 / 8, 9)))      # rounded first: 7.5 s is 192 rows whatever 7.5 * 25.6 gives in binary
+
+
+def _window_rows(states, B, n, what):
+    """Text states / masks of the long-clip sampler as B * n rows, row b * n + k: B rows are repeated per window, B * n rows
+    give every window its own."""
+    if states is None or states.shape[0] not in (B, B * n):
+        got = None if states is None else tuple(states.shape)
+        raise ValueError("%s %s: expected %d rows (repeated per window) or %d (one per window)" % (what, got, B, B * n))
+    return states.repeat_interleave(n, 0) if states.shape[0] == B and n > 1 else states
+
+
+def _window_fuse(zh, B, w_post, w_dev, plan, draw, sig, latent_h, z_in=None, x0_long=None):
+    """`_student_next_input` for a clip of `latent_h` rows queried as n overlapping windows (rows b * n + k of `zh`): the
+    post-CFG combine per window, the weighted overlap-add into one long x0, add_noise with ONE long draw,
+    scale_model_input, the cut into the next windows and the 2 x stacking in ONE launch (ctta_window_fuse_renoise).  `zh`
+    None: the sampler's start, x0 = 0.  `draw` and `z_in` None: the sampler's end, the fused x0 goes to `x0_long`.
+    `plan`: (host int32 array of starts, (n, window_h) device weights)."""
+    starts, weights = plan
+    n, wh = weights.shape
+    use_cf = w_post > 1.
+    if zh is None:
+        cond, unc = None, None
+    elif use_cf and _post_cfg_fusable(w_post):
+        cond, unc = zh[B * n:], zh[:B * n]
+    elif use_cf:
+        cond, unc = (1 - w_post) * zh[:B * n] + w_post * zh[B * n:], None
+    else:
+        cond, unc = zh, None
+    C, W = (x0_long if z_in is None else z_in).shape[1], (x0_long if z_in is None else z_in).shape[3]
+    N.check(N.lib().ctta_window_fuse_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
+                                             starts, N.ptr(weights), N.ptr(draw), N.ptr(sig), N.ptr(x0_long), N.ptr(z_in),
+                                             2 if use_cf else 1, B, n, C, wh, latent_h, W, N.stream_ptr()))
+
+
 class AudioDistilledModel(nn.Module):
     """models/audio_distilled_model.py: text encoding, CFG teacher query, EMA bookkeeping."""
 
@@ -2271,6 +2318,218 @@ class ConsistencyTTA(nn.Module):
             return out[2]
 
         replay.graph, replay.outputs, replay.queries = graph, out, r
+        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
+        return replay
+
+    # ---- long and short clips: overlapping windows of one long latent, fused between two queries of the few-step sampler
+    # (the `duration` of audioldm/pipeline.py:49-50,94-95; the fusion is MultiDiffusion's, in consistency-sampling terms)
+    @staticmethod
+    def long_plan(latent_h, window_h=256, overlap=64):
+        """How a latent of `latent_h` rows is covered by windows of `window_h` rows that share about `overlap` rows with
+        each neighbour: (starts, weights).  `starts`: n ascending first rows, evenly spread from 0 to latent_h - window_h
+        (integer round-half-up).  `weights`: (n, window_h) fp32; the raw weight of window k at its row j ramps over the
+        overlaps with its neighbours, min(1, (j + 1) / (ovl + 1)) * min(1, (window_h - j) / (ovr + 1)), and is divided in
+        float64 by the sum over the windows covering that long row, so a long row's weights sum to 1 and a row under one
+        window weighs exactly 1.  latent_h <= window_h: ONE window of latent_h rows, weights (1, latent_h) of ones.
+        Raises ValueError for rows that are no multiples of 8, an overlap outside [0, window_h), more than 1024 rows or
+        more than 16 windows."""
+        latent_h, window_h, overlap = int(latent_h), int(window_h), int(overlap)
+        if latent_h <= 0 or window_h <= 0 or latent_h % 8 or window_h % 8:
+            raise ValueError("latent_h %d / window_h %d: expected positive multiples of 8" % (latent_h, window_h))
+        if not 0 <= overlap < window_h:
+            raise ValueError("overlap %d: expected 0 <= overlap < window_h = %d" % (overlap, window_h))
+        if latent_h > LONG_MAX_LATENT_H:
+            raise ValueError("latent_h %d: at most %d rows" % (latent_h, LONG_MAX_LATENT_H))
+        if latent_h <= window_h:
+            return [0], torch.ones(1, latent_h, dtype=torch.float32)
+        span = latent_h - window_h
+        n = -(-span // (window_h - overlap)) + 1
+        if n > LONG_MAX_WINDOWS:
+            raise ValueError("latent_h %d, window_h %d, overlap %d: %d windows, at most %d"
+                             % (latent_h, window_h, overlap, n, LONG_MAX_WINDOWS))
+        starts = [(2 * k * span + (n - 1)) // (2 * (n - 1)) for k in range(n)]
+        j = np.arange(window_h, dtype=np.float64)
+        raw = np.empty((n, window_h), dtype=np.float64)
+        total = np.zeros(latent_h, dtype=np.float64)
+        for k, s in enumerate(starts):
+            ovl = starts[k - 1] + window_h - s if k > 0 else 0
+            ovr = s + window_h - starts[k + 1] if k < n - 1 else 0
+            raw[k] = np.minimum(1.0, (j + 1) / (ovl + 1)) * np.minimum(1.0, (window_h - j) / (ovr + 1))
+            total[s:s + window_h] += raw[k]
+        weights = np.stack([raw[k] / total[s:s + window_h] for k, s in enumerate(starts)]).astype(np.float32)
+        return starts, torch.from_numpy(weights)
+
+    @torch.no_grad()
+    def generate_long_latent(self, encoder_states, encoder_mask, noise, cfg_scale_input=3., cfg_scale_post=1., num_steps=4,
+                             overlap=64, window_h=256, uncond_states=None, uncond_mask=None, step_noise=None):
+        """`generate_latent` for a latent of another height: `noise` is (B, C, Ht, W), and the student -- distilled at
+        `window_h` rows -- is queried on the n overlapping windows of `long_plan(Ht, window_h, overlap)` as B * n rows of
+        one batch (row b * n + k).  Between two queries the windows' x0 estimates are fused into one long x0, re-noised
+        with ONE long draw and cut into the next windows; the start, every such step and the end are one launch each of
+        ctta_window_fuse_renoise.  The query times are `generate_latent`'s.  Text states of B rows are repeated per
+        window; B * n rows give every window its own (the uncond states likewise).  `step_noise`:
+        (num_steps - 1, B, C, Ht, W), None draws it.  num_steps == 1 is a weighted cross-fade of independent windows.
+        Ht <= window_h is one window of Ht rows: Ht == window_h equals `generate_latent` bit for bit.  Returns the fused
+        (B, C, Ht, W) latent."""
+        if not torch.is_tensor(noise) or noise.ndim != 4:
+            raise ValueError("noise %s: expected (B, C, Ht, W)" % (tuple(noise.shape) if torch.is_tensor(noise) else noise,))
+        _check_step_noise(step_noise, int(num_steps) - 1, noise)
+
+        def draw(k):
+            if k == 0:
+                return noise
+            return torch.randn_like(noise) if step_noise is None else step_noise[k - 1]
+        return self._long_loop(encoder_states, encoder_mask, draw, tuple(noise.shape), cfg_scale_input, cfg_scale_post,
+                               num_steps, overlap, window_h, uncond_states, uncond_mask)
+
+    def _long_loop(self, encoder_states, encoder_mask, draw, shape, cfg_scale_input, cfg_scale_post, num_steps, overlap,
+                   window_h, uncond_states, uncond_mask):
+        """The body of `generate_long_latent` and of the captured long path: nothing but launches once `draw(k)`, the k-th
+        long noise, is a tensor at hand.  Queries after the first take the text K / V from the handle's cache (the text
+        states are the same tensors for the whole call)."""
+        sch = self.scheduler
+        num_steps = int(num_steps)
+        if num_steps < 1:
+            raise ValueError("num_steps must be at least 1, got %d" % num_steps)
+        B, C, Ht, W = shape
+        starts, weights = self.long_plan(Ht, window_h, overlap)
+        n, wh = weights.shape
+        use_cf = cfg_scale_post > 1.
+        enc, mask = _window_rows(encoder_states, B, n, "encoder_states"), _window_rows(encoder_mask, B, n, "encoder_mask")
+        if use_cf:
+            enc = torch.cat([_window_rows(uncond_states, B, n, "uncond_states"), enc])
+            mask = torch.cat([_window_rows(uncond_mask, B, n, "uncond_mask"), mask])
+        first = sch._check(draw(0))
+        dev = first.device
+        # the weights are uploaded once per layout and device: a capture's warm-up run leaves them here, so the recorded
+        # sequence holds no host -> device copy
+        cache = self.__dict__.setdefault("_long_weights", {})
+        key = (Ht, wh, n, int(overlap), str(dev))
+        if key not in cache:
+            cache[key] = weights.to(dev)
+        plan = ((N.c_int32 * n)(*starts), cache[key])
+        w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev) if use_cf else None
+        sch.set_timesteps(18, device=dev)
+        t_head = float(sch._timesteps_host[0])
+        sig = sch._sigma_dev(sch.index_for_timestep(t_head), B, dev)
+        sch.set_timesteps(num_steps, device=dev)
+        times = [t_head] + [float(v) for v in sch._timesteps_host[1::2]]
+        copies = 2 if use_cf else 1
+        z_in = torch.empty((copies * B * n, C, wh, W), dtype=torch.float32, device=dev)
+        _window_fuse(None, B, cfg_scale_post, w_post, plan, first, sig, Ht, z_in=z_in)
+        for k, t in enumerate(times):
+            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=enc, encoder_attention_mask=mask,
+                           reuse_text=k > 0).sample
+            if k == num_steps - 1:
+                break
+            sig = sch._sigma_dev(sch.index_for_timestep(times[k + 1]), B, dev)
+            z_in = torch.empty_like(zh)
+            _window_fuse(zh, B, cfg_scale_post, w_post, plan, sch._check(draw(k + 1)), sig, Ht, z_in=z_in)
+        out = torch.empty((B, C, Ht, W), dtype=torch.float32, device=dev)
+        _window_fuse(zh, B, cfg_scale_post, w_post, plan, None, None, Ht, x0_long=out)
+        return out
+
+    def _decode_long(self, lat, scratch=None, chunk_rows=LONG_DECODE_ROWS):
+        """Long latent -> (mel, int16 waveform on the device): `decode_first_stage`, `vocode` and vocoder_infer's
+        batch-global centring.  The batch is cut into chunks of at most chunk_rows // Ht clips per decoder / vocoder call;
+        the centring stays over the WHOLE batch: per-chunk extrema (ctta_wav_extrema), their maximum / minimum, then
+        ctta_wav_center per chunk with that pair -- the arithmetic of ctta_wav_finalize on the whole batch.  `scratch`:
+        the kernels' work buffer (4 floats), the caller's in a capture."""
+        B, Ht = lat.shape[0], lat.shape[2]
+        per = max(1, int(chunk_rows) // Ht)
+        dev = lat.device
+        if scratch is None:
+            scratch = torch.empty(4, dtype=torch.float32, device=dev)
+        L_ = N.lib()
+        mels = [self.vae.decode_first_stage(lat[i:i + per]) for i in range(0, B, per)]
+        wavs = [self.vae.vocode(m) for m in mels]
+        pcm = torch.empty((B, wavs[0].shape[1]), dtype=torch.int16, device=dev)
+        with torch.cuda.device(dev):
+            if len(wavs) == 1:
+                N.check(L_.ctta_wav_finalize(N.ptr(wavs[0]), wavs[0].numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
+                return mels[0], pcm
+            mm = torch.empty(len(wavs), 2, dtype=torch.float32, device=dev)
+            for i, w in enumerate(wavs):
+                N.check(L_.ctta_wav_extrema(N.ptr(w), w.numel(), N.ptr(scratch), N.ptr(mm[i]), N.stream_ptr()))
+            both = torch.stack([mm[:, 0].max(), mm[:, 1].min()])
+            for i, w in enumerate(wavs):
+                N.check(L_.ctta_wav_center(N.ptr(w), w.numel(), N.ptr(both), N.ptr(scratch), None, N.ptr(pcm[i * per:]),
+                                           N.stream_ptr()))
+        return torch.cat(mels), pcm
+
+    @torch.no_grad()
+    def generate_long_from_embeds(self, encoder_states, encoder_mask, noise, duration, cfg_scale_input=3., cfg_scale_post=1.,
+                                  num_steps=4, sr=16000, step_noise=None, overlap=64, window_h=256,
+                                  _chunk_rows=LONG_DECODE_ROWS, **kw):
+        """`forward_from_embeds` for a clip of `duration` seconds in [2.5, 40]: `noise` is (B, C, Ht, W) with
+        Ht = 8 * ceil(duration * 25.6 / 8) rows (audioldm/pipeline.py:49-50), `generate_long_latent`, the VAE decoder and
+        HiFi-GAN at that extent -- chunked over the batch, centred over the whole batch --, cut to int(sr * duration)
+        samples.  int16 waveforms (numpy)."""
+        self.check_eval_mode()
+        Ht = _long_latent_h(duration)
+        if not torch.is_tensor(noise) or noise.ndim != 4 or noise.shape[2] != Ht:
+            raise ValueError("noise %s: a clip of %r s takes (B, C, %d, W)"
+                             % (tuple(noise.shape) if torch.is_tensor(noise) else noise, duration, Ht))
+        lat = self.generate_long_latent(encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps,
+                                        overlap, window_h, step_noise=step_noise, **kw)
+        _, pcm = self._decode_long(lat, chunk_rows=_chunk_rows)
+        return pcm.cpu().numpy()[:, :int(sr * float(duration))]
+
+    @torch.no_grad()
+    def generate_long(self, prompt, duration, cfg_scale_input=3., cfg_scale_post=1., num_steps=4, num_samples=1, sr=16000,
+                      overlap=64):
+        """`forward` with a duration: prompts -> int16 waveforms (numpy) of int(sr * duration) samples, 2.5 .. 40 s."""
+        self.check_eval_mode()
+        Ht = _long_latent_h(duration)
+        embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
+        B = embeds.shape[0]
+        noise = randn_tensor((B, self.unet.config.in_channels, Ht, 16), device=embeds.device, dtype=torch.float32)
+        kw = {}
+        if cfg_scale_post > 1.:
+            kw = dict(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        return self.generate_long_from_embeds(embeds, mask, noise, duration, cfg_scale_input, cfg_scale_post, num_steps, sr,
+                                              overlap=overlap, **kw)
+
+    @torch.no_grad()
+    def capture_long_graph(self, batch, text_len, duration, cfg_scale_input=3., num_steps=4, cfg_scale_post=1., overlap=64,
+                           window_h=256, cross_attention_dim=1024, latent_cw=(8, 16), sr=16000, uncond_states=None,
+                           uncond_mask=None, _chunk_rows=LONG_DECODE_ROWS):
+        """`capture_graph` for a clip of `duration` seconds: the windowed few-step sampler of `generate_long_latent`, the
+        VAE decoder, HiFi-GAN and the int16 conversion as ONE hipGraph.  Returns `f(encoder_states, encoder_mask, noise) ->
+        pcm` (int16 on the device, int(sr * duration) samples); `noise` is (num_steps, B, C, Ht, W), row 0 the initial
+        draw and rows 1.. the step noise; every argument is copied into static inputs ((B, L, D) text states, repeated per
+        window).  The window layout is part of the capture.  Bit-identical to `generate_long_from_embeds(...,
+        step_noise=noise[1:])`.  As with every capture, the graph holds the addresses of the engine handles it was recorded
+        on, and the VAE keeps ONE decoder and ONE vocoder handle, re-created for another extent: a clip of another length
+        decoded on this module afterwards -- eagerly or by another capture -- frees what this graph replays.  Captures of
+        different durations need a module each (tools/serve_bench.py --long builds two)."""
+        self.check_eval_mode()
+        dev = self.unet.device
+        Ht = _long_latent_h(duration)
+        self.long_plan(Ht, window_h, overlap)
+        C, W = latent_cw
+        st, load = self._serving_inputs(batch, text_len, cross_attention_dim, (C, Ht, W), num_steps, cfg_scale_post,
+                                        uncond_states, uncond_mask, False)
+        # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
+        st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
+        samples = int(sr * float(duration))
+
+        def run():
+            lat = self._long_loop(st["enc"], st["mask"], lambda k: st["noise"][k], (batch, C, Ht, W), cfg_scale_input,
+                                  cfg_scale_post, num_steps, overlap, window_h, st.get("unc"), st.get("unc_mask"))
+            mel, pcm = self._decode_long(lat, st["scratch"], _chunk_rows)
+            return lat, mel, pcm
+
+        _warm_up(run, dev)
+        graph, out = _capture(run)
+
+        def replay(*args):
+            load(*args)
+            graph.replay()
+            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
+            return out[2][:, :samples]
+
+        replay.graph, replay.outputs, replay.latent_h = graph, out, Ht
         replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
         return replay
 

@@ -374,6 +374,28 @@ ctta_status ctta_consistency_edit_renoise(const float* cond, const float* uncond
                                           int copies, int batch, int64_t n_per_sample, int64_t hw, void* stream);
 ctta_status ctta_cfg_combine_keep(const float* uncond, const float* cond, const float* w, const float* src,
                                   const float* keep, float* out, int batch, int64_t n_per_sample, int64_t hw, void* stream);
+/* The same step for a clip longer than the student's window (the `duration` of audioldm/pipeline.py:49-50,94-95 in the
+ * few-step sampler's terms): the student is queried on n_windows overlapping windows of window_h rows of ONE long latent of
+ * latent_h rows, as rows of one batch, and between two queries the windows' x0 estimates are fused into one long x0,
+ * re-noised with one long draw and cut into the next windows.  cond / uncond are (batch * n_windows, C, window_h, W), row
+ * b * n_windows + k; noise and x0_long are (batch, C, latent_h, W); out is (copies * batch * n_windows, C, window_h, W), the
+ * same row order stacked `copies` (1 or 2) times.  Per long element (b, c, h, x), over the windows k that cover row h
+ * (starts[k] <= h < starts[k] + window_h), in ascending k, every multiply and every add rounded on its own:
+ *   x_k = uncond == NULL ? cond : (1 - w_post[b]) * uncond + w_post[b] * cond      (as ctta_consistency_renoise)
+ *   acc = weights[k0][h - starts[k0]] * x_k0;   acc = acc + weights[k][h - starts[k]] * x_k   (k > k0)
+ *   z   = acc + noise * sigma[b];   o = z / sqrt(sigma[b]^2 + 1)
+ * and o is written to out at (b * n_windows + k, c, h - starts[k], x) for every covering k and every copy; acc is written
+ * to x0_long when that is given.  One pass over the long elements: every window element is written exactly once.
+ * starts is a HOST array of n_windows (<= 16) int32, copied into the launch arguments: it begins with 0, ends with
+ * latent_h - window_h, increases strictly and leaves no gap (starts[k + 1] <= starts[k] + window_h).  weights is
+ * (n_windows, window_h) f32 on the device; sigma and w_post are (batch) f32 on the device; width % 4 == 0.
+ * cond == NULL (then uncond must be NULL too) means x0 = 0: the sampler's start, pure noise cut into windows.
+ * noise == NULL and out == NULL together: the sampler's end, only x0_long (then required) is written.  uncond and w_post
+ * are given together or not at all. */
+ctta_status ctta_window_fuse_renoise(const float* cond, const float* uncond, const float* w_post, const int32_t* starts,
+                                     const float* weights, const float* noise, const float* sigma, float* x0_long,
+                                     float* out, int copies, int batch, int n_windows, int channels, int window_h,
+                                     int latent_h, int width, void* stream);
 /* get_loss with MSELoss('instance') and SNR clamp (models/audio_consistency_model.py:250-266,
  * tools/losses.py:28-33): loss = mean_b( mean((pred-target)^2) * min(sigma^-2, gamma) ).
  * gamma <= 0 disables the weighting.  loss: 1 float on device. */

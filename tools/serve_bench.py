@@ -24,6 +24,12 @@ every form alike; the JSON keeps every window, the median and the ratios of medi
 `--edit-steps` queries, and the one-pass step kernel beside the launches it replaces (see `edit_leg`):
 
   python tools/serve_bench.py --edit --out profiles/edit_serving.json
+
+`--long [--duration 30.72]` runs the long-clip leg alone: the captured long path (8 clips x 4 windows by default) beside the
+captured plain few-step path at the same number of U-Net rows (batch 32), and the one-pass window step beside the launches
+it replaces (see `long_leg`):
+
+  python tools/serve_bench.py --long --out profiles/long_serving.json
 """
 import argparse
 import json
@@ -193,8 +199,193 @@ def edit_leg(args):
             f.write(json.dumps(result, indent=1) + "\n")
 
 
+def long_leg(args):
+    """`--long`: the captured long-clip path (capture_long_graph: `--long-clips` clips of `--duration` seconds, each queried
+    as n overlapping windows) beside the captured plain few-step path (capture_graph) at the SAME number of U-Net rows
+    (clips x windows clips of the model's own length), states in, at `--edit-steps` queries, in alternating windows; the
+    eager forms of both; and the one-pass step kernel (ctta_window_fuse_renoise) beside the launches it replaces (torch
+    combine, slices, torch weighted sum, ctta_heun_add_noise, ctta_heun_scale_model_input, the cut into windows,
+    torch.cat) on one long batch.  The two paths decode different extents (clips x Ht rows against clips x windows x
+    window rows); the JSON names both."""
+    import torch
+    from consistencytta_amd import _native as N
+    from consistencytta_amd import modules, spec
+    from consistencytta_amd.models import ConsistencyTTA, _long_latent_h
+    dev = "cuda:0"
+    Bl, L, steps = args.long_clips, args.text_len, args.edit_steps
+    if args.tiny:
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        import cases
+        ucfg, (C, wh, W), overlap = dict(cases.TINY_UNET), (8, 32, 16), 8
+        duration = args.duration if args.duration is not None else 3.0
+        make_vae = lambda: modules.AutoencoderKL(ddconfig=cases.TINY_VAE_DD, embed_dim=8, scale_factor=0.9,      # noqa: E731
+                                                 hifigan_config=cases.TINY_HIFIGAN)
+    else:
+        ucfg, (C, wh, W), overlap = spec.LIGHT_UNET_CONFIG, (8, 256, 16), 64
+        duration = args.duration if args.duration is not None else 30.72
+        make_vae = lambda: modules.AutoencoderKL(ddconfig=spec.VAE_DDCONFIG, embed_dim=8,                        # noqa: E731
+                                                 scale_factor=0.9227914214134216)
+    Ht = _long_latent_h(duration)
+    starts, weights = ConsistencyTTA.long_plan(Ht, wh, overlap)
+    n = len(starts)
+    if Ht <= wh:
+        raise SystemExit("--duration %.2f s is one window of %d rows: nothing to fuse" % (duration, Ht))
+    B = Bl * n                                             # the plain path's batch: the same U-Net rows
+    D = ucfg["cross_attention_dim"]
+
+    def build_pipe():
+        v = make_vae()
+        p = ConsistencyTTA(unet_config=ucfg, vae=v)
+        p.to(dev)
+        p.unet.init_random_(seed=0)
+        v.init_random_(seed=1)
+        return p.eval().requires_grad_(False)
+    # one pipe per extent, with the same weights: a module keeps ONE decoder / vocoder handle, re-created for another
+    # (H, W), and a captured graph holds the addresses of the handle it was recorded on -- the long path on the plain
+    # path's module would free what the plain graph replays
+    pipe, pipe_long = build_pipe(), build_pipe()
+    vae = pipe.vae
+    W_IN = 4.0
+    g = torch.Generator(device="cpu").manual_seed(3)
+    batches = []
+    for _ in range(2):
+        lens = torch.randint(min(6, L), L + 1, (B,), generator=g)
+        enc, mask = (torch.randn(B, L, D, generator=g) * 0.25).to(dev), (torch.arange(L)[None, :] < lens[:, None]).to(dev)
+        batches.append({"enc": enc, "mask": mask, "noise": torch.randn((steps, B, C, wh, W), generator=g).to(dev),
+                        "long_enc": enc[:Bl].contiguous(), "long_mask": mask[:Bl].contiguous(),
+                        "long_noise": torch.randn((steps, Bl, C, Ht, W), generator=g).to(dev)})
+    scratch = torch.empty(4, dtype=torch.float32, device=dev)
+    samples = int(16000 * duration)
+
+    def eager_plain(b):
+        lat = pipe.generate_latent(b["enc"], b["mask"], b["noise"][0], W_IN, 1.0, steps, step_noise=b["noise"][1:])
+        wav = vae.vocode(vae.decode_first_stage(lat))
+        pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
+        N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
+        return pcm
+
+    def eager_long(b):
+        lat = pipe_long.generate_long_latent(b["long_enc"], b["long_mask"], b["long_noise"][0], W_IN, 1.0, steps,
+                                             overlap=overlap, window_h=wh, step_noise=b["long_noise"][1:])
+        return pipe_long._decode_long(lat, scratch)[1][:, :samples]
+
+    ref_plain, ref_long = eager_plain(batches[0]).clone(), eager_long(batches[0]).clone()
+    torch.cuda.synchronize()
+    gen_plain = pipe.capture_graph(B, L, cfg_scale_input=W_IN, cross_attention_dim=D, latent=(C, wh, W), num_steps=steps)
+    gen_long = pipe_long.capture_long_graph(Bl, L, duration, cfg_scale_input=W_IN, num_steps=steps, overlap=overlap,
+                                            window_h=wh, cross_attention_dim=D, latent_cw=(C, W))
+    b0 = batches[0]
+    parity = {"plain_graph": bool(torch.equal(gen_plain(b0["enc"], b0["mask"], b0["noise"]), ref_plain)),
+              "long_graph": bool(torch.equal(gen_long(b0["long_enc"], b0["long_mask"], b0["long_noise"]), ref_long))}
+    if not all(parity.values()):
+        raise SystemExit("a captured form differs from its eager counterpart: %s" % parity)
+
+    turn = [0]
+
+    def nxt():
+        turn[0] ^= 1
+        return batches[turn[0]]
+
+    def plain_call():
+        b = nxt()
+        return gen_plain(b["enc"], b["mask"], b["noise"])
+
+    def long_call():
+        b = nxt()
+        return gen_long(b["long_enc"], b["long_mask"], b["long_noise"])
+    forms = {"plain_graph": plain_call, "long_graph": long_call, "plain_eager": lambda: eager_plain(nxt()),
+             "long_eager": lambda: eager_long(nxt())}
+    for fn in forms.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    windows = {k: [] for k in forms}
+    for _ in range(args.rounds):
+        for k, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            windows[k].append((time.perf_counter() - t0) / args.steps * 1e3)
+    med = {k: statistics.median(v) for k, v in windows.items()}
+
+    # ---- the step between two queries alone: one launch against the chain it replaces, device time by events
+    c, u = (torch.randn(Bl * n, C, wh, W, generator=g).to(dev) for _ in range(2))
+    nz = torch.randn(Bl, C, Ht, W, generator=g).to(dev)
+    sig = torch.full((Bl,), 0.7, device=dev)
+    w = torch.full((Bl,), 2.0, device=dev)
+    wdev = weights.to(dev)
+    host_starts = (N.c_int32 * n)(*starts)
+    n_long = C * Ht * W
+    L_ = N.lib()
+
+    def chain(cfg):
+        xw = (((1 - 2.0) * u + 2.0 * c) if cfg else c).view(Bl, n, C, wh, W)
+        x0 = torch.zeros(Bl, C, Ht, W, device=dev)
+        for k, s in enumerate(starts):
+            x0[:, :, s:s + wh] += wdev[k].view(1, 1, wh, 1) * xw[:, k]
+        z, out = torch.empty_like(x0), torch.empty_like(x0)
+        N.check(L_.ctta_heun_add_noise(N.ptr(x0), N.ptr(nz), N.ptr(sig), N.ptr(z), Bl, n_long, N.stream_ptr()))
+        N.check(L_.ctta_heun_scale_model_input(N.ptr(z), N.ptr(sig), N.ptr(out), Bl, n_long, N.stream_ptr()))
+        cut = torch.stack([out[:, :, s:s + wh] for s in starts], dim=1).reshape(Bl * n, C, wh, W)
+        return torch.cat([cut] * 2) if cfg else cut
+
+    def fused(cfg):
+        out = torch.empty(((2 if cfg else 1) * Bl * n, C, wh, W), device=dev)
+        N.check(L_.ctta_window_fuse_renoise(N.ptr(c), N.ptr(u) if cfg else N.c_void_p(0), N.ptr(w) if cfg else N.c_void_p(0),
+                                            host_starts, N.ptr(wdev), N.ptr(nz), N.ptr(sig), N.c_void_p(0), N.ptr(out),
+                                            2 if cfg else 1, Bl, n, C, wh, Ht, W, N.stream_ptr()))
+        return out
+    step_parity = {("cfg" if cfg else "cond"): bool(torch.equal(chain(cfg), fused(cfg))) for cfg in (False, True)}
+    step_forms = {"chain_cond": lambda: chain(False), "fused_cond": lambda: fused(False),
+                  "chain_cfg": lambda: chain(True), "fused_cfg": lambda: fused(True)}
+    step_us = {k: [] for k in step_forms}
+    reps = 200
+    for _ in range(args.rounds + 1):           # the first round warms up and is dropped
+        for k, fn in step_forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            step_us[k].append(e0.elapsed_time(e1) / reps * 1e3)
+    step_med = {k: statistics.median(v[1:]) for k, v in step_us.items()}
+    result = {
+        "tool": "tools/serve_bench.py --long", "device": torch.cuda.get_device_name(0), "tiny": bool(args.tiny),
+        "long": {"clips": Bl, "duration_s": duration, "latent_h": Ht, "window_h": wh, "overlap": overlap, "windows": n,
+                 "starts": starts, "unet_rows": Bl * n, "decoder_rows_x_latent_h": Bl * Ht, "seconds_of_audio": Bl * duration},
+        "plain": {"clips": B, "latent_h": wh, "unet_rows": B, "decoder_rows_x_latent_h": B * wh,
+                  "seconds_of_audio": B * wh * 0.04},
+        "text_len": L, "num_steps": steps, "steps_per_window": args.steps, "rounds": args.rounds, "warmup_calls": args.warmup,
+        "unit": "ms per call of one batch; step kernels: us per step, stream time by events over %d back-to-back steps "
+                "(launch cost included)" % reps,
+        "timing": "host clock around a window of calls ending in a device synchronise; forms alternate within a round",
+        "parity_bit_identical_to_eager": parity, "step_parity_equal": step_parity,
+        "ms_per_call_median": {k: round(v, 3) for k, v in med.items()},
+        "ms_per_call_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()},
+        "ratios_of_medians": {"long_graph_over_plain_graph": round(med["long_graph"] / med["plain_graph"], 4),
+                              "long_eager_over_plain_eager": round(med["long_eager"] / med["plain_eager"], 4),
+                              "long_graph_over_long_eager": round(med["long_graph"] / med["long_eager"], 4)},
+        "step_us_median": {k: round(v, 2) for k, v in step_med.items()},
+        "step_us_windows": {k: [round(x, 2) for x in v[1:]] for k, v in step_us.items()},
+        "step_fused_over_chain": {"cond": round(step_med["fused_cond"] / step_med["chain_cond"], 4),
+                                  "cfg": round(step_med["fused_cfg"] / step_med["chain_cfg"], 4)},
+    }
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--long", action="store_true", help="only the long-clip leg: the captured long path beside the captured "
+                    "plain few-step path at the same number of U-Net rows, and the one-pass step kernel beside its chain")
+    ap.add_argument("--duration", type=float, default=None, help="seconds per clip of the long leg (default 30.72; --tiny: 3.0)")
+    ap.add_argument("--long-clips", type=int, default=8, help="clips per call of the long leg")
     ap.add_argument("--edit", action="store_true", help="only the editing leg: the captured edit path beside the captured "
                     "plain few-step path, and the one-pass step kernel beside the chain it replaces")
     ap.add_argument("--edit-steps", type=int, default=4, help="num_steps of the editing leg")
@@ -215,6 +406,8 @@ def main():
         raise SystemExit("serve_bench needs a GPU: there is no CPU path and no number without one")
     if args.edit:
         return edit_leg(args)
+    if args.long:
+        return long_leg(args)
     dev = "cuda:0"
     B, L = args.batch, args.text_len
 
