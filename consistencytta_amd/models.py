@@ -49,6 +49,62 @@ def _check_step_noise(step_noise, count, noise):
         raise ValueError("step_noise %s: expected %s (one draw per re-noising step)" % (got, want))
 
 
+def _seed_tensor(seeds, count=None, what="seeds"):
+    """`seeds=` of the seeded samplers -> a 1-D int64 tensor, left where it was given (host or device).  A sequence of
+    Python ints may use the whole uint64 range: values from 2^63 up wrap to the int64 of the same bits, which is how the
+    kernel reads a seed.  `count`: the rows it must have.  Raises ValueError before anything is launched."""
+    if torch.is_tensor(seeds):
+        if seeds.dtype != torch.int64 or seeds.ndim != 1:
+            raise ValueError("%s: expected a 1-D int64 tensor, got %s %s" % (what, seeds.dtype, tuple(seeds.shape)))
+        t = seeds.detach()
+    else:
+        try:
+            vals = [int(s) for s in seeds]
+        except TypeError:
+            raise ValueError("%s: expected a sequence of ints or a 1-D int64 tensor, got %s" % (what, type(seeds).__name__))
+        if any(not -(1 << 63) <= v < (1 << 64) for v in vals):
+            raise ValueError("%s: a seed is 64 bits wide, got %r" % (what, vals))
+        t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in vals], dtype=torch.int64)
+    if t.numel() == 0 or (count is not None and t.numel() != int(count)):
+        raise ValueError("%s: %d given, expected %s" % (what, t.numel(), "at least one" if count is None else int(count)))
+    return t
+
+
+def _sample_tensor(samples, count):
+    """`samples=` beside `seeds=`: None (every row is sample 0) or `count` sample indices >= 0 -> 1-D int32 tensor."""
+    if samples is None:
+        return None
+    if torch.is_tensor(samples):
+        if samples.dtype not in (torch.int32, torch.int64) or samples.ndim != 1:
+            raise ValueError("samples: expected a 1-D int32 tensor, got %s %s" % (samples.dtype, tuple(samples.shape)))
+        t = samples.detach().to(torch.int32)
+    else:
+        vals = [int(s) for s in samples]
+        if any(not 0 <= v < (1 << 31) for v in vals):
+            raise ValueError("samples: sample indices are 0 .. 2^31 - 1, got %r" % (vals,))
+        t = torch.tensor(vals, dtype=torch.int32)
+    if t.numel() != int(count):
+        raise ValueError("samples: %d given, expected %d (one per seed)" % (t.numel(), int(count)))
+    return t
+
+
+def _prompt_seeds(seeds, prompt, num_samples):
+    """`seeds=` of the prompt-level entries (one per prompt) -> (seeds, samples) per row: row i * n + m draws with
+    (seeds[i], sample m), the order `encode_text_classifier_free` repeats the text states in."""
+    n = int(num_samples)
+    t = _seed_tensor(seeds, 1 if isinstance(prompt, str) else len(prompt), "seeds (one per prompt)")
+    return t.repeat_interleave(n), torch.arange(n, dtype=torch.int32).repeat(t.numel())
+
+
+def _philox_fill(seeds, samples, draw0, out):
+    """ONE launch of ctta_philox_normal: `out` (draws, B, C, H, W) f32 takes the draws draw0 .. of the rows' (seed, sample)
+    streams.  `seeds` (B) int64 and `samples` (B) int32 or None live on out's device and are read when the kernel RUNS."""
+    draws, B, C, H, W = out.shape
+    with torch.cuda.device(out.device):
+        N.check(N.lib().ctta_philox_normal(N.ptr(seeds), N.ptr(samples), B, int(draw0), draws, C, H, W, 1.0, N.ptr(out),
+                                           N.stream_ptr()))
+
+
 def _post_cfg_fusable(w):
     """Whether the kernels' post-CFG combine (ctta_consistency_renoise, ctta_cfg_combine: a = 1 - w subtracted in fp32) gives
     torch's `(1 - w) * u + w * c` bit for bit: torch rounds the Python double 1 - w to fp32, so the two coefficients are the
@@ -2048,6 +2104,31 @@ class ConsistencyTTA(nn.Module):
             for p in model.parameters():
                 assert p.requires_grad is False, f"The {name} is not frozen."
 
+    # ---- seeded noise: a request's draws as a function of (seed, sample, draw, latent element) and of nothing else
+    @torch.no_grad()
+    def seeded_noise(self, seeds, num_draws, latent=(8, 256, 16), samples=None, draw0=0):
+        """Standard-normal draws of the per-request Philox stream (include/ctta.h, ctta_philox_normal):
+        (num_draws, B, C, H, W) fp32 on the module's device, row b of draw j being draw `draw0 + j` of the stream
+        (seeds[b], samples[b]) -- draw 0 is a sampler's initial latent, draw k its k-th re-noising draw.  `seeds`: B ints
+        (a sequence, or an int64 tensor on the host or the device); `samples`: B sample indices, None for all zeros.  A
+        row's values depend on its seed, sample, draw and position in the latent ONLY: not on its row, not on B, not on
+        what was drawn before; a latent of H rows draws the first H rows of a taller one.  One launch.  This is the one
+        place the stream is produced: the seeded samplers call it, the seeded captures record its launch."""
+        s = _seed_tensor(seeds)
+        m = _sample_tensor(samples, s.numel())
+        num_draws, draw0 = int(num_draws), int(draw0)
+        latent = tuple(int(v) for v in latent)
+        if num_draws < 1 or draw0 < 0:
+            raise ValueError("num_draws %d / draw0 %d: expected at least one draw and a first draw >= 0" % (num_draws, draw0))
+        if len(latent) != 3 or min(latent) < 1 or latent[2] % 4:
+            raise ValueError("latent %r: expected (C, H, W) with W a multiple of 4" % (latent,))
+        dev = self.unet.device
+        if dev.type != "cuda":
+            raise N.CttaError("the module is on %s: the Philox stream has no CPU path" % dev)
+        out = torch.empty((num_draws, s.numel()) + latent, dtype=torch.float32, device=dev)
+        _philox_fill(s.to(dev), None if m is None else m.to(dev), draw0, out)
+        return out
+
     @torch.no_grad()
     def generate_latent(self, encoder_states, encoder_mask, noise, cfg_scale_input=3., cfg_scale_post=1.,
                         num_steps=1, uncond_states=None, uncond_mask=None, step_noise=None):
@@ -2247,13 +2328,15 @@ class ConsistencyTTA(nn.Module):
     @torch.no_grad()
     def edit(self, prompt, source_wav, time_mask_ratio_start_and_end=(1., 1.), freq_mask_ratio_start_and_end=(1., 1.),
              strength=1.0, cfg_scale_input=3., cfg_scale_post=1., num_steps=4, num_samples=1, sr=16000,
-             sample_posterior=False):
+             sample_posterior=False, seeds=None):
         """Prompts and source waveforms ((B, T) in [-1, 1] at 16 kHz, one per prompt) -> int16 waveforms (numpy), 9.5 s:
         the clip with the masked time span / frequency band regenerated (pipeline.py:247-300; a frequency band is the
         reference's super-resolution), or, with `strength` < 1, a text-guided variation of it (pipeline.py:145-245).  The
         default ratios (1.0, 1.0) mask nothing: at strength 1 everything is kept and the clip comes back through the VAE and
-        the vocoder; with `strength` < 1 there is then no mask at all, as in style_transfer, and the whole clip varies."""
+        the vocoder; with `strength` < 1 there is then no mask at all, as in style_transfer, and the whole clip varies.
+        `seeds`: as in `forward`; the r queries that run take the draws 0 .. r - 1."""
         self.check_eval_mode()
+        rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
         embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
         B = embeds.shape[0]
         source_wav = torch.as_tensor(source_wav)
@@ -2261,38 +2344,48 @@ class ConsistencyTTA(nn.Module):
             raise ValueError("source_wav %s: expected (%d, samples), one clip per prompt"
                              % (tuple(source_wav.shape), B // num_samples))
         source_wav = source_wav.repeat_interleave(num_samples, 0)
-        noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
+        kw = {}
+        if rows is None:
+            noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
+        else:
+            shape = torch.empty(B, 0, 256, 16)        # the strength / num_steps rules alone: r queries take r draws
+            r = _check_edit_inputs(shape, shape, None, strength, num_steps)
+            draws = self.seeded_noise(rows[0], r, (self.unet.config.in_channels, 256, 16), rows[1])
+            noise, kw["step_noise"] = draws[0], draws[1:]
         keep = self.latent_keep_mask(B, (256, 16), time_mask_ratio_start_and_end=time_mask_ratio_start_and_end,
                                      freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end)
         if float(strength) < 1. and bool((keep == 1).all()):
             keep = None       # style_transfer has no mask: a variation without a masked span changes the whole clip
-        kw = {}
         if cfg_scale_post > 1.:
-            kw = dict(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
         return self.edit_from_embeds(embeds, mask, noise, source_wav, keep, strength, cfg_scale_input, cfg_scale_post,
                                      num_steps, sr, sample_posterior=sample_posterior, **kw)
 
     @torch.no_grad()
     def capture_edit_graph(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
-                           num_steps=4, strength=1.0, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None):
+                           num_steps=4, strength=1.0, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None,
+                           seeded=False):
         """`capture_graph` for edits: the r = max(1, int(strength * num_steps)) queries of `edit_latent`, the VAE decoder,
         HiFi-GAN and the int16 conversion as ONE hipGraph.  Returns `replay(encoder_states, encoder_mask, noise,
         src_latent, keep_mask) -> pcm`; `noise` is (r, B, C, H, W) (or (B, C, H, W) when r == 1), the source latent and the
         mask ((B, 1, H, W) or (1, 1, H, W), None keeps nothing) are static inputs owned by the capture: every argument is
         copied in.  The waveform -> latent half (`_source_latent`) runs eagerly before a replay.  Results are identical to
-        `edit_latent(..., step_noise=noise[1:])` followed by the eager decoder and vocoder."""
+        `edit_latent(..., step_noise=noise[1:])` followed by the eager decoder and vocoder.  `seeded=True`: as in
+        `capture_graph` -- `replay(encoder_states, encoder_mask, seeds, src_latent, keep_mask, samples=None)`, the graph
+        begins with the fill of the r draws 0 .. r - 1."""
         self.check_eval_mode()
         dev = self.unet.device
         src0 = torch.zeros((batch,) + tuple(latent), device=dev)
         r = _check_edit_inputs(src0, src0, None, strength, num_steps)
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, r, cfg_scale_post, uncond_states,
-                                        uncond_mask, False)
+                                        uncond_mask, False, seeded)
         st["src"] = src0
         st["keep"] = torch.zeros(batch, 1, latent[1], latent[2], device=dev)
         # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
         st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
 
         def run():
+            self._fill_noise(st)
             lat = self._edit_latent_static(st["enc"], st["mask"], st["noise"], st["src"], st["keep"], cfg_scale_input,
                                            cfg_scale_post, num_steps, strength, st.get("unc"), st.get("unc_mask"))
             mel = self.vae.decode_first_stage(lat)
@@ -2305,9 +2398,9 @@ class ConsistencyTTA(nn.Module):
         _warm_up(run, dev)
         graph, out = _capture(run)
 
-        def replay(encoder_states, encoder_mask, noise, src_latent, keep_mask=None):
+        def replay(encoder_states, encoder_mask, noise, src_latent, keep_mask=None, **kw):
             _check_edit_inputs(st["noise"], src_latent, keep_mask, strength, num_steps)
-            load(encoder_states, encoder_mask, noise)
+            load(encoder_states, encoder_mask, noise, **kw)
             st["src"].copy_(src_latent)
             if keep_mask is None:
                 st["keep"].zero_()
@@ -2477,23 +2570,30 @@ class ConsistencyTTA(nn.Module):
 
     @torch.no_grad()
     def generate_long(self, prompt, duration, cfg_scale_input=3., cfg_scale_post=1., num_steps=4, num_samples=1, sr=16000,
-                      overlap=64):
-        """`forward` with a duration: prompts -> int16 waveforms (numpy) of int(sr * duration) samples, 2.5 .. 40 s."""
+                      overlap=64, seeds=None):
+        """`forward` with a duration: prompts -> int16 waveforms (numpy) of int(sr * duration) samples, 2.5 .. 40 s.
+        `seeds`: as in `forward`, on the long latent -- rows are the outer index of the stream, so clips of two durations
+        under one seed start from the same noise on the rows they share."""
         self.check_eval_mode()
         Ht = _long_latent_h(duration)
+        rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
         embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
         B = embeds.shape[0]
-        noise = randn_tensor((B, self.unet.config.in_channels, Ht, 16), device=embeds.device, dtype=torch.float32)
         kw = {}
+        if rows is None:
+            noise = randn_tensor((B, self.unet.config.in_channels, Ht, 16), device=embeds.device, dtype=torch.float32)
+        else:
+            draws = self.seeded_noise(rows[0], num_steps, (self.unet.config.in_channels, Ht, 16), rows[1])
+            noise, kw["step_noise"] = draws[0], draws[1:]
         if cfg_scale_post > 1.:
-            kw = dict(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
         return self.generate_long_from_embeds(embeds, mask, noise, duration, cfg_scale_input, cfg_scale_post, num_steps, sr,
                                               overlap=overlap, **kw)
 
     @torch.no_grad()
     def capture_long_graph(self, batch, text_len, duration, cfg_scale_input=3., num_steps=4, cfg_scale_post=1., overlap=64,
                            window_h=256, cross_attention_dim=1024, latent_cw=(8, 16), sr=16000, uncond_states=None,
-                           uncond_mask=None, _chunk_rows=LONG_DECODE_ROWS):
+                           uncond_mask=None, _chunk_rows=LONG_DECODE_ROWS, seeded=False):
         """`capture_graph` for a clip of `duration` seconds: the windowed few-step sampler of `generate_long_latent`, the
         VAE decoder, HiFi-GAN and the int16 conversion as ONE hipGraph.  Returns `f(encoder_states, encoder_mask, noise) ->
         pcm` (int16 on the device, int(sr * duration) samples); `noise` is (num_steps, B, C, Ht, W), row 0 the initial
@@ -2502,19 +2602,22 @@ class ConsistencyTTA(nn.Module):
         step_noise=noise[1:])`.  As with every capture, the graph holds the addresses of the engine handles it was recorded
         on, and the VAE keeps ONE decoder and ONE vocoder handle, re-created for another extent: a clip of another length
         decoded on this module afterwards -- eagerly or by another capture -- frees what this graph replays.  Captures of
-        different durations need a module each (tools/serve_bench.py --long builds two)."""
+        different durations need a module each (tools/serve_bench.py --long builds two).  `seeded=True`: as in
+        `capture_graph`, `f(encoder_states, encoder_mask, seeds, samples=None)`; the fill draws the long (C, Ht, W) latent,
+        whose first rows are the draw of every shorter clip under the same seed."""
         self.check_eval_mode()
         dev = self.unet.device
         Ht = _long_latent_h(duration)
         self.long_plan(Ht, window_h, overlap)
         C, W = latent_cw
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, (C, Ht, W), num_steps, cfg_scale_post,
-                                        uncond_states, uncond_mask, False)
+                                        uncond_states, uncond_mask, False, seeded)
         # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
         st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
         samples = int(sr * float(duration))
 
         def run():
+            self._fill_noise(st)
             lat = self._long_loop(st["enc"], st["mask"], lambda k: st["noise"][k], (batch, C, Ht, W), cfg_scale_input,
                                   cfg_scale_post, num_steps, overlap, window_h, st.get("unc"), st.get("unc_mask"))
             mel, pcm = self._decode_long(lat, st["scratch"], _chunk_rows)
@@ -2523,8 +2626,8 @@ class ConsistencyTTA(nn.Module):
         _warm_up(run, dev)
         graph, out = _capture(run)
 
-        def replay(*args):
-            load(*args)
+        def replay(*args, **kw):
+            load(*args, **kw)
             graph.replay()
             self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
             return out[2][:, :samples]
@@ -2534,10 +2637,13 @@ class ConsistencyTTA(nn.Module):
         return replay
 
     def _serving_inputs(self, batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post, uncond_states,
-                        uncond_mask, from_tokens):
+                        uncond_mask, from_tokens, seeded=False):
         """Static inputs of a captured serving path and the function that refills them from a replay's arguments.
         States-in: `(encoder_states, encoder_mask, noise)`; tokens-in: `(input_ids, attention_mask, noise)`.  `noise` is
         (num_steps, B, C, H, W) -- row 0 the initial draw, rows 1.. the step noise --, or (B, C, H, W) when num_steps == 1.
+        `seeded`: static (B) int64 seeds and (B) int32 sample indices stand beside the noise buffer, the function takes
+        `seeds` (B ints, or an int64 tensor on the host or the device) where it took `noise`, and an optional `samples=`
+        (None: all zeros); the recorded work fills the noise buffer from them (`_fill_noise`).
         With post-CFG the uncond states are static inputs fixed HERE: (B, L, D) or (1, L, D) (broadcast); tokens-in
         captures compute them once, from the prompt "" padded to the bucket's length, when none are given."""
         from .text_encoder import check_tokens
@@ -2547,6 +2653,9 @@ class ConsistencyTTA(nn.Module):
             raise ValueError("num_steps must be at least 1, got %d" % num_steps)
         nshape = (num_steps, batch) + tuple(latent)
         st = {"noise": torch.zeros(nshape, device=dev)}
+        if seeded:
+            st["seeds"] = torch.zeros(batch, dtype=torch.int64, device=dev)
+            st["samples"] = torch.zeros(batch, dtype=torch.int32, device=dev)
         if from_tokens:
             if self.text_encoder is None:          # the tokens are the caller's: no tokenizer is needed here
                 self._require_text_encoder()
@@ -2585,23 +2694,41 @@ class ConsistencyTTA(nn.Module):
                 raise ValueError("noise %s: expected %s (row 0 the initial draw, rows 1.. the step noise)"
                                  % (tuple(noise.shape), nshape))
 
-        def load_states(encoder_states, encoder_mask, noise):
-            load_noise(noise)
+        def load_seeds(seeds, samples=None):
+            seeds, samples = _seed_tensor(seeds, batch), _sample_tensor(samples, batch)     # ValueError before any copy
+            st["seeds"].copy_(seeds)
+            if samples is None:
+                st["samples"].zero_()
+            else:
+                st["samples"].copy_(samples)
+
+        if seeded:
+            load_noise = load_seeds
+
+        def load_states(encoder_states, encoder_mask, noise, **kw):
+            load_noise(noise, **kw)
             st["enc"].copy_(encoder_states)
             st["mask"].copy_(encoder_mask)
 
-        def load_tokens(input_ids, attention_mask, noise):
+        def load_tokens(input_ids, attention_mask, noise, **kw):
             if not input_ids.is_cuda and not attention_mask.is_cuda:
                 check_tokens(input_ids, attention_mask, self.text_encoder.config["vocab_size"], batch, text_len)
             elif tuple(input_ids.shape) != (batch, text_len) or tuple(attention_mask.shape) != (batch, text_len):
                 raise ValueError("tokens %s / %s are not the captured bucket (%d, %d)"
                                  % (tuple(input_ids.shape), tuple(attention_mask.shape), batch, text_len))
             # tokens already on the device are uploaded unchecked: t5_embed_kernel clamps ids into the vocabulary
-            load_noise(noise)
+            load_noise(noise, **kw)
             st["ids"].copy_(input_ids)
             st["attn"].copy_(attention_mask)
 
         return st, (load_tokens if from_tokens else load_states)
+
+    @staticmethod
+    def _fill_noise(st):
+        """Head of a seeded capture's recorded work: ONE ctta_philox_normal launch fills the static noise buffer with the
+        draws 0 .. of the streams the static seeds / sample indices name when the graph RUNS.  Not seeded: nothing."""
+        if "seeds" in st:
+            _philox_fill(st["seeds"], st["samples"], 0, st["noise"])
 
     def _encode_static(self, st):
         """`encode_text` on the static token buffers, launches only: (states, bool mask)."""
@@ -2609,7 +2736,8 @@ class ConsistencyTTA(nn.Module):
 
     @torch.no_grad()
     def capture_graph(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
-                      num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None, from_tokens=False):
+                      num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None, from_tokens=False,
+                      seeded=False):
         """Captures the whole pipeline (U-Net queries -> VAE decoder -> HiFi-GAN -> int16) for a fixed
         (batch, text_len) into ONE hipGraph and returns a callable `(encoder_states, encoder_mask, noise) -> pcm` that
         copies its arguments into the graph's static inputs and replays it.  The ~1500 kernel launches of a clip cost
@@ -2621,14 +2749,20 @@ class ConsistencyTTA(nn.Module):
         static inputs fixed at capture.  `from_tokens=True`: the callable takes `(input_ids, attention_mask, noise)` --
         int64 (B, L) ids and a (B, L) mask, on the host or on the device -- and FLAN-T5 runs inside the graph; host tokens
         pass `text_encoder.check_tokens` before the upload, device tokens are taken as they are (t5_embed_kernel clamps
-        ids into the vocabulary); with post-CFG the uncond states are those of the prompt "" at length `text_len`."""
+        ids into the vocabulary); with post-CFG the uncond states are those of the prompt "" at length `text_len`.
+        `seeded=True`: the callable takes `seeds` where it took `noise` -- B ints, or an int64 tensor on the host or the
+        device -- and an optional `samples=` (B sample indices, None for zeros); the graph begins with ONE
+        ctta_philox_normal launch that fills the static noise buffer from the static seeds, read when the graph runs, and
+        everything after it is the graph recorded without `seeded`.  Bit-identical to the plain capture fed
+        `seeded_noise(seeds, num_steps, latent, samples)`."""
         self.check_eval_mode()
         dev = self.unet.device
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
-                                        uncond_states, uncond_mask, from_tokens)
+                                        uncond_states, uncond_mask, from_tokens, seeded)
         scratch = torch.empty(4, dtype=torch.float32, device=dev)
 
         def run():
+            self._fill_noise(st)
             enc, mask = self._encode_static(st) if from_tokens else (st["enc"], st["mask"])
             lat = self._generate_latent_static(enc, mask, st["noise"], cfg_scale_input, cfg_scale_post, num_steps,
                                                st.get("unc"), st.get("unc_mask"))
@@ -2641,8 +2775,8 @@ class ConsistencyTTA(nn.Module):
         _warm_up(run, dev)
         graph, out = _capture(run)
 
-        def replay(*args):
-            load(*args)
+        def replay(*args, **kw):
+            load(*args, **kw)
             graph.replay()
             self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
             return out[2]
@@ -2653,7 +2787,7 @@ class ConsistencyTTA(nn.Module):
 
     def capture_pipeline(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
                          candidates=8, num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None,
-                         from_tokens=False):
+                         from_tokens=False, seeded=False):
         """The same pipeline as a 3-deep SOFTWARE PIPELINE over batches for a throughput-bound server: three
         hipGraphs -- U-Net queries, VAE decoder, HiFi-GAN + int16 -- replayed per call on three streams for three DIFFERENT
         batches (the batch of this call, of the previous call, of the call before).  The stages of one batch stay strictly
@@ -2666,23 +2800,31 @@ class ConsistencyTTA(nn.Module):
         `num_steps`, `cfg_scale_post`, `uncond_states`, `uncond_mask`, `from_tokens`: as in `capture_graph`.  With
         `from_tokens=True` FLAN-T5 is a FOURTH graph on a fourth stream, placed by the same measurement, one batch ahead of
         the U-Net: `f(input_ids, attention_mask, noise)` returns the batch fed THREE calls earlier (`f.depth == 3`); a
-        batch's noise is held back one call so that it meets its own text states."""
+        batch's noise is held back one call so that it meets its own text states.  `seeded=True`: as in `capture_graph`;
+        the fill launch is the head of the U-Net stage's graph, and with `from_tokens=True` a batch's seeds and sample
+        indices are held back one call as its noise is."""
         self.check_eval_mode()
         dev = self.unet.device
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
-                                        uncond_states, uncond_mask, from_tokens)
+                                        uncond_states, uncond_mask, from_tokens, seeded)
         scratch = torch.empty(4, dtype=torch.float32, device=dev)
+        held = ("seeds", "samples") if seeded else ("noise",)      # what waits one call beside the text states
 
         def graphed(fn):      # every stage on the stream that warmed it up
             return _capture(fn, stream=_warm_up(fn, dev, sync=True))
 
         if from_tokens:
             g_t, (enc, mask) = graphed(lambda: self._encode_static(st))
-            u_in = {"enc": enc.clone(), "mask": mask.clone(), "noise": st["noise"].clone()}
+            u_in = {"enc": enc.clone(), "mask": mask.clone(), "noise": st["noise"]}
+            u_in.update((k, st[k].clone()) for k in held)
         else:
             g_t, u_in = None, st
-        g_u, lat = graphed(lambda: self._generate_latent_static(u_in["enc"], u_in["mask"], u_in["noise"], cfg_scale_input,
-                                                                cfg_scale_post, num_steps, st.get("unc"), st.get("unc_mask")))
+
+        def unet_stage():
+            self._fill_noise(u_in)
+            return self._generate_latent_static(u_in["enc"], u_in["mask"], u_in["noise"], cfg_scale_input, cfg_scale_post,
+                                                num_steps, st.get("unc"), st.get("unc_mask"))
+        g_u, lat = graphed(unet_stage)
         lat_in = lat.clone()
         g_v, mel = graphed(lambda: self.vae.decode_first_stage(lat_in))
         mel_in = mel.clone()
@@ -2702,7 +2844,8 @@ class ConsistencyTTA(nn.Module):
             if from_tokens:                            # ... and the text states + noise of the batch fed last call to the U-Net
                 u_in["enc"].copy_(enc)
                 u_in["mask"].copy_(mask)
-                u_in["noise"].copy_(st["noise"])
+                for k in held:
+                    u_in[k].copy_(st[k])
 
         def launch():
             cur = torch.cuda.current_stream(dev)
@@ -2723,9 +2866,9 @@ class ConsistencyTTA(nn.Module):
             cands = [streams[k]] + [torch.cuda.Stream(device=dev) for _ in range(max(0, candidates - 1))]
             streams[k], placement[k] = _place_stream(cands, run_on, dev)
 
-        def replay(*args):
+        def replay(*args, **kw):
             hand_over()                                # reads the previous call's inputs and results, before ...
-            load(*args)                                # ... this call's arguments overwrite the static inputs
+            load(*args, **kw)                          # ... this call's arguments overwrite the static inputs
             launch()
             self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
             return pcm
@@ -2745,15 +2888,22 @@ class ConsistencyTTA(nn.Module):
     encode_text_classifier_free = AudioDistilledModel.encode_text_classifier_free
 
     @torch.no_grad()
-    def forward(self, prompt, cfg_scale_input=3., cfg_scale_post=1., num_steps=1, num_samples=1, sr=16000):
-        """easy_inference/consistencytta.py:135-200: prompts -> int16 waveforms (numpy), truncated to 9.5 s."""
+    def forward(self, prompt, cfg_scale_input=3., cfg_scale_post=1., num_steps=1, num_samples=1, sr=16000, seeds=None):
+        """easy_inference/consistencytta.py:135-200: prompts -> int16 waveforms (numpy), truncated to 9.5 s.  `seeds`: one
+        int per prompt; row i * num_samples + m then draws from the stream (seeds[i], sample m) of `seeded_noise` -- draw 0
+        the initial latent, draw k the k-th re-noising draw -- and not from torch's generator (None: as the reference)."""
         self.check_eval_mode()
+        rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
         embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
         B = embeds.shape[0]
-        noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
         kw = {}
+        if rows is None:
+            noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
+        else:
+            draws = self.seeded_noise(rows[0], num_steps, (self.unet.config.in_channels, 256, 16), rows[1])
+            noise, kw["step_noise"] = draws[0], draws[1:]
         if cfg_scale_post > 1.:
-            kw = dict(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
         return self.forward_from_embeds(embeds, mask, noise, cfg_scale_input, cfg_scale_post, num_steps, sr, **kw)
 
     @torch.no_grad()

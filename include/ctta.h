@@ -396,6 +396,24 @@ ctta_status ctta_window_fuse_renoise(const float* cond, const float* uncond, con
                                      const float* weights, const float* noise, const float* sigma, float* x0_long,
                                      float* out, int copies, int batch, int n_windows, int channels, int window_h,
                                      int latent_h, int width, void* stream);
+/* Seeded sampler noise: what torch.randn at easy_inference/consistencytta.py's noise draw becomes when a request carries
+ * a seed.  Philox4x32-10 as published (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), one
+ * block per four consecutive w of a (C, H, W) latent:
+ *   q       = (h * C + c) * W + w                      (rows are the OUTER index: H rows are the first H of a taller draw)
+ *   key     = (seed & 0xffffffff, seed >> 32)          (seed: the request's int64 taken as uint64)
+ *   counter = (q >> 2, d, m, 0)                        (d: draw index, m: sample index, 0: domain tag "sampler noise")
+ * and the block's words x0..x3 serve q & 3 = 0..3.  With u(x) = ((x >> 9) + 0.5) * 2^-23 and r(x) = sqrtf(-2 logf(u(x))):
+ *   z0 = r(x0) * cos(2 pi u(x1)),  z1 = r(x0) * sin(2 pi u(x1)),  z2 = r(x2) * cos(2 pi u(x3)),  z3 = r(x2) * sin(2 pi u(x3))
+ * the angle through sincospif(2 u) (2 u is exact in fp32), no fast-math intrinsic; |z| <= sqrt(-2 ln 2^-24) = 5.768.
+ * seeds is (batch) int64 and samples (batch) int32 (NULL: all zeros), both on the DEVICE and read when the kernel runs: a
+ * captured launch picks up what the buffers hold at replay.  out is (draws, batch, C, H, W) and holds the draws
+ * d = draw0 .. draw0 + draws - 1 of every row, in ONE launch; ctta_philox_normal writes scale * z (f32, the product
+ * rounded on its own), ctta_philox_words the raw words.  Refused before any launch: width % 4 != 0, a non-positive extent,
+ * draw0 < 0, C * H * W >= 2^34 (q >> 2 is a 32-bit counter word), seeds or out NULL. */
+ctta_status ctta_philox_normal(const int64_t* seeds, const int32_t* samples, int batch, int draw0, int draws, int channels,
+                               int height, int width, float scale, float* out, void* stream);
+ctta_status ctta_philox_words(const int64_t* seeds, const int32_t* samples, int batch, int draw0, int draws, int channels,
+                              int height, int width, int32_t* out, void* stream);
 /* get_loss with MSELoss('instance') and SNR clamp (models/audio_consistency_model.py:250-266,
  * tools/losses.py:28-33): loss = mean_b( mean((pred-target)^2) * min(sigma^-2, gamma) ).
  * gamma <= 0 disables the weighting.  loss: 1 float on device. */

@@ -30,6 +30,12 @@ captured plain few-step path at the same number of U-Net rows (batch 32), and th
 it replaces (see `long_leg`):
 
   python tools/serve_bench.py --long --out profiles/long_serving.json
+
+`--seeded` runs the seeded leg alone: the seeded captures (seeds in, the Philox fill at the head of the graph) beside the
+plain captures fed a device `torch.randn` per call, at the plain mode's shape and at the long leg's, and the fill launch
+beside the draws and uploads it replaces (see `seeded_leg`):
+
+  python tools/serve_bench.py --seeded --out profiles/seeded_serving.txt
 """
 import argparse
 import json
@@ -380,8 +386,149 @@ def long_leg(args):
             f.write(json.dumps(result, indent=1) + "\n")
 
 
+def seeded_leg(args):
+    """`--seeded`: the seeded captures (capture_graph / capture_long_graph with seeded=True: B seeds in, one
+    ctta_philox_normal launch at the head of the graph) beside the plain captures fed a device `torch.randn` per call (the
+    caller's RNG, then the copy into the static noise buffer), states in, at `--edit-steps` queries, in alternating windows:
+    the plain mode's shape (`--batch` clips of the model's own length) and the long leg's (`--long-clips` clips of
+    `--duration` seconds).  Then the draw alone, stream time by events: the fill launch, `torch.randn` of the same shape,
+    and the upload of the same bytes from pageable and from pinned host memory.  No threshold: the leg records what the fill
+    costs against what it replaces."""
+    import torch
+    from consistencytta_amd import _native as N
+    from consistencytta_amd import modules, spec
+    from consistencytta_amd.models import ConsistencyTTA, _long_latent_h
+    dev = "cuda:0"
+    B, Bl, L, steps = args.batch, args.long_clips, args.text_len, args.edit_steps
+    if args.tiny:
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        import cases
+        ucfg, (C, wh, W), overlap = dict(cases.TINY_UNET), (8, 32, 16), 8
+        duration = args.duration if args.duration is not None else 3.0
+        make_vae = lambda: modules.AutoencoderKL(ddconfig=cases.TINY_VAE_DD, embed_dim=8, scale_factor=0.9,      # noqa: E731
+                                                 hifigan_config=cases.TINY_HIFIGAN)
+    else:
+        ucfg, (C, wh, W), overlap = spec.LIGHT_UNET_CONFIG, (8, 256, 16), 64
+        duration = args.duration if args.duration is not None else 30.72
+        make_vae = lambda: modules.AutoencoderKL(ddconfig=spec.VAE_DDCONFIG, embed_dim=8,                        # noqa: E731
+                                                 scale_factor=0.9227914214134216)
+    Ht = _long_latent_h(duration)
+    D = ucfg["cross_attention_dim"]
+
+    def build_pipe():
+        v = make_vae()
+        p = ConsistencyTTA(unet_config=ucfg, vae=v)
+        p.to(dev)
+        p.unet.init_random_(seed=0)
+        v.init_random_(seed=1)
+        return p.eval().requires_grad_(False)
+    pipe, pipe_long = build_pipe(), build_pipe()           # one module per decoder extent (see long_leg)
+    W_IN = 4.0
+    g = torch.Generator(device="cpu").manual_seed(3)
+    shapes = {"plain": (steps, B, C, wh, W), "long": (steps, Bl, C, Ht, W)}
+    batches = []
+    for _ in range(2):
+        lens = torch.randint(min(6, L), L + 1, (B,), generator=g)
+        enc, mask = (torch.randn(B, L, D, generator=g) * 0.25).to(dev), (torch.arange(L)[None, :] < lens[:, None]).to(dev)
+        batches.append({"plain": (enc, mask, torch.randint(-2 ** 62, 2 ** 62, (B,), generator=g)),
+                        "long": (enc[:Bl].contiguous(), mask[:Bl].contiguous(), torch.randint(-2 ** 62, 2 ** 62, (Bl,), generator=g))})
+    kw = {"plain": dict(cfg_scale_input=W_IN, cross_attention_dim=D, latent=(C, wh, W), num_steps=steps),
+          "long": dict(cfg_scale_input=W_IN, num_steps=steps, overlap=overlap, window_h=wh, cross_attention_dim=D,
+                       latent_cw=(C, W))}
+    gens = {("plain", False): pipe.capture_graph(B, L, **kw["plain"]),
+            ("plain", True): pipe.capture_graph(B, L, seeded=True, **kw["plain"]),
+            ("long", False): pipe_long.capture_long_graph(Bl, L, duration, **kw["long"]),
+            ("long", True): pipe_long.capture_long_graph(Bl, L, duration, seeded=True, **kw["long"])}
+    noise_of = {"plain": lambda s: pipe.seeded_noise(s, steps, (C, wh, W)),
+                "long": lambda s: pipe_long.seeded_noise(s, steps, (C, Ht, W))}
+    parity = {}
+    for leg in ("plain", "long"):                          # the seeded capture is the plain one fed seeded_noise, bit for bit
+        enc, mask, seeds = batches[0][leg]
+        want = gens[(leg, False)](enc, mask, noise_of[leg](seeds)).clone()
+        parity[leg + "_seeded_graph"] = bool(torch.equal(gens[(leg, True)](enc, mask, seeds), want))
+    if not all(parity.values()):
+        raise SystemExit("a seeded capture differs from the plain capture fed seeded_noise: %s" % parity)
+
+    turn = [0]
+
+    def nxt(leg):
+        turn[0] ^= 1
+        return batches[turn[0]][leg]
+
+    def randn_call(leg):
+        enc, mask, _ = nxt(leg)
+        return gens[(leg, False)](enc, mask, torch.randn(shapes[leg], device=dev))
+
+    def seeded_call(leg):
+        return gens[(leg, True)](*nxt(leg))                # host seeds: the upload is B int64
+    forms = {"plain_graph_device_randn": lambda: randn_call("plain"), "plain_graph_seeded": lambda: seeded_call("plain"),
+             "long_graph_device_randn": lambda: randn_call("long"), "long_graph_seeded": lambda: seeded_call("long")}
+    for fn in forms.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    windows = {k: [] for k in forms}
+    for _ in range(args.rounds):
+        for k, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            windows[k].append((time.perf_counter() - t0) / args.steps * 1e3)
+    med = {k: statistics.median(v) for k, v in windows.items()}
+
+    # ---- the draw alone: stream time by events over back-to-back calls (launch cost included)
+    draw_forms = {}
+    for leg, p in (("plain", pipe), ("long", pipe_long)):
+        shape = shapes[leg]
+        seeds = batches[0][leg][2].to(dev)
+        out = torch.empty(shape, device=dev)
+        pageable, pinned = torch.randn(shape, generator=g), torch.randn(shape, generator=g).pin_memory()
+        draw_forms[leg + "_philox_fill"] = (lambda p=p, seeds=seeds, shape=shape: p.seeded_noise(seeds, shape[0], shape[2:]))
+        draw_forms[leg + "_torch_randn"] = (lambda shape=shape: torch.randn(shape, device=dev))
+        draw_forms[leg + "_upload_pageable"] = (lambda out=out, src=pageable: out.copy_(src))
+        draw_forms[leg + "_upload_pinned"] = (lambda out=out, src=pinned: out.copy_(src, non_blocking=True))
+    draw_us = {k: [] for k in draw_forms}
+    reps = 50
+    for _ in range(args.rounds + 1):           # the first round warms up and is dropped
+        for k, fn in draw_forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            draw_us[k].append(e0.elapsed_time(e1) / reps * 1e3)
+    draw_med = {k: statistics.median(v[1:]) for k, v in draw_us.items()}
+    result = {
+        "tool": "tools/serve_bench.py --seeded", "device": torch.cuda.get_device_name(0), "tiny": bool(args.tiny),
+        "plain": {"clips": B, "noise_shape": list(shapes["plain"]), "noise_bytes": 4 * int(torch.Size(shapes["plain"]).numel())},
+        "long": {"clips": Bl, "duration_s": duration, "latent_h": Ht, "noise_shape": list(shapes["long"]),
+                 "noise_bytes": 4 * int(torch.Size(shapes["long"]).numel())},
+        "text_len": L, "num_steps": steps, "steps_per_window": args.steps, "rounds": args.rounds, "warmup_calls": args.warmup,
+        "unit": "ms per call of one batch; draws: us per call, stream time by events over %d back-to-back calls (launch "
+                "cost included)" % reps,
+        "timing": "host clock around a window of calls ending in a device synchronise; forms alternate within a round",
+        "parity_seeded_graph_bit_identical_to_plain_graph_on_seeded_noise": parity,
+        "ms_per_call_median": {k: round(v, 3) for k, v in med.items()},
+        "ms_per_call_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()},
+        "ratios_of_medians": {leg + "_seeded_over_device_randn":
+                              round(med[leg + "_graph_seeded"] / med[leg + "_graph_device_randn"], 4) for leg in ("plain", "long")},
+        "draw_us_median": {k: round(v, 2) for k, v in draw_med.items()},
+        "draw_us_windows": {k: [round(x, 2) for x in v[1:]] for k, v in draw_us.items()},
+    }
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--seeded", action="store_true", help="only the seeded leg: the seeded captures beside the plain captures "
+                    "fed a device torch.randn per call, and the fill launch beside the draws and uploads it replaces")
     ap.add_argument("--long", action="store_true", help="only the long-clip leg: the captured long path beside the captured "
                     "plain few-step path at the same number of U-Net rows, and the one-pass step kernel beside its chain")
     ap.add_argument("--duration", type=float, default=None, help="seconds per clip of the long leg (default 30.72; --tiny: 3.0)")
@@ -408,6 +555,8 @@ def main():
         return edit_leg(args)
     if args.long:
         return long_leg(args)
+    if args.seeded:
+        return seeded_leg(args)
     dev = "cuda:0"
     B, L = args.batch, args.text_len
 
