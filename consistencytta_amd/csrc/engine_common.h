@@ -273,7 +273,9 @@ struct WeightStore {
 
   // The fp32 copies whose key names an adapter tensor ("_lora."), from a table of their own: what moves when only the
   // adapters changed.  Nothing else of the store is touched; a key the table lacks fails with that key named.
-  ctta_status run_adapters(const WeightTable& wt, hipStream_t s) {
+  // `rebase` (an adapter bank's slot): a destination inside [from, from + floats) moves to the same offset behind `to`.
+  struct Rebase { const float* from; size_t floats; float* to; };
+  ctta_status run_adapters(const WeightTable& wt, hipStream_t s, const std::vector<Rebase>* rebase = nullptr) {
     h_acopy.clear();
     for (const CopySpec& c : copies) {
       if (c.key.find("_lora.") == std::string::npos) continue;
@@ -289,6 +291,13 @@ struct WeightStore {
         memset(&g, 0, sizeof(g));
         g.src = t->data + c.src_start + off; g.dst = c.dst + off;
         g.count = c.count - off < CTTA_COPY_ELEMS_PER_BLOCK ? c.count - off : CTTA_COPY_ELEMS_PER_BLOCK;
+        if (rebase) {
+          float* moved = nullptr;
+          for (const Rebase& b : *rebase)
+            if (g.dst >= b.from && g.dst + g.count <= b.from + b.floats) { moved = b.to + (g.dst - b.from); break; }
+          if (!moved) { ctta_set_error("internal: adapter tensor '%s' lies outside every site", c.key.c_str()); return CTTA_ERR_INVALID; }
+          g.dst = moved;
+        }
         h_acopy.push_back(g);
       }
     }

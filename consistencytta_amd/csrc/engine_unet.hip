@@ -83,6 +83,8 @@ struct LoraSite {
   int32_t *kmap = nullptr, *nmap = nullptr;
   int k = 0, n = 0, k_pad = 0, n_pad = 0;
   float* d = nullptr;   // down(x) [rows][r] of the training forward, kept for the backward pass
+  // per-request adapters (ctta_unet_adapter_bank): `slots` copies of a / b in the same packed layout, zeros where never loaded
+  float *bank_a = nullptr, *bank_b = nullptr;
 };
 
 struct Transformer {
@@ -147,6 +149,12 @@ struct ctta_unet : EngineBase {
   // measured slower than the launches it replaces (profiles/lora_step.txt).
   int lora_fused = 1;
   float lora_scale = 1.0f;
+  // Per-request adapters: one allocation behind every site's bank_a / bank_b, and the caller's device arrays of
+  // ctta_unet_set_adapter_rows (read by the kernels, never by the host).  row_slot == nullptr: no launch differs.
+  float* bank_base = nullptr;
+  int bank_slots = 0;
+  const int32_t* row_slot = nullptr;
+  const float* row_scale = nullptr;
   // Text cache: the cross-attention K / V^T projections of the text states (32 small GEMMs per forward) live in
   // persistent buffers; a caller that queries the same handle again with the SAME text states and mask (the second CFG
   // teacher query of a distillation step, every query of the Heun teacher loop) says so with ctta_unet_reuse_text and
@@ -188,6 +196,8 @@ struct UCtx : GradCtx {
   bool train = false;
   bool lora_fused = false;   // the forward groups (bit 1 of the handle's setting)
   float lora_scale = 1.0f;
+  const int32_t* row_slot = nullptr;   // per-request adapters: the rows kernels read the sites' banks through these
+  const float* row_scale = nullptr;
 };
 
 static ctta_status make_resnet(ctta_unet* U, const std::string& p, int cin, int cout, Resnet* R) {
@@ -398,6 +408,18 @@ struct LoraDst { LoraSite* S; bf16_t* y; int ldy; int vt_tokens; };
 static ctta_status lora_forward_one(UCtx& c, const LoraDst& D, const bf16_t* x, int ldx, int64_t rows, float* d) {
   const int r = c.U->lora_r;
   LoraSite& S = *D.S;
+  if (c.row_slot) {   // a different adapter per sample: the sample's slot of the site's bank, its scale (or the handle's)
+    const int slots = c.U->bank_slots;
+    const int64_t sa = (int64_t)r * S.k_pad, sb = (int64_t)S.n_pad * r;
+    RUN(c, ctta_lora_down_rows(x, ldx, rows, S.k_pad, S.bank_a, sa, slots, r, rows / c.B, c.row_slot, d, c.stream));
+    if (D.vt_tokens > 0)
+      RUN(c, ctta_lora_up_add_t_rows(D.y, D.ldy, (int64_t)S.n_pad * D.ldy, c.B, D.vt_tokens, S.n_pad, d, D.vt_tokens, S.bank_b, sb,
+                                     slots, r, c.row_slot, c.row_scale, c.lora_scale, c.stream));
+    else
+      RUN(c, ctta_lora_up_add_rows(D.y, D.ldy, rows, S.n_pad, d, S.bank_b, sb, slots, r, rows / c.B, c.row_slot, c.row_scale,
+                                   c.lora_scale, c.stream));
+    return CTTA_OK;
+  }
   RUN(c, ctta_lora_down(x, ldx, rows, S.k_pad, S.a, 0, r, d, c.stream));
   if (D.vt_tokens > 0)
     RUN(c, ctta_lora_up_add_t(D.y, D.ldy, (int64_t)S.n_pad * D.ldy, c.B, D.vt_tokens, S.n_pad, d, D.vt_tokens, S.b, r, c.lora_scale,
@@ -579,6 +601,9 @@ static ctta_status unet_forward_impl(ctta_unet* U, bool dry, const float* sample
   U->bind(c, stream, dry, cfg.debug_taps != 0, cfg.norm_num_groups);
   c.U = U; c.B = B; c.L = L; c.Lp = round_up(L, 8);
   c.lora_fused = (U->lora_fused & 2) != 0; c.lora_scale = U->lora_scale;
+  if (U->row_slot && !train) {   // per-request adapters: the per-site rows launches, whatever bit 1 says
+    c.row_slot = U->row_slot; c.row_scale = U->row_scale; c.lora_fused = false;
+  }
   c.reuse_text = !dry && !train && U->tc_reuse_next && U->tc_valid && U->tc_base && U->tc_B == B && U->tc_L == L;
   U->tc_reuse_next = false;
   // a forward that re-projects the text states overwrites the cache as it goes: the cache is valid again only when this
@@ -1023,6 +1048,7 @@ extern "C" void ctta_unet_destroy(ctta_unet* U) {
   if (!U) return;
   U->destroy_base();
   if (U->tc_base) (void)hipFree(U->tc_base);
+  if (U->bank_base) (void)hipFree(U->bank_base);
   if (U->wg.stream) { (void)hipStreamSynchronize(U->wg.stream); (void)hipStreamDestroy(U->wg.stream); }
   for (int i = 0; i < WgradSide::NS; ++i) {
     if (U->wg.ready[i]) (void)hipEventDestroy(U->wg.ready[i]);
@@ -1066,6 +1092,92 @@ extern "C" ctta_status ctta_unet_set_lora(ctta_unet* U, int fused, float scale) 
   if (scale != U->lora_scale) U->tc_valid = false;   // the cached K / V^T hold scale * the adapter term
   U->lora_fused = fused;
   U->lora_scale = scale;
+  return CTTA_OK;
+}
+
+// ---- per-request adapters.  The bank is ONE allocation carved into per-site A [slots][r][k_pad] / B [slots][n_pad][r]; a slot
+// is loaded with the copy segments make_lora_site registered for the handle's own a / b, rebased into the slot.
+static void lora_sites_of(ctta_unet* U, std::vector<LoraSite*>* out) {
+  auto of = [&](Transformer& T) {
+    for (LoraSite* S : {&T.lq1, &T.lk1, &T.lv1, &T.lo1, &T.lq2, &T.lk2, &T.lv2, &T.lo2}) out->push_back(S);
+  };
+  for (Level& Lv : U->down) for (Transformer& T : Lv.att) of(T);
+  of(U->mid_att);
+  for (Level& Lv : U->up) for (Transformer& T : Lv.att) of(T);
+}
+
+extern "C" ctta_status ctta_unet_adapter_bank(ctta_unet* U, int slots, void* stream) {
+  CTTA_REQUIRE(U, "unet_adapter_bank: null handle");
+  CTTA_REQUIRE(U->lora_r > 0, "unet_adapter_bank: the handle has no adapters (its weight table named none at creation)");
+  CTTA_REQUIRE(slots >= 1 && slots <= 64, "unet_adapter_bank: %d slots outside [1,64]", slots);
+  if (U->bank_base) {
+    CTTA_REQUIRE(slots == U->bank_slots, "unet_adapter_bank: the handle already has a bank of %d slots (asked for %d); a bank is allocated once per handle",
+                 U->bank_slots, slots);
+    return CTTA_OK;
+  }
+  std::vector<LoraSite*> sites;
+  lora_sites_of(U, &sites);
+  const int r = U->lora_r;
+  auto padded = [](size_t floats) { return (floats + 63) & ~(size_t)63; };   // 256-byte steps: every site's bank is 16-byte aligned
+  size_t total = 0;
+  for (LoraSite* S : sites) total += padded((size_t)slots * r * S->k_pad) + padded((size_t)slots * S->n_pad * r);
+  float* base = nullptr;
+  if (hipMalloc((void**)&base, total * sizeof(float)) != hipSuccess) {
+    ctta_set_error("unet_adapter_bank: hipMalloc of %zu bytes failed", total * sizeof(float));
+    return CTTA_ERR_NOMEM;
+  }
+  if (hipMemsetAsync(base, 0, total * sizeof(float), (hipStream_t)stream) != hipSuccess) {
+    (void)hipFree(base);
+    ctta_set_error("unet_adapter_bank: hipMemset of the bank failed");
+    return CTTA_ERR_HIP;
+  }
+  float* q = base;
+  for (LoraSite* S : sites) {
+    S->bank_a = q; q += padded((size_t)slots * r * S->k_pad);
+    S->bank_b = q; q += padded((size_t)slots * S->n_pad * r);
+  }
+  U->bank_base = base;
+  U->bank_slots = slots;
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_unet_load_adapter_slot(ctta_unet* U, int slot, const ctta_tensor* weights, int n_weights, void* stream) {
+  CTTA_REQUIRE(U && weights, "unet_load_adapter_slot: null pointer");
+  CTTA_REQUIRE(U->lora_r > 0, "unet_load_adapter_slot: the handle has no adapters (its weight table named none at creation)");
+  CTTA_REQUIRE(U->bank_base, "unet_load_adapter_slot: the handle has no adapter bank (ctta_unet_adapter_bank)");
+  CTTA_REQUIRE(slot >= 0 && slot < U->bank_slots, "unet_load_adapter_slot: slot %d outside [0,%d)", slot, U->bank_slots);
+  WeightTable wt;
+  wt.map.clear();
+  for (int i = 0; i < n_weights; ++i) {
+    const char* nm = weights[i].name;
+    if (!nm || !strstr(nm, "_lora.")) continue;
+    const size_t len = strlen(nm);
+    int r = U->lora_r;
+    if (weights[i].ndim == 2 && len > 11 && !strcmp(nm + len - 11, "down.weight")) r = (int)weights[i].shape[0];
+    else if (weights[i].ndim == 2 && len > 9 && !strcmp(nm + len - 9, "up.weight")) r = (int)weights[i].shape[1];
+    CTTA_REQUIRE(r == U->lora_r, "unet_load_adapter_slot: '%s' has rank %d, the handle's adapters have rank %d", nm, r, U->lora_r);
+    wt.map[nm] = &weights[i];
+  }
+  // the handle's own packed a / b -> the same place of this slot of the site's bank
+  std::vector<LoraSite*> sites;
+  lora_sites_of(U, &sites);
+  const size_t r = (size_t)U->lora_r;
+  std::vector<WeightStore::Rebase> rb;
+  for (LoraSite* S : sites) {
+    rb.push_back({S->a, r * S->k_pad, S->bank_a + (size_t)slot * r * S->k_pad});
+    rb.push_back({S->b, (size_t)S->n_pad * r, S->bank_b + (size_t)slot * S->n_pad * r});
+  }
+  U->tc_valid = false;   // the cached K / V^T hold the rows' adapter terms
+  return U->store.run_adapters(wt, (hipStream_t)stream, &rb);
+}
+
+extern "C" ctta_status ctta_unet_set_adapter_rows(ctta_unet* U, const int32_t* slot_of_sample, const float* scale_of_sample) {
+  CTTA_REQUIRE(U, "unet_set_adapter_rows: null handle");
+  CTTA_REQUIRE(!slot_of_sample || U->bank_base, "unet_set_adapter_rows: the handle has no adapter bank (ctta_unet_adapter_bank)");
+  CTTA_REQUIRE(slot_of_sample || !scale_of_sample, "unet_set_adapter_rows: scale_of_sample without slot_of_sample");
+  U->tc_valid = false;   // the cached K / V^T hold the adapter terms of whatever was bound before
+  U->row_slot = slot_of_sample;
+  U->row_scale = scale_of_sample;
   return CTTA_OK;
 }
 

@@ -491,6 +491,7 @@ extern "C" ctta_status ctta_unet_forward_train(ctta_unet* U, const float* sample
                                                int text_len, float* out, void* stream) {
   CTTA_REQUIRE(U && sample && timesteps && enc && out, "unet_forward_train: null pointer");
   CTTA_REQUIRE(U->cfg.enable_training, "unet_forward_train: handle was created without enable_training");
+  CTTA_REQUIRE(!U->row_slot, "unet_forward_train: per-request adapter rows are bound (ctta_unet_set_adapter_rows); training mixes no adapters, unbind them first");
   CTTA_REQUIRE(!U->cfg.guided || guidance, "unet_forward_train: guidance is required by the guided U-Net");
   CTTA_REQUIRE(batch >= 1 && batch <= U->cfg.max_batch, "unet_forward_train: batch %d outside [1,%d]", batch, U->cfg.max_batch);
   CTTA_REQUIRE(text_len >= 1 && text_len <= U->cfg.max_text_len, "unet_forward_train: text_len %d outside [1,%d]", text_len,

@@ -4,6 +4,7 @@
 //   ctta_lora_down     D[M][r] (fp32)  = X[M][K] (bf16) * A^T         forward D = X A^T, backward dD = dY B
 //   ctta_lora_up_add   Y[M][N] (bf16) += scale * D * B^T               forward Y += D B^T, backward dX += dD A
 //   ctta_lora_up_add_t the same into a transposed result V^T[b][n][token] (how the engines keep attention values)
+//   ctta_lora_down_rows / _up_add_rows / _up_add_t_rows   the three forward operators with one adapter PER SAMPLE, from a bank
 //   ctta_lora_wgrad    G (fp32)       += scale * sum_m D[m][j] X[m][k]  dA = dD^T X, dB = dY^T D
 //   ctta_lora_sites_fwd / _bwd         the same for one to three sites on ONE input at rank <= 4 (end of this file)
 // All are skinny and memory bound (r << K): no matrix pipe, bf16 rows move as 16-byte vectors, sums are fp32.  No float
@@ -124,6 +125,153 @@ __global__ __launch_bounds__(256) void lora_up_add_t_kernel(bf16_t* __restrict__
   const int t0 = (int)(idx % tc) * W;
   const int n = (int)((idx / tc) % N);
   const int bb = (int)(idx / ((int64_t)tc * N));
+  const float* dr = d + ((size_t)bb * d_tokens + t0) * r;
+  float acc[W];
+#pragma unroll
+  for (int i = 0; i < W; ++i) acc[i] = 0.f;
+#pragma unroll
+  for (int j = 0; j < RMAX; ++j) {
+    if (j < r) {
+      const float bv = b[(size_t)n * r + j] * scale;
+#pragma unroll
+      for (int i = 0; i < W; ++i) acc[i] = fmaf(dr[(size_t)i * r + j], bv, acc[i]);
+    }
+  }
+  bf16_t* p = yt + (size_t)bb * batch_stride + (size_t)n * ldt + t0;
+  if constexpr (VEC) {
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) any = any || acc[i] != 0.f;
+    if (!any) return;
+    float f[8];
+    unpack8(*reinterpret_cast<uint4*>(p), f);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] += acc[i];
+    *reinterpret_cast<uint4*>(p) = pack8(f);
+  } else {
+    if (acc[0] != 0.f) *p = f2bf(bf2f(*p) + acc[0]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- per-sample adapters
+// The three forward operators above with one adapter PER SAMPLE: `bank` holds n_slots packed matrices slot_stride floats
+// apart, sample = row / rows_per_sample (the batch index of the transposed form) looks its slot up in a device array, and
+// a slot outside [0, n_slots) is "no adapter": nothing of the bank is read, d gets zeros, y keeps its bits.  For a valid
+// slot a row's arithmetic is that of the kernels above (same lanes per row, same chains, same fold, the same bw = b * scale),
+// so the bits are those of a launch with that slot's matrix and scale.
+__device__ __forceinline__ bool slot_valid(int slot, int n_slots) { return (unsigned)slot < (unsigned)n_slots; }
+
+// A wave may hold rows of several samples: every row picks its own a; the fold stays inside the row's LPR lanes.
+template <int RMAX, int LPR>
+__global__ __launch_bounds__(256) void lora_down_rows_kernel(const bf16_t* __restrict__ x, int ldx, int64_t M, int K,
+                                                             const float* __restrict__ bank, int64_t slot_stride, int n_slots,
+                                                             int r, int64_t rps, const int32_t* __restrict__ slot_of_sample,
+                                                             float* __restrict__ d) {
+  const int lr = threadIdx.x % LPR;
+  const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
+  float acc[RMAX];
+#pragma unroll
+  for (int j = 0; j < RMAX; ++j) acc[j] = 0.f;
+  if (row < M) {
+    const int slot = slot_of_sample[row / rps];
+    if (slot_valid(slot, n_slots)) {
+      const float* __restrict__ a = bank + (size_t)slot * slot_stride;
+      const bf16_t* xr = x + row * ldx;
+      for (int k0 = lr * 8; k0 < K; k0 += LPR * 8) {
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(xr + k0), f);
+#pragma unroll
+        for (int j = 0; j < RMAX; ++j) {
+          if (j < r) {
+            const float4 w0 = *reinterpret_cast<const float4*>(a + (size_t)j * K + k0);
+            const float4 w1 = *reinterpret_cast<const float4*>(a + (size_t)j * K + k0 + 4);
+            acc[j] = fmaf(f[0], w0.x, acc[j]); acc[j] = fmaf(f[1], w0.y, acc[j]);
+            acc[j] = fmaf(f[2], w0.z, acc[j]); acc[j] = fmaf(f[3], w0.w, acc[j]);
+            acc[j] = fmaf(f[4], w1.x, acc[j]); acc[j] = fmaf(f[5], w1.y, acc[j]);
+            acc[j] = fmaf(f[6], w1.z, acc[j]); acc[j] = fmaf(f[7], w1.w, acc[j]);
+          }
+        }
+      }
+    }
+  }
+  // every lane of the wave takes part in the fold (rows past M and rows without an adapter carry zeros)
+#pragma unroll
+  for (int j = 0; j < RMAX; ++j)
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
+  if (row < M && lr == 0) {
+#pragma unroll
+    for (int j = 0; j < RMAX; ++j)
+      if (j < r) d[row * r + j] = acc[j];
+  }
+}
+
+// The grid is laid out per sample: blockIdx.x = sample * blocks_per_sample + block, so a block's UP_ROWS rows are one
+// sample's and its [8][r] slice of that sample's b stays in registers as above.  B * ceil(rps / 64) slices are read in
+// all, the fewest any layout reads (a slice per sample a block touches).  A block of a sample without an adapter returns.
+template <int RMAX>
+__global__ __launch_bounds__(256) void lora_up_add_rows_kernel(bf16_t* __restrict__ y, int ldy, int64_t M, int N,
+                                                               const float* __restrict__ d, const float* __restrict__ bank,
+                                                               int64_t slot_stride, int n_slots, int r, int64_t rps, int bps,
+                                                               const int32_t* __restrict__ slot_of_sample,
+                                                               const float* __restrict__ scale_of_sample, float scale) {
+  const int c8 = (blockIdx.y * 32 + threadIdx.x % 32) * 8;
+  if (c8 >= N) return;
+  const int64_t sample = blockIdx.x / bps;
+  const int slot = slot_of_sample[sample];
+  if (!slot_valid(slot, n_slots)) return;
+  if (scale_of_sample) scale = scale_of_sample[sample];
+  const float* __restrict__ b = bank + (size_t)slot * slot_stride;
+  float bw[RMAX][8];
+#pragma unroll
+  for (int j = 0; j < RMAX; ++j)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bw[j][i] = j < r ? b[(size_t)(c8 + i) * r + j] * scale : 0.f;
+  const int64_t s1 = (sample + 1) * rps < M ? (sample + 1) * rps : M;
+  const int64_t m0 = sample * rps + (int64_t)(blockIdx.x % bps) * UP_ROWS;
+  const int64_t m1 = m0 + UP_ROWS < s1 ? m0 + UP_ROWS : s1;
+  for (int64_t row = m0 + threadIdx.x / 32; row < m1; row += 8) {
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < RMAX; ++j) {
+      if (j < r) {
+        const float dv = d[row * r + j];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(dv, bw[j][i], acc[i]);
+      }
+    }
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) any = any || acc[i] != 0.f;
+    if (!any) continue;
+    uint4* p = reinterpret_cast<uint4*>(y + row * ldy + c8);
+    float f[8];
+    unpack8(*p, f);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] += acc[i];
+    *p = pack8(f);
+  }
+}
+
+template <int RMAX, bool VEC>
+__global__ __launch_bounds__(256) void lora_up_add_t_rows_kernel(bf16_t* __restrict__ yt, int ldt, int64_t batch_stride, int batch,
+                                                                 int tokens, int N, const float* __restrict__ d, int d_tokens,
+                                                                 const float* __restrict__ bank, int64_t slot_stride, int n_slots,
+                                                                 int r, const int32_t* __restrict__ slot_of_sample,
+                                                                 const float* __restrict__ scale_of_sample, float scale) {
+  constexpr int W = VEC ? 8 : 1;
+  const int tc = tokens / W;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)batch * N * tc) return;
+  const int t0 = (int)(idx % tc) * W;
+  const int n = (int)((idx / tc) % N);
+  const int bb = (int)(idx / ((int64_t)tc * N));
+  const int slot = slot_of_sample[bb];
+  if (!slot_valid(slot, n_slots)) return;
+  if (scale_of_sample) scale = scale_of_sample[bb];
+  const float* __restrict__ b = bank + (size_t)slot * slot_stride;
   const float* dr = d + ((size_t)bb * d_tokens + t0) * r;
   float acc[W];
 #pragma unroll
@@ -300,6 +448,95 @@ extern "C" ctta_status ctta_lora_up_add_t(void* yt, int ldt, int64_t batch_strid
                                 tokens, n, d, d_tokens, b, r, scale);                                                         \
     else hipLaunchKernelGGL((lora_up_add_t_kernel<RM, false>), grid, dim3(256), 0, s, (bf16_t*)yt, ldt, batch_stride, batch,    \
                             tokens, n, d, d_tokens, b, r, scale);                                                             \
+  } while (0)
+  LORA_RMAX_DISPATCH(r, CALL);
+#undef CALL
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+// ---- per-sample adapters: the dispatch rules (lanes per row by k, RMAX by r, the vector path of the transposed form) are
+// those of the three entry points above, so a row with a valid slot gets their bits
+extern "C" ctta_status ctta_lora_down_rows(const void* x, int ldx, int64_t m, int k, const float* a_bank, int64_t slot_stride,
+                                           int n_slots, int r, int64_t rows_per_sample, const int32_t* slot_of_sample, float* d,
+                                           void* stream) {
+  CTTA_REQUIRE(x && a_bank && d && slot_of_sample, "lora_down_rows: null pointer");
+  CTTA_REQUIRE(r >= 1 && r <= 16, "lora_down_rows: rank %d outside [1,16]", r);
+  CTTA_REQUIRE(m >= 0 && k >= 8 && k % 8 == 0 && ldx >= k && ldx % 8 == 0, "lora_down_rows: m=%lld k=%d ldx=%d (k, ldx multiples of 8, ldx >= k)",
+               (long long)m, k, ldx);
+  CTTA_REQUIRE(n_slots >= 1 && slot_stride >= (int64_t)r * k && slot_stride % 4 == 0 && rows_per_sample >= 1,
+               "lora_down_rows: n_slots=%d slot_stride=%lld (a multiple of 4, at least r * k) rows_per_sample=%lld", n_slots,
+               (long long)slot_stride, (long long)rows_per_sample);
+  CTTA_REQUIRE(aligned16(x) && aligned16(a_bank), "lora_down_rows: x and a_bank must be 16-byte aligned");
+  if (m == 0) return CTTA_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bf16_t* xp = (const bf16_t*)x;
+#define LAUNCH_LPR(RM, LPR)                                                                                                \
+  hipLaunchKernelGGL((lora_down_rows_kernel<RM, LPR>), dim3((unsigned)cdiv64(m, 256 / LPR)), dim3(256), 0, s, xp, ldx, m, k, \
+                     a_bank, slot_stride, n_slots, r, rows_per_sample, slot_of_sample, d)
+#define CALL(RM)                             \
+  do {                                       \
+    if (k <= 64) LAUNCH_LPR(RM, 8);          \
+    else if (k <= 128) LAUNCH_LPR(RM, 16);   \
+    else if (k <= 256) LAUNCH_LPR(RM, 32);   \
+    else LAUNCH_LPR(RM, 64);                 \
+  } while (0)
+  LORA_RMAX_DISPATCH(r, CALL);
+#undef CALL
+#undef LAUNCH_LPR
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_lora_up_add_rows(void* y, int ldy, int64_t m, int n, const float* d, const float* b_bank,
+                                             int64_t slot_stride, int n_slots, int r, int64_t rows_per_sample,
+                                             const int32_t* slot_of_sample, const float* scale_of_sample, float scale,
+                                             void* stream) {
+  CTTA_REQUIRE(y && d && b_bank && slot_of_sample, "lora_up_add_rows: null pointer");
+  CTTA_REQUIRE(r >= 1 && r <= 16, "lora_up_add_rows: rank %d outside [1,16]", r);
+  CTTA_REQUIRE(m >= 0 && n >= 8 && n % 8 == 0 && ldy >= n && ldy % 8 == 0, "lora_up_add_rows: m=%lld n=%d ldy=%d (n, ldy multiples of 8, ldy >= n)",
+               (long long)m, n, ldy);
+  CTTA_REQUIRE(n_slots >= 1 && slot_stride >= (int64_t)n * r && rows_per_sample >= 1,
+               "lora_up_add_rows: n_slots=%d slot_stride=%lld (at least n * r) rows_per_sample=%lld", n_slots, (long long)slot_stride,
+               (long long)rows_per_sample);
+  CTTA_REQUIRE(aligned16(y), "lora_up_add_rows: y must be 16-byte aligned");
+  if (m == 0) return CTTA_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t samples = cdiv64(m, rows_per_sample);
+  const int64_t bps = cdiv64(rows_per_sample < m ? rows_per_sample : m, UP_ROWS);
+  CTTA_REQUIRE(samples * bps <= 0x7fffffff, "lora_up_add_rows: %lld samples of %lld rows exceed the grid", (long long)samples,
+               (long long)rows_per_sample);
+  const dim3 grid((unsigned)(samples * bps), (unsigned)((n / 8 + 31) / 32));
+#define CALL(RM)                                                                                                                 \
+  hipLaunchKernelGGL((lora_up_add_rows_kernel<RM>), grid, dim3(256), 0, s, (bf16_t*)y, ldy, m, n, d, b_bank, slot_stride, n_slots, \
+                     r, rows_per_sample, (int)bps, slot_of_sample, scale_of_sample, scale)
+  LORA_RMAX_DISPATCH(r, CALL);
+#undef CALL
+  CTTA_LAUNCH_CHECK();
+  return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_lora_up_add_t_rows(void* yt, int ldt, int64_t batch_stride, int batch, int tokens, int n,
+                                               const float* d, int d_tokens, const float* b_bank, int64_t slot_stride, int n_slots,
+                                               int r, const int32_t* slot_of_sample, const float* scale_of_sample, float scale,
+                                               void* stream) {
+  CTTA_REQUIRE(yt && d && b_bank && slot_of_sample, "lora_up_add_t_rows: null pointer");
+  CTTA_REQUIRE(r >= 1 && r <= 16, "lora_up_add_t_rows: rank %d outside [1,16]", r);
+  CTTA_REQUIRE(batch >= 0 && tokens >= 1 && n >= 1 && ldt >= tokens && d_tokens >= tokens && batch_stride >= (int64_t)n * ldt,
+               "lora_up_add_t_rows: batch=%d tokens=%d n=%d ldt=%d d_tokens=%d batch_stride=%lld", batch, tokens, n, ldt, d_tokens,
+               (long long)batch_stride);
+  CTTA_REQUIRE(n_slots >= 1 && slot_stride >= (int64_t)n * r, "lora_up_add_t_rows: n_slots=%d slot_stride=%lld (at least n * r)",
+               n_slots, (long long)slot_stride);
+  if (batch == 0) return CTTA_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = tokens % 8 == 0 && ldt % 8 == 0 && batch_stride % 8 == 0 && aligned16(yt);
+  const dim3 grid((unsigned)cdiv64((int64_t)batch * n * (vec ? tokens / 8 : tokens), 256));
+#define CALL(RM)                                                                                                                  \
+  do {                                                                                                                            \
+    if (vec) hipLaunchKernelGGL((lora_up_add_t_rows_kernel<RM, true>), grid, dim3(256), 0, s, (bf16_t*)yt, ldt, batch_stride, batch, \
+                                tokens, n, d, d_tokens, b_bank, slot_stride, n_slots, r, slot_of_sample, scale_of_sample, scale);  \
+    else hipLaunchKernelGGL((lora_up_add_t_rows_kernel<RM, false>), grid, dim3(256), 0, s, (bf16_t*)yt, ldt, batch_stride, batch,   \
+                            tokens, n, d, d_tokens, b_bank, slot_stride, n_slots, r, slot_of_sample, scale_of_sample, scale);      \
   } while (0)
   LORA_RMAX_DISPATCH(r, CALL);
 #undef CALL

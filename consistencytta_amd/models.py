@@ -96,6 +96,32 @@ def _prompt_seeds(seeds, prompt, num_samples):
     return t.repeat_interleave(n), torch.arange(n, dtype=torch.int32).repeat(t.numel())
 
 
+def expand_adapter_rows(adapters, adapter_scales, count, num_samples=1, post_cfg=False):
+    """`adapters=` / `adapter_scales=` of the prompt-level entries (one entry per prompt: a registered adapter's name or
+    None for the base model; a strength or None for the module's `lora_scale`) -> what the U-Net's `adapter_rows` /
+    `adapter_scales` take, one entry per ROW of a query: entry i is repeated `num_samples` times (row i * n + m, the order
+    `encode_text_classifier_free` repeats the text states in), and with post-CFG the uncond half and the cond half of the
+    2B rows both carry the B rows' mapping.  Either argument may be None (all base / all default); (None, None) when both
+    are.  Pure host code: no tensor, no GPU call."""
+    if adapters is None and adapter_scales is None:
+        return None, None
+    n = int(num_samples)
+    out = []
+    for what, v in (("adapters", adapters), ("adapter_scales", adapter_scales)):
+        if v is None:
+            out.append(None)
+            continue
+        if isinstance(v, str) or not hasattr(v, "__len__"):
+            raise ValueError("%s: expected a sequence with one entry per prompt, got %r" % (what, v))
+        if len(v) != count:
+            raise ValueError("%s has %d entries, there are %d prompts" % (what, len(v), count))
+        rows = [e for e in v for _ in range(n)]
+        out.append(rows * 2 if post_cfg else rows)
+    if out[0] is None:       # strengths alone make no row differ from the base model; say so instead of ignoring them
+        raise ValueError("adapter_scales without adapters: name the adapters the strengths belong to")
+    return out[0], out[1]
+
+
 def _philox_fill(seeds, samples, draw0, out):
     """ONE launch of ctta_philox_normal: `out` (draws, B, C, H, W) f32 takes the draws draw0 .. of the rows' (seed, sample)
     streams.  `seeds` (B) int64 and `samples` (B) int32 or None live on out's device and are read when the kernel RUNS."""
@@ -307,13 +333,13 @@ def _place_stream(candidates, run_on, dev):
     return best[0], tried
 
 
-def _student_query(unet, sch, z_n, t, w_in, w_post, enc, mask):
+def _student_query(unet, sch, z_n, t, w_in, w_post, enc, mask, **unet_kw):
     """One eager query of the few-step sampler (audio_consistency_model.py:480-495, consistencytta.py:168-180): scale, the
     guided student on B rows -- 2B with post-CFG, `enc` / `mask` then hold the uncond rows first --, post-CFG combine."""
     use_cf = w_post > 1.
     z_in = torch.cat([z_n] * 2) if use_cf else z_n
     z_in = sch.scale_model_input(z_in, t)
-    zh = unet(z_in, t, guidance=w_in, encoder_hidden_states=enc, encoder_attention_mask=mask).sample
+    zh = unet(z_in, t, guidance=w_in, encoder_hidden_states=enc, encoder_attention_mask=mask, **unet_kw).sample
     if use_cf:
         u, c = zh.chunk(2)
         zh = (1 - w_post) * u + w_post * c
@@ -2131,12 +2157,16 @@ class ConsistencyTTA(nn.Module):
 
     @torch.no_grad()
     def generate_latent(self, encoder_states, encoder_mask, noise, cfg_scale_input=3., cfg_scale_post=1.,
-                        num_steps=1, uncond_states=None, uncond_mask=None, step_noise=None):
+                        num_steps=1, uncond_states=None, uncond_mask=None, step_noise=None, adapters=None,
+                        adapter_scales=None):
         """consistencytta.py:152-197 from pre-computed text states (T5 excluded).  `step_noise`: the re-noising draws of
         the few-step sampler, (num_steps - 1, B, C, H, W), one per entry of `_timesteps_host[1::2]`; None draws them with
-        `torch.randn_like` as the reference does."""
+        `torch.randn_like` as the reference does.  `adapters` / `adapter_scales`: per row of `encoder_states`, the name of
+        an adapter registered with `unet.add_adapter` (None: the base model) and its strength (`expand_adapter_rows`)."""
         sch = self.scheduler
         use_cf = cfg_scale_post > 1.
+        rows, scales = expand_adapter_rows(adapters, adapter_scales, noise.shape[0], 1, use_cf)
+        akw = {} if rows is None else dict(adapter_rows=rows, adapter_scales=scales)
         _check_step_noise(step_noise, int(num_steps) - 1, noise)
         if use_cf:
             encoder_states = torch.cat([uncond_states, encoder_states])
@@ -2145,7 +2175,7 @@ class ConsistencyTTA(nn.Module):
         z_N = noise * sch.init_noise_sigma
 
         def calc(z_n, t):
-            return _student_query(self.unet, sch, z_n, t, cfg_scale_input, cfg_scale_post, encoder_states, encoder_mask)
+            return _student_query(self.unet, sch, z_n, t, cfg_scale_input, cfg_scale_post, encoder_states, encoder_mask, **akw)
 
         zhat_0 = calc(z_N, float(sch._timesteps_host[0]))
         sch.set_timesteps(num_steps, device=noise.device)
@@ -2156,7 +2186,7 @@ class ConsistencyTTA(nn.Module):
         return zhat_0
 
     def _generate_latent_static(self, encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps,
-                                uncond_states=None, uncond_mask=None):
+                                uncond_states=None, uncond_mask=None, **unet_kw):
         """`generate_latent` in the form the captured paths record: `noise` is (num_steps, B, C, H, W) -- row 0 the initial
         draw, rows 1.. the step noise, nothing random happens here --, every query after the first takes the text K / V
         from the handle's cache on the caller's word (`reuse_text=True`: the text states are the same tensors for the
@@ -2182,7 +2212,7 @@ class ConsistencyTTA(nn.Module):
         assert len(later) == noise.shape[0] - 1, (len(later), tuple(noise.shape))
         for k in range(len(later) + 1):
             zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=encoder_states,
-                           encoder_attention_mask=encoder_mask, reuse_text=k > 0).sample
+                           encoder_attention_mask=encoder_mask, reuse_text=k > 0, **unet_kw).sample
             if k == len(later):
                 break
             t = later[k]
@@ -2637,13 +2667,16 @@ class ConsistencyTTA(nn.Module):
         return replay
 
     def _serving_inputs(self, batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post, uncond_states,
-                        uncond_mask, from_tokens, seeded=False):
+                        uncond_mask, from_tokens, seeded=False, adapters=False):
         """Static inputs of a captured serving path and the function that refills them from a replay's arguments.
         States-in: `(encoder_states, encoder_mask, noise)`; tokens-in: `(input_ids, attention_mask, noise)`.  `noise` is
         (num_steps, B, C, H, W) -- row 0 the initial draw, rows 1.. the step noise --, or (B, C, H, W) when num_steps == 1.
         `seeded`: static (B) int64 seeds and (B) int32 sample indices stand beside the noise buffer, the function takes
         `seeds` (B ints, or an int64 tensor on the host or the device) where it took `noise`, and an optional `samples=`
         (None: all zeros); the recorded work fills the noise buffer from them (`_fill_noise`).
+        `adapters`: a static (rows) int32 slot buffer and a (rows) float32 strength buffer, rows = B or 2B with post-CFG,
+        which the recorded U-Net queries read when the graph runs; `st["load_adapters"](adapters, adapter_scales)` refills
+        them from one entry per row of B (None: all base / the U-Net's `lora_scale`), checked on the host first.
         With post-CFG the uncond states are static inputs fixed HERE: (B, L, D) or (1, L, D) (broadcast); tokens-in
         captures compute them once, from the prompt "" padded to the bucket's length, when none are given."""
         from .text_encoder import check_tokens
@@ -2656,6 +2689,26 @@ class ConsistencyTTA(nn.Module):
         if seeded:
             st["seeds"] = torch.zeros(batch, dtype=torch.int64, device=dev)
             st["samples"] = torch.zeros(batch, dtype=torch.int32, device=dev)
+        if adapters:
+            if not getattr(self.unet, "lora_rank", 0):
+                raise ValueError("adapters=True: the U-Net has no adapters; call unet.enable_lora_(rank) first")
+            post = cfg_scale_post > 1.
+            st["slots"] = torch.full((batch * (2 if post else 1),), -1, dtype=torch.int32, device=dev)
+            st["ascale"] = torch.full((batch * (2 if post else 1),), float(self.unet.lora_scale), device=dev)
+
+            def load_adapters(names=None, strengths=None):
+                rows, scales = expand_adapter_rows(names, strengths, batch, 1, post)
+                if rows is None:
+                    rows = [None] * st["slots"].numel()
+                slots, scales = self.unet.adapter_row_table(len(rows), rows, scales)      # ValueError before any copy
+                self.unet._sync_bank()      # an adapter registered after the capture reaches the handle here
+                st["slots"].copy_(torch.tensor(slots, dtype=torch.int32))
+                if scales is None:
+                    st["ascale"].fill_(float(self.unet.lora_scale))
+                else:
+                    st["ascale"].copy_(torch.tensor(scales, dtype=torch.float32))
+
+            st["load_adapters"] = load_adapters
         if from_tokens:
             if self.text_encoder is None:          # the tokens are the caller's: no tokenizer is needed here
                 self._require_text_encoder()
@@ -2737,7 +2790,7 @@ class ConsistencyTTA(nn.Module):
     @torch.no_grad()
     def capture_graph(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
                       num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None, from_tokens=False,
-                      seeded=False):
+                      seeded=False, adapters=False):
         """Captures the whole pipeline (U-Net queries -> VAE decoder -> HiFi-GAN -> int16) for a fixed
         (batch, text_len) into ONE hipGraph and returns a callable `(encoder_states, encoder_mask, noise) -> pcm` that
         copies its arguments into the graph's static inputs and replays it.  The ~1500 kernel launches of a clip cost
@@ -2754,18 +2807,25 @@ class ConsistencyTTA(nn.Module):
         device -- and an optional `samples=` (B sample indices, None for zeros); the graph begins with ONE
         ctta_philox_normal launch that fills the static noise buffer from the static seeds, read when the graph runs, and
         everything after it is the graph recorded without `seeded`.  Bit-identical to the plain capture fed
-        `seeded_noise(seeds, num_steps, latent, samples)`."""
+        `seeded_noise(seeds, num_steps, latent, samples)`.
+        `adapters=True` (a U-Net with `enable_lora_` and adapters registered through `unet.add_adapter`): the callable
+        takes `adapters=` and `adapter_scales=` keywords, one entry per row of B -- a registered name or None for the
+        base model, a strength or None for the U-Net's `lora_scale`; leaving both out means all base -- and refills a
+        static slot and strength buffer before the replay.  The recorded adapter launches read the buffers when the
+        graph runs, as the seeded capture reads its seeds: one graph serves every mapping.  Composes with `seeded` and
+        `from_tokens`; identical to `forward_from_embeds(..., adapters=, adapter_scales=)`."""
         self.check_eval_mode()
         dev = self.unet.device
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
-                                        uncond_states, uncond_mask, from_tokens, seeded)
+                                        uncond_states, uncond_mask, from_tokens, seeded, adapters)
         scratch = torch.empty(4, dtype=torch.float32, device=dev)
+        akw = dict(adapter_rows=st["slots"], adapter_scales=st["ascale"]) if adapters else {}
 
         def run():
             self._fill_noise(st)
             enc, mask = self._encode_static(st) if from_tokens else (st["enc"], st["mask"])
             lat = self._generate_latent_static(enc, mask, st["noise"], cfg_scale_input, cfg_scale_post, num_steps,
-                                               st.get("unc"), st.get("unc_mask"))
+                                               st.get("unc"), st.get("unc_mask"), **akw)
             mel = self.vae.decode_first_stage(lat)
             wav = self.vae.vocode(mel)
             pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
@@ -2776,7 +2836,13 @@ class ConsistencyTTA(nn.Module):
         graph, out = _capture(run)
 
         def replay(*args, **kw):
+            if adapters:
+                names, strengths = kw.pop("adapters", None), kw.pop("adapter_scales", None)
+            elif "adapters" in kw or "adapter_scales" in kw:
+                raise ValueError("this graph was captured without adapters=True")
             load(*args, **kw)
+            if adapters:
+                st["load_adapters"](names, strengths)
             graph.replay()
             self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
             return out[2]
@@ -2888,11 +2954,16 @@ class ConsistencyTTA(nn.Module):
     encode_text_classifier_free = AudioDistilledModel.encode_text_classifier_free
 
     @torch.no_grad()
-    def forward(self, prompt, cfg_scale_input=3., cfg_scale_post=1., num_steps=1, num_samples=1, sr=16000, seeds=None):
+    def forward(self, prompt, cfg_scale_input=3., cfg_scale_post=1., num_steps=1, num_samples=1, sr=16000, seeds=None,
+                adapters=None, adapter_scales=None):
         """easy_inference/consistencytta.py:135-200: prompts -> int16 waveforms (numpy), truncated to 9.5 s.  `seeds`: one
         int per prompt; row i * num_samples + m then draws from the stream (seeds[i], sample m) of `seeded_noise` -- draw 0
-        the initial latent, draw k the k-th re-noising draw -- and not from torch's generator (None: as the reference)."""
+        the initial latent, draw k the k-th re-noising draw -- and not from torch's generator (None: as the reference).
+        `adapters` / `adapter_scales`: one entry per prompt, the name of an adapter registered with `unet.add_adapter`
+        (None: the base model) and its strength (None: the U-Net's `lora_scale`); all of a prompt's samples take them."""
         self.check_eval_mode()
+        n_prompts = 1 if isinstance(prompt, str) else len(prompt)
+        a_rows, a_scales = expand_adapter_rows(adapters, adapter_scales, n_prompts, num_samples)   # ValueError before any work
         rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
         embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
         B = embeds.shape[0]
@@ -2904,11 +2975,15 @@ class ConsistencyTTA(nn.Module):
             noise, kw["step_noise"] = draws[0], draws[1:]
         if cfg_scale_post > 1.:
             kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        if a_rows is not None:
+            kw.update(adapters=a_rows, adapter_scales=a_scales)
         return self.forward_from_embeds(embeds, mask, noise, cfg_scale_input, cfg_scale_post, num_steps, sr, **kw)
 
     @torch.no_grad()
     def forward_from_embeds(self, encoder_states, encoder_mask, noise, cfg_scale_input=3., cfg_scale_post=1.,
                             num_steps=1, sr=16000, step_noise=None, **kw):
+        """`kw`: `uncond_states` / `uncond_mask` of post-CFG, and `adapters` / `adapter_scales`, one entry per row of
+        `encoder_states` (`generate_latent`)."""
         self.check_eval_mode()
         lat = self.generate_latent(encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps,
                                    step_noise=step_noise, **kw)

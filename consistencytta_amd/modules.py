@@ -294,6 +294,15 @@ class _UNetBase(_ParamTree):
         # the fused site kernels where they take the shapes: True (= 1) in the backward groups, 3 in the forward groups too
         # (measured slower than the launches they replace there, profiles/lora_step.txt), False: per-site launches everywhere
         self.lora_fused = True
+        # per-request adapters (add_adapter): name -> slot of the handle's bank, slot -> (version, host-side tensors or
+        # None for a slot to be zeroed), what the current handle holds, and the row table bound to it
+        self.adapter_slots = 8         # slots of the bank a new handle gets; grows (to at most 64) with add_adapter
+        self._adapters = OrderedDict()
+        self._slot_state = {}
+        self._adapter_ver = 0
+        self._h_bank = None
+        self._bank_loaded = {}
+        self._h_rows = self._rows_key = self._rows_dev = None
 
     # ---- LoRA (audio_distilled_model.py:116-145 -> diffusers LoRAAttnProcessor, attention_processor.py:508-613)
     def enable_lora_(self, rank=4, generator=None):
@@ -341,6 +350,164 @@ class _UNetBase(_ParamTree):
     def lora_keys(self):
         return [k for k, _ in self.named_parameters() if "_lora." in k]
 
+    # ---- per-request adapters: a bank of named adapter sets beside the module's own, one batch row -> one of them
+    ADAPTER_SLOTS_MAX = 64
+
+    def add_adapter(self, name, state_dict):
+        """Registers the adapter set `state_dict` (the keys of `lora_keys()`, the shapes of this module's adapters) under
+        `name` for `forward(..., adapter_rows=)`; the same name again replaces that set in its slot.  Everything is checked
+        here, on the host, and the error names the key; the upload into the handle's bank happens at the next forward.  At
+        most 64 adapters.  The module's own adapter parameters (what `enable_lora_` set up and training moves) are not
+        touched: they serve the calls that pass no `adapter_rows`."""
+        if not self.lora_rank:
+            raise ValueError("add_adapter: the module has no adapters; call enable_lora_(rank) first")
+        if not isinstance(name, str) or not name:
+            raise ValueError("add_adapter: the name must be a non-empty string, got %r" % (name,))
+        own = dict(self.named_parameters())
+        keys = self.lora_keys()
+        unknown = sorted(k for k in state_dict if k not in own or "_lora." not in k)
+        if unknown:
+            raise KeyError("add_adapter(%r): unexpected key '%s' (the accepted keys are lora_keys())" % (name, unknown[0]))
+        sd = OrderedDict()
+        for k in keys:
+            if k not in state_dict:
+                raise KeyError("add_adapter(%r): missing key '%s'" % (name, k))
+            v = state_dict[k]
+            want = tuple(own[k].shape)
+            if not torch.is_tensor(v) or v.ndim != 2:
+                raise ValueError("add_adapter(%r): '%s' must be a 2-D tensor" % (name, k))
+            rank = v.shape[0] if k.endswith("down.weight") else v.shape[1]
+            if rank != self.lora_rank:
+                raise ValueError("add_adapter(%r): '%s' has rank %d, the module's adapters have rank %d"
+                                 % (name, k, rank, self.lora_rank))
+            if tuple(v.shape) != want:
+                raise ValueError("add_adapter(%r): '%s' has shape %s, expected %s" % (name, k, tuple(v.shape), want))
+            sd[k] = v.detach().to(torch.float32).clone()
+        slot = self._adapters.get(name)
+        if slot is None:
+            if len(self._adapters) >= self.ADAPTER_SLOTS_MAX:
+                raise ValueError("add_adapter(%r): the bank is full (%d adapters); remove_adapter one first"
+                                 % (name, self.ADAPTER_SLOTS_MAX))
+            used = set(self._adapters.values())
+            slot = next(i for i in range(self.ADAPTER_SLOTS_MAX) if i not in used)
+            if slot >= self.adapter_slots:     # a bank is allocated once per handle: a larger one needs a new handle
+                self.adapter_slots = min(self.ADAPTER_SLOTS_MAX, max(2 * self.adapter_slots, slot + 1))
+                if self._h_bank is not None:
+                    self._engine.release()
+                    self._h_bank = None
+            self._adapters[name] = slot
+        self._adapter_ver += 1
+        self._slot_state[slot] = (self._adapter_ver, sd)
+        return slot
+
+    def adapter_names(self):
+        return list(self._adapters)
+
+    def adapter_slot(self, name):
+        """The bank slot of a registered adapter: what an int32 device tensor given as `adapter_rows` holds (-1: base)."""
+        if name not in self._adapters:
+            raise KeyError("unknown adapter %r (registered: %s)" % (name, ", ".join(self._adapters) or "none"))
+        return self._adapters[name]
+
+    def remove_adapter(self, name):
+        """Forgets `name`; its slot is zeroed at the next forward (a zero adapter is the base model) and free for reuse."""
+        slot = self.adapter_slot(name)
+        del self._adapters[name]
+        self._adapter_ver += 1
+        self._slot_state[slot] = (self._adapter_ver, None)
+
+    def _sync_bank(self):
+        """Brings the current handle's bank up to the registered adapters: allocates it (a rebuilt handle starts without
+        one), then uploads every slot whose contents changed since this handle last saw it."""
+        e = self._engine
+        if e.h is None or (not self._slot_state and self._h_bank is None):
+            return
+        L_, dev = N.lib(), self.device
+        with torch.cuda.device(dev):
+            if self._h_bank is not e.h:
+                N.check(L_.ctta_unet_adapter_bank(e.h, int(self.adapter_slots), N.stream_ptr()))
+                self._h_bank, self._bank_loaded = e.h, {}
+            for slot, (ver, sd) in sorted(self._slot_state.items()):
+                have = self._bank_loaded.get(slot)
+                if have == ver:
+                    continue
+                if sd is None and have is None:     # removed before this handle ever loaded it: the slot is still zero
+                    self._bank_loaded[slot] = ver
+                    continue
+                if sd is None:
+                    sd = OrderedDict((k, torch.zeros_like(p)) for k, p in self.named_parameters() if "_lora." in k)
+                table, keep = N.tensor_table(OrderedDict((k, v.to(dev)) for k, v in sd.items()))
+                N.check(L_.ctta_unet_load_adapter_slot(e.h, slot, table, len(table), N.stream_ptr()))
+                self._bank_loaded[slot] = ver
+
+    def adapter_row_table(self, batch, adapter_rows, adapter_scales):
+        """Host-side check of a call's `adapter_rows` / `adapter_scales` -> (slots, scales): a list of `batch` slot indices
+        (-1: base model) or the int32 device tensor as given, and a list of `batch` floats, the float32 device tensor as
+        given, or None (every row takes `lora_scale`).  Raises before anything is uploaded; no GPU work."""
+        slots = adapter_rows
+        if adapter_rows is None:
+            slots = [-1] * batch
+        elif torch.is_tensor(adapter_rows):
+            if adapter_rows.dtype != torch.int32 or adapter_rows.ndim != 1 or adapter_rows.numel() < batch:
+                raise ValueError("adapter_rows: a tensor must be 1-D int32 with at least batch = %d entries, got %s %s"
+                                 % (batch, adapter_rows.dtype, tuple(adapter_rows.shape)))
+            if not adapter_rows.is_cuda:
+                raise ValueError("adapter_rows: a tensor of slot indices must live on the device (host callers pass names)")
+        else:
+            slots = list(adapter_rows)
+            if len(slots) != batch:
+                raise ValueError("adapter_rows has %d entries, the batch has %d rows" % (len(slots), batch))
+            slots = [-1 if n is None else self.adapter_slot(n) for n in slots]
+        scales = adapter_scales
+        if torch.is_tensor(adapter_scales) and adapter_scales.is_cuda:
+            if adapter_scales.dtype != torch.float32 or adapter_scales.ndim != 1 or adapter_scales.numel() < batch:
+                raise ValueError("adapter_scales: a tensor must be 1-D float32 with at least batch = %d entries, got %s %s"
+                                 % (batch, adapter_scales.dtype, tuple(adapter_scales.shape)))
+        elif adapter_scales is not None:
+            scales = adapter_scales.tolist() if torch.is_tensor(adapter_scales) else list(adapter_scales)
+            if len(scales) != batch:
+                raise ValueError("adapter_scales has %d entries, the batch has %d rows" % (len(scales), batch))
+            scales = [float(self.lora_scale if s is None else s) for s in scales]
+            for i, s in enumerate(scales):
+                if not math.isfinite(s):
+                    raise ValueError("adapter_scales[%d] = %r is not finite" % (i, s))
+        return slots, scales
+
+    def unbind_adapter_rows(self):
+        """Back to the single-adapter path, as a `forward` without `adapter_rows` does on its way."""
+        if self._bind_adapter_rows(None, None):
+            self._text_key = None
+
+    def _bind_adapter_rows(self, slots, scales):
+        """Binds (or, both None, unbinds) the row table on the current handle.  True when the rows' adapters may differ
+        from the previous forward's -- another mapping, other array contents, a new handle, a bank upload -- so the text
+        cache, which holds K / V^T with the adapter terms, must not be reused."""
+        e, L_ = self._engine, N.lib()
+        if slots is None:
+            if self._h_rows is e.h and self._rows_key is not None:
+                N.check(L_.ctta_unet_set_adapter_rows(e.h, None, None))
+                self._rows_key = self._rows_dev = None
+                return True
+            self._h_rows = self._rows_key = self._rows_dev = None
+            return False
+        loaded = dict(self._bank_loaded), self._h_bank
+        self._sync_bank()
+        if self._h_bank is not e.h:      # no adapter was ever registered: an empty bank, every valid slot is the base model
+            with torch.cuda.device(self.device):
+                N.check(L_.ctta_unet_adapter_bank(e.h, int(self.adapter_slots), N.stream_ptr()))
+            self._h_bank, self._bank_loaded = e.h, {}
+        # device arrays by identity + version counter (as the text states; `_rows_dev` keeps them alive), host values by value
+        key = tuple((id(v), v._version) if torch.is_tensor(v) else (None if v is None else tuple(v)) for v in (slots, scales))
+        changed = loaded != (self._bank_loaded, self._h_bank)
+        if self._h_rows is not e.h or key != self._rows_key:
+            dev = self.device
+            s_dev = slots if torch.is_tensor(slots) else torch.tensor(slots, dtype=torch.int32).to(dev)
+            c_dev = scales if scales is None or torch.is_tensor(scales) else torch.tensor(scales, dtype=torch.float32).to(dev)
+            N.check(L_.ctta_unet_set_adapter_rows(e.h, N.ptr(s_dev), N.ptr(c_dev)))
+            self._h_rows, self._rows_key, self._rows_dev = e.h, key, (s_dev, c_dev)     # the handle reads them: kept alive
+            changed = True
+        return changed
+
     def merge_lora_(self):
         """Folds every adapter into its base weight, W += lora_scale * up @ down (fp32, in place; the strength the module
         serves with, 1.0 unless `lora_scale` was set), and drops the adapters: the module is a plain U-Net again and
@@ -361,6 +528,9 @@ class _UNetBase(_ParamTree):
                 del m._modules["processor"]
         self._frozen_keys = ("guidance_proj.weight",)
         self.lora_rank = 0
+        self._adapters.clear()         # the bank goes with the adapters (and with the handle: its key names the rank)
+        self._slot_state.clear()
+        self._h_bank = self._h_rows = self._rows_key = self._rows_dev = None
         self._drop_flat_()
         return self
 
@@ -471,7 +641,7 @@ class _UNetBase(_ParamTree):
         return float(cross_attention_kwargs["scale"])
 
     def _forward(self, sample, timestep, guidance, encoder_hidden_states, encoder_attention_mask, train=False,
-                 reuse_text=None, lora_scale=None):
+                 reuse_text=None, lora_scale=None, adapter_rows=None, adapter_scales=None):
         if sample.ndim != 4 or sample.shape[1] != self._cfg["in_channels"]:
             raise ValueError("sample must be (batch, %d, height, width), got %s"
                              % (self._cfg["in_channels"], tuple(sample.shape)))
@@ -482,11 +652,21 @@ class _UNetBase(_ParamTree):
         if encoder_hidden_states.shape[0] != B or encoder_hidden_states.shape[2] != self._cfg["cross_attention_dim"]:
             raise ValueError("encoder_hidden_states shape %s does not match batch %d / cross_attention_dim %d"
                              % (tuple(encoder_hidden_states.shape), B, self._cfg["cross_attention_dim"]))
+        slots = scales = None
+        if adapter_rows is not None or adapter_scales is not None:     # checked on the host before anything is uploaded
+            if not self.lora_rank:
+                raise ValueError("adapter_rows / adapter_scales: the module has no adapters; call enable_lora_(rank) first")
+            if train:
+                raise ValueError("forward_train takes no adapter_rows: training mixes no adapters")
+            slots, scales = self.adapter_row_table(B, adapter_rows, adapter_scales)
         dev = self.device
         if not sample.is_cuda:
             raise N.CttaError("sample is on %s: the HIP engine has no CPU path" % sample.device)
         had_handle, ver0 = self._h_unet is not None, self._engine.version
         self._ensure(B, H, W, L)
+        # a training forward leaves the binding alone: with rows bound the handle refuses it (unbind_adapter_rows first)
+        if not train and self._bind_adapter_rows(slots, scales):
+            self._text_key = None      # the cached K / V^T hold the previous mapping's adapter terms
         reuse = self._text_unchanged(encoder_hidden_states, encoder_attention_mask, B, reuse_text)
         reuse = reuse and not train and had_handle and ver0 == self._engine.version  # same handle, same packed weights
         x = sample.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -618,7 +798,7 @@ class UNet2DConditionGuidedModel(_UNetBase):
     def forward(self, sample, timestep, guidance, encoder_hidden_states, class_labels=None, timestep_cond=None,
                 guidance_cond=None, attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
-                encoder_attention_mask=None, return_dict=True, **kwargs):
+                encoder_attention_mask=None, return_dict=True, adapter_rows=None, adapter_scales=None, **kwargs):
         for name, v in (("class_labels", class_labels), ("timestep_cond", timestep_cond),
                         ("guidance_cond", guidance_cond), ("attention_mask", attention_mask),
                         ("down_block_additional_residuals", down_block_additional_residuals),
@@ -626,7 +806,8 @@ class UNet2DConditionGuidedModel(_UNetBase):
             if v is not None:
                 raise NotImplementedError("%s is not used on the ConsistencyTTA path and is not supported" % name)
         out = self._forward(sample, timestep, guidance, encoder_hidden_states, encoder_attention_mask,
-                            reuse_text=kwargs.get("reuse_text"), lora_scale=self._call_lora_scale(cross_attention_kwargs))
+                            reuse_text=kwargs.get("reuse_text"), lora_scale=self._call_lora_scale(cross_attention_kwargs),
+                            adapter_rows=adapter_rows, adapter_scales=adapter_scales)
         return UNet2DConditionOutput(sample=out) if return_dict else (out,)
 
 
@@ -638,9 +819,10 @@ class UNet2DConditionModel(_UNetBase):
     def forward(self, sample, timestep, encoder_hidden_states, class_labels=None, timestep_cond=None,
                 attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
-                encoder_attention_mask=None, return_dict=True, **kwargs):
+                encoder_attention_mask=None, return_dict=True, adapter_rows=None, adapter_scales=None, **kwargs):
         out = self._forward(sample, timestep, None, encoder_hidden_states, encoder_attention_mask,
-                            reuse_text=kwargs.get("reuse_text"), lora_scale=self._call_lora_scale(cross_attention_kwargs))
+                            reuse_text=kwargs.get("reuse_text"), lora_scale=self._call_lora_scale(cross_attention_kwargs),
+                            adapter_rows=adapter_rows, adapter_scales=adapter_scales)
         return UNet2DConditionOutput(sample=out) if return_dict else (out,)
 
 

@@ -119,6 +119,31 @@ ctta_status ctta_unet_load_adapters(ctta_unet* h, const ctta_tensor* weights, in
  * summation order only.  A change of `scale` drops the text cache.  Defaults (1, 1.0f): the fused backward measured 3.4x
  * faster than its launches, the fused forward slower than its own (profiles/lora_step.txt), so it is opt-in (fused = 3). */
 ctta_status ctta_unet_set_lora(ctta_unet* h, int fused, float scale);
+/* Per-request adapters: one batch, a different adapter (and strength) per row.  diffusers' LoRAAttnProcessor carries one
+ * adapter set and takes one `scale` per call (attention_processor.py:508-613, `__call__(..., scale=)`); a server that offers
+ * several fine-tunes of one base checkpoint wants both per row, with the base GEMMs shared by the whole batch.
+ *   ctta_unet_adapter_bank     : gives a handle with adapters (created from a table that named some) a zero-filled bank of
+ *       `slots` in [1, 64] adapter sets: per site A [slots][r][k_pad] and B [slots][n_pad][r] beside the handle's own pair.
+ *       Once per handle -- a second call with the same count changes nothing, with another count it fails -- and freed with
+ *       the handle.  A slot that was never loaded is all zeros and behaves as the base model.
+ *   ctta_unet_load_adapter_slot: packs one adapter set into one slot through the site maps of the handle's own adapters.  The
+ *       rules of ctta_unet_load_adapters: names without `_lora.` are ignored, a missing tensor of an attention's eight is
+ *       named, a rank other than the handle's fails.  Neither the handle's own adapters nor any base pack is touched; the
+ *       text cache is dropped.
+ *   ctta_unet_set_adapter_rows : binds DEVICE arrays of at least `batch` entries (of every later forward): slot_of_sample
+ *       int32 -- a slot of the bank, or -1 (any value outside the bank) for the base model -- and scale_of_sample float, or
+ *       NULL: every row takes the handle's scale (ctta_unet_set_lora).  The caller keeps the arrays alive; their CONTENTS are
+ *       read when the kernels run, so a captured graph serves another mapping on its next replay without being recorded
+ *       again.  slot_of_sample NULL unbinds: the handle is back on its single-adapter path, launch for launch.  Binding,
+ *       rebinding and unbinding drop the text cache.  The cache holds K / V^T WITH the rows' adapter terms: a caller that
+ *       rewrites the arrays' contents between two forwards must not ask for ctta_unet_reuse_text across that change (the
+ *       handle cannot see the rewrite).
+ * With rows bound, ctta_unet_forward runs the per-site ctta_lora_*_rows launches at every site (whatever bit 1 of `fused`
+ * says; there is no fused rows form), the handle's own adapters are not applied, and ctta_unet_forward_train fails: training
+ * mixes no adapters. */
+ctta_status ctta_unet_adapter_bank(ctta_unet* h, int slots, void* stream);
+ctta_status ctta_unet_load_adapter_slot(ctta_unet* h, int slot, const ctta_tensor* weights, int n_weights, void* stream);
+ctta_status ctta_unet_set_adapter_rows(ctta_unet* h, const int32_t* slot_of_sample, const float* scale_of_sample);
 /* sample (B,C,H,W) f32; timesteps (B) f32; guidance (B) f64 or NULL when !guided;
  * enc (B,L,X) f32; mask (B,L) u8 (1 = keep) or NULL; out (B,Cout,H,W) f32. */
 /* One-shot hint for the NEXT ctta_unet_forward / _forward_train on this handle: reuse != 0 promises that its
@@ -1162,6 +1187,30 @@ ctta_status ctta_lora_up_add(void* y, int ldy, int64_t m, int n, const float* d,
                              float scale, void* stream);
 ctta_status ctta_lora_up_add_t(void* yt, int ldt, int64_t batch_stride, int batch, int tokens, int n, const float* d,
                                int d_tokens, const float* b, int r, float scale, void* stream);
+/* The three forward operators with one adapter PER SAMPLE (a batch whose rows ask for different fine-tunes over one base
+ * model; diffusers gives a call one strength, attention_processor.py:508-613 `LoRAAttnProcessor.__call__(..., scale=)`, and
+ * one adapter set -- here both are looked up per row).  A *bank* is n_slots packed matrices slot_stride floats apart, each in
+ * the layout and under the padded-column contract above: a_bank slots are [r][k] (slot_stride a multiple of 4, >= r * k),
+ * b_bank slots are [n][r].  sample = row / rows_per_sample (the batch index of the transposed form); slot_of_sample is a
+ * DEVICE int32 array, scale_of_sample a DEVICE float array or NULL, both read when the kernel runs, so a captured graph
+ * serves whatever they hold at replay.
+ *   down_rows     : d[row][:] = x[row] * a_bank[slot]^T where slot is in [0, n_slots), d[row][:] = 0 otherwise
+ *   up_add_rows   : y[row] += s * d[row] * b_bank[slot]^T, s = scale_of_sample[sample] when the array is given, `scale`
+ *                   otherwise (not their product)
+ *   up_add_t_rows : the same into yt[batch][n][tokens], tokens / d_tokens as ctta_lora_up_add_t
+ * A slot outside [0, n_slots) -- -1, the documented "base model", or any index too large -- reads nothing of the bank and
+ * stores nothing to y: no value in a device array makes a kernel read outside the bank.  For a valid slot a row's result is
+ * BIT FOR BIT that of ctta_lora_down / _up_add / _up_add_t on that row with that slot's matrix and that scale (same lanes
+ * per row by k, same fold and fmaf chains, same rank dispatch, same b * scale pre-multiply, same "store nothing where all
+ * eight sums are zero").  The grid of up_add_rows is per sample, so rows_per_sample need not be a multiple of anything. */
+ctta_status ctta_lora_down_rows(const void* x, int ldx, int64_t m, int k, const float* a_bank, int64_t slot_stride, int n_slots,
+                                int r, int64_t rows_per_sample, const int32_t* slot_of_sample, float* d, void* stream);
+ctta_status ctta_lora_up_add_rows(void* y, int ldy, int64_t m, int n, const float* d, const float* b_bank, int64_t slot_stride,
+                                  int n_slots, int r, int64_t rows_per_sample, const int32_t* slot_of_sample,
+                                  const float* scale_of_sample, float scale, void* stream);
+ctta_status ctta_lora_up_add_t_rows(void* yt, int ldt, int64_t batch_stride, int batch, int tokens, int n, const float* d,
+                                    int d_tokens, const float* b_bank, int64_t slot_stride, int n_slots, int r,
+                                    const int32_t* slot_of_sample, const float* scale_of_sample, float scale, void* stream);
 size_t ctta_lora_wgrad_scratch_floats(int64_t m, int k, int r);
 ctta_status ctta_lora_wgrad(const float* d, const void* x, int ldx, int64_t m, int k, int r, float scale, float* g,
                             int64_t g_stride_r, int64_t g_stride_k, const int32_t* col_map, float* scratch, void* stream);

@@ -36,6 +36,12 @@ plain captures fed a device `torch.randn` per call, at the plain mode's shape an
 beside the draws and uploads it replaces (see `seeded_leg`):
 
   python tools/serve_bench.py --seeded --out profiles/seeded_serving.txt
+
+`--adapters` runs the adapter leg alone: a batch whose rows ask for four different LoRA adapters (one captured graph, the
+adapter looked up per row) beside the plain path, the single-adapter path and four quarter-batch replays with an
+adapter reload in front of each (see `adapters_leg`):
+
+  python tools/serve_bench.py --adapters --out profiles/lora_mixed.txt
 """
 import argparse
 import json
@@ -525,8 +531,144 @@ def seeded_leg(args):
             f.write(json.dumps(result, indent=1) + "\n")
 
 
+def adapters_leg(args):
+    """`--adapters`: what a batch costs when its rows ask for different LoRA adapters.  Light U-Net (`--tiny`: the tiny one),
+    `--batch` clips, rank 4, four adapters, one query, states in, every form one captured hipGraph of the whole pipeline, in
+    alternating windows:
+
+      (a) plain            no adapters at all
+      (b) single_adapter   one adapter for all rows on the single-adapter path (the module's own adapters)
+      (c) mixed_rows       capture_graph(adapters=True): a quarter of the rows per adapter, looked up per row
+      (d) split_and_swap   what a server does without (c): four quarter-batch single-adapter replays with an adapter-only
+                           reload (ctta_unet_load_adapters) in front of each
+
+    (c) / (b) is the price of the per-row lookup, (c) / (d) what mixing buys.  Checked before anything is timed: (c) with one
+    adapter in every row gives the latent of (b) bit for bit.  No threshold: the leg records."""
+    import torch
+    from collections import OrderedDict
+    from consistencytta_amd import _native as N
+    from consistencytta_amd import modules, spec
+    from consistencytta_amd.models import ConsistencyTTA
+    dev = "cuda:0"
+    B, L, RANK, NA = args.batch, args.text_len, 4, 4
+    if B % NA:
+        raise SystemExit("--batch must be a multiple of %d" % NA)
+    Bq = B // NA
+    if args.tiny:
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        import cases
+        ucfg, latent = dict(cases.TINY_UNET), (8, 32, 16)
+        make_vae = lambda: modules.AutoencoderKL(ddconfig=cases.TINY_VAE_DD, embed_dim=8, scale_factor=0.9,      # noqa: E731
+                                                 hifigan_config=cases.TINY_HIFIGAN)
+    else:
+        ucfg, latent = spec.LIGHT_UNET_CONFIG, (8, 256, 16)
+        make_vae = lambda: modules.AutoencoderKL(ddconfig=spec.VAE_DDCONFIG, embed_dim=8,                        # noqa: E731
+                                                 scale_factor=0.9227914214134216)
+    D = ucfg["cross_attention_dim"]
+    g = torch.Generator(device="cpu").manual_seed(5)
+    sets = []
+    for _ in range(NA):          # down as LoRALinearLayer's init (std 1 / rank), up small but non-zero
+        sets.append(OrderedDict((k, torch.randn(shape, generator=g) * (1.0 / RANK if k.endswith("down.weight") else 0.02))
+                                for k, shape in spec.lora_param_spec(ucfg, RANK).items()))
+
+    def build_pipe(lora):
+        v = make_vae()
+        p = ConsistencyTTA(unet_config=ucfg, vae=v)
+        p.to(dev)
+        p.unet.init_random_(seed=0)
+        v.init_random_(seed=1)
+        if lora:
+            p.unet.enable_lora_(RANK)
+            p.unet.load_state_dict(sets[0], strict=False)
+        return p.eval().requires_grad_(False)
+    plain, single, bank, swap = build_pipe(False), build_pipe(True), build_pipe(True), build_pipe(True)
+    names = ["style%d" % i for i in range(NA)]
+    for n, sd in zip(names, sets):
+        bank.unet.add_adapter(n, sd)
+    W_IN = 4.0
+    batches = []
+    for _ in range(2):
+        lens = torch.randint(min(6, L), L + 1, (B,), generator=g)
+        batches.append(((torch.randn(B, L, D, generator=g) * 0.25).to(dev), (torch.arange(L)[None, :] < lens[:, None]).to(dev),
+                        torch.randn((B,) + latent, generator=g).to(dev)))
+    kw = dict(cfg_scale_input=W_IN, cross_attention_dim=D, latent=latent, num_steps=1)
+    g_plain, g_single = plain.capture_graph(B, L, **kw), single.capture_graph(B, L, **kw)
+    g_mixed = bank.capture_graph(B, L, adapters=True, **kw)
+    g_swap = swap.capture_graph(Bq, L, **kw)
+    mixed_rows = [names[i // Bq] for i in range(B)]
+    # (d) in its cheapest form: the four sets are device resident, a swap is ONE multi-tensor copy into the module's adapter
+    # parameters and ONE ctta_unet_load_adapters from them (the same source pointers every time: no job table is uploaded)
+    own = OrderedDict((k, p.data) for k, p in swap.unet.named_parameters() if "_lora." in k)
+    own_table, _keep = N.tensor_table(own)
+    dev_sets = [[sd[k].to(dev) for k in own] for sd in sets]
+    swap_h = swap.unet._h_unet
+
+    def swap_call(enc, mask, noise):
+        out = None
+        for i, srcs in enumerate(dev_sets):
+            torch._foreach_copy_(list(own.values()), srcs)
+            N.check(N.lib().ctta_unet_load_adapters(swap_h, own_table, len(own_table), N.stream_ptr()))
+            out = g_swap(enc[i * Bq:(i + 1) * Bq], mask[i * Bq:(i + 1) * Bq], noise[i * Bq:(i + 1) * Bq])
+        return out
+
+    enc, mask, noise = batches[0]
+    g_single(enc, mask, noise)
+    want = g_single.outputs[0].clone()
+    g_mixed(enc, mask, noise, adapters=[names[0]] * B)
+    parity = {"mixed_rows_all_one_adapter_equals_single_adapter": bool(torch.equal(g_mixed.outputs[0], want))}
+    g_mixed(enc, mask, noise, adapters=mixed_rows)
+    parity["mixed_rows_differ_from_single_adapter"] = not bool(torch.equal(g_mixed.outputs[0], want))
+    swap_call(enc, mask, noise)
+    last = g_swap.outputs[0].clone()
+    parity["swap_last_quarter_differs_from_adapter_0"] = not bool(torch.equal(last, want[:Bq]))
+    if not all(parity.values()):
+        raise SystemExit("the adapter forms disagree: %s" % parity)
+
+    turn = [0]
+
+    def nxt():
+        turn[0] ^= 1
+        return batches[turn[0]]
+    forms = {"plain": lambda: g_plain(*nxt()), "single_adapter": lambda: g_single(*nxt()),
+             "mixed_rows": lambda: g_mixed(*nxt(), adapters=mixed_rows), "split_and_swap": lambda: swap_call(*nxt())}
+    for fn in forms.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    windows = {k: [] for k in forms}
+    for _ in range(args.rounds):
+        for k, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            windows[k].append((time.perf_counter() - t0) / args.steps * 1e3)
+    med = {k: statistics.median(v) for k, v in windows.items()}
+    result = {
+        "tool": "tools/serve_bench.py --adapters", "device": torch.cuda.get_device_name(0), "tiny": bool(args.tiny),
+        "clips_per_call": B, "adapters": NA, "rows_per_adapter": Bq, "rank": RANK, "text_len": L, "num_steps": 1,
+        "latent": list(latent), "steps_per_window": args.steps, "rounds": args.rounds, "warmup_calls": args.warmup,
+        "unit": "ms per call of one batch of %d clips (split_and_swap: %d reloads + %d replays of %d clips)" % (B, NA, NA, Bq),
+        "timing": "host clock around a window of calls ending in a device synchronise; forms alternate within a round",
+        "parity": parity,
+        "ms_per_call_median": {k: round(v, 3) for k, v in med.items()},
+        "clips_per_s_median": {k: round(B / v * 1e3, 1) for k, v in med.items()},
+        "ms_per_call_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()},
+        "ratios_of_medians": {"single_over_plain": round(med["single_adapter"] / med["plain"], 4),
+                              "mixed_over_single": round(med["mixed_rows"] / med["single_adapter"], 4),
+                              "mixed_over_split_and_swap": round(med["mixed_rows"] / med["split_and_swap"], 4)},
+    }
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--adapters", action="store_true", help="only the adapter leg: a batch with a different LoRA adapter per "
+                    "row beside the plain, the single-adapter and the split-and-swap forms")
     ap.add_argument("--seeded", action="store_true", help="only the seeded leg: the seeded captures beside the plain captures "
                     "fed a device torch.randn per call, and the fill launch beside the draws and uploads it replaces")
     ap.add_argument("--long", action="store_true", help="only the long-clip leg: the captured long path beside the captured "
@@ -551,6 +693,8 @@ def main():
     from consistencytta_amd.models import ConsistencyTTA
     if not torch.cuda.is_available():
         raise SystemExit("serve_bench needs a GPU: there is no CPU path and no number without one")
+    if args.adapters:
+        return adapters_leg(args)
     if args.edit:
         return edit_leg(args)
     if args.long:
