@@ -202,13 +202,17 @@ __global__ void cfg_combine_keep_kernel(const float4* __restrict__ u, const floa
 // mul per window, torch's add per further window, heun_add_noise_kernel and heun_scale_kernel, in their order.
 // MODE 0: cond alone; 1: uncond + cond; 2: no query output yet, x0 = 0 (the sampler's start).  COPIES 0: the sampler's end,
 // nothing is re-noised and only x0_long is written.
+// KEEP: the clip is an edit of a long source (ctta_window_fuse_edit_renoise): between the fusion and add_noise the long x0
+// becomes keep * src + (1 - keep) * x0 (keep_blend), `src` a long latent and `keep` one (latent_h, W) plane per clip, shared
+// by its channels.  Both are read at the thread's own long element, so the walk and the writes are unchanged.
 #define CTTA_MAX_WINDOWS 16
 struct WindowStarts { int s[CTTA_MAX_WINDOWS]; };
 
-template <int MODE, int COPIES>
+template <int MODE, int COPIES, bool KEEP>
 __global__ void window_fuse_renoise_kernel(const float4* __restrict__ c, const float4* __restrict__ u,
                                            const float* __restrict__ w, const WindowStarts st,
-                                           const float* __restrict__ wt, const float4* __restrict__ nz,
+                                           const float* __restrict__ wt, const float4* __restrict__ src,
+                                           const float4* __restrict__ keep, const float4* __restrict__ nz,
                                            const float* __restrict__ sigma, float4* __restrict__ x0_long,
                                            float4* __restrict__ out, int n_windows, int channels, int window_h, int latent_h,
                                            int wv, long long total, long long out_total) {
@@ -238,6 +242,7 @@ __global__ void window_fuse_renoise_kernel(const float4* __restrict__ c, const f
       acc = first ? t : make_float4(acc.x + t.x, acc.y + t.y, acc.z + t.z, acc.w + t.w);
       first = false;
     }
+    if (KEEP) acc = keep_blend(keep[((long long)b * latent_h + h) * wv + xv], src[i], acc);
     if (x0_long) x0_long[i] = acc;
     if (COPIES > 0) {
       const float s = sigma[b];
@@ -683,52 +688,76 @@ extern "C" ctta_status ctta_cfg_combine_keep(const float* uncond, const float* c
   return CTTA_OK;
 }
 
-extern "C" ctta_status ctta_window_fuse_renoise(const float* cond, const float* uncond, const float* w_post,
-                                                const int32_t* starts, const float* weights, const float* noise,
-                                                const float* sigma, float* x0_long, float* out, int copies, int batch,
-                                                int n_windows, int channels, int window_h, int latent_h, int width,
-                                                void* stream) {
-  CTTA_REQUIRE(starts && weights, "window_fuse_renoise: starts and weights are both required");
+// ctta_window_fuse_renoise (src == keep == NULL) and ctta_window_fuse_edit_renoise: one set of refusals, one launch
+static ctta_status window_fuse_launch(const char* what, const float* cond, const float* uncond, const float* w_post,
+                                      const int32_t* starts, const float* weights, const float* src, const float* keep,
+                                      const float* noise, const float* sigma, float* x0_long, float* out, int copies,
+                                      int batch, int n_windows, int channels, int window_h, int latent_h, int width,
+                                      void* stream) {
+  CTTA_REQUIRE(starts && weights, "%s: starts and weights are both required", what);
   CTTA_REQUIRE((uncond != nullptr) == (w_post != nullptr),
-               "window_fuse_renoise: uncond and w_post are given together or not at all");
-  CTTA_REQUIRE(!uncond || cond, "window_fuse_renoise: uncond without cond");
+               "%s: uncond and w_post are given together or not at all", what);
+  CTTA_REQUIRE(!uncond || cond, "%s: uncond without cond", what);
   CTTA_REQUIRE((noise != nullptr) == (out != nullptr),
-               "window_fuse_renoise: noise and out are given together (a step) or not at all (the end)");
+               "%s: noise and out are given together (a step) or not at all (the end)", what);
   CTTA_REQUIRE(out ? sigma != nullptr : x0_long != nullptr,
-               "window_fuse_renoise: a step needs sigma, the end (noise == out == NULL) needs x0_long");
-  CTTA_REQUIRE(copies == 1 || copies == 2, "window_fuse_renoise: copies=%d (1 or 2)", copies);
-  CTTA_REQUIRE(batch > 0 && channels > 0 && window_h > 0 && latent_h > 0 && width > 0, "window_fuse_renoise: empty tensor");
-  CTTA_REQUIRE(width % 4 == 0, "window_fuse_renoise: width=%d must be a multiple of 4", width);
-  CTTA_REQUIRE(n_windows >= 1 && n_windows <= CTTA_MAX_WINDOWS, "window_fuse_renoise: n_windows=%d (1 .. %d)", n_windows,
+               "%s: a step needs sigma, the end (noise == out == NULL) needs x0_long", what);
+  CTTA_REQUIRE(copies == 1 || copies == 2, "%s: copies=%d (1 or 2)", what, copies);
+  CTTA_REQUIRE(batch > 0 && channels > 0 && window_h > 0 && latent_h > 0 && width > 0, "%s: empty tensor", what);
+  CTTA_REQUIRE(width % 4 == 0, "%s: width=%d must be a multiple of 4", what, width);
+  CTTA_REQUIRE(n_windows >= 1 && n_windows <= CTTA_MAX_WINDOWS, "%s: n_windows=%d (1 .. %d)", what, n_windows,
                CTTA_MAX_WINDOWS);
-  CTTA_REQUIRE(starts[0] == 0, "window_fuse_renoise: starts[0]=%d must be 0", (int)starts[0]);
+  CTTA_REQUIRE(starts[0] == 0, "%s: starts[0]=%d must be 0", what, (int)starts[0]);
   CTTA_REQUIRE(starts[n_windows - 1] == latent_h - window_h,
-               "window_fuse_renoise: the last start %d must be latent_h - window_h = %d", (int)starts[n_windows - 1],
+               "%s: the last start %d must be latent_h - window_h = %d", what, (int)starts[n_windows - 1],
                latent_h - window_h);
   WindowStarts st;
   for (int k = 0; k < CTTA_MAX_WINDOWS; ++k) st.s[k] = k < n_windows ? (int)starts[k] : 0;
   for (int k = 0; k + 1 < n_windows; ++k) {
-    CTTA_REQUIRE(st.s[k + 1] > st.s[k], "window_fuse_renoise: starts[%d]=%d, starts[%d]=%d are not strictly increasing", k,
+    CTTA_REQUIRE(st.s[k + 1] > st.s[k], "%s: starts[%d]=%d, starts[%d]=%d are not strictly increasing", what, k,
                  st.s[k], k + 1, st.s[k + 1]);
-    CTTA_REQUIRE(st.s[k + 1] <= st.s[k] + window_h, "window_fuse_renoise: a gap between starts[%d]=%d + window_h=%d and "
-                 "starts[%d]=%d", k, st.s[k], window_h, k + 1, st.s[k + 1]);
+    CTTA_REQUIRE(st.s[k + 1] <= st.s[k] + window_h, "%s: a gap between starts[%d]=%d + window_h=%d and "
+                 "starts[%d]=%d", what, k, st.s[k], window_h, k + 1, st.s[k + 1]);
   }
   // starts[0] = 0, strictly increasing without gaps up to latent_h - window_h >= 0: every long row lies under a window and
   // every window lies inside the clip
   const int wv = width / 4;
   const long long total = (long long)batch * channels * latent_h * wv;
   const long long out_total = (long long)batch * n_windows * channels * window_h * wv;
-#define FUSE(MODE, CP)                                                                                                 \
-  hipLaunchKernelGGL((window_fuse_renoise_kernel<MODE, CP>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,  \
-                     (const float4*)cond, (const float4*)uncond, w_post, st, weights, (const float4*)noise, sigma,      \
-                     (float4*)x0_long, (float4*)out, n_windows, channels, window_h, latent_h, wv, total, out_total)
-#define FUSE_MODE(CP)                                                                                                  \
-  do { if (!cond) FUSE(2, CP); else if (uncond) FUSE(1, CP); else FUSE(0, CP); } while (0)
-  if (!out) FUSE_MODE(0); else if (copies == 2) FUSE_MODE(2); else FUSE_MODE(1);
+#define FUSE(MODE, CP, KP)                                                                                             \
+  hipLaunchKernelGGL((window_fuse_renoise_kernel<MODE, CP, KP>), dim3(grid_for(total)), dim3(256), 0,                  \
+                     (hipStream_t)stream, (const float4*)cond, (const float4*)uncond, w_post, st, weights,             \
+                     (const float4*)src, (const float4*)keep, (const float4*)noise, sigma, (float4*)x0_long,           \
+                     (float4*)out, n_windows, channels, window_h, latent_h, wv, total, out_total)
+#define FUSE_MODE(CP, KP)                                                                                              \
+  do { if (!cond) FUSE(2, CP, KP); else if (uncond) FUSE(1, CP, KP); else FUSE(0, CP, KP); } while (0)
+#define FUSE_COPIES(KP)                                                                                                \
+  do { if (!out) FUSE_MODE(0, KP); else if (copies == 2) FUSE_MODE(2, KP); else FUSE_MODE(1, KP); } while (0)
+  if (src) FUSE_COPIES(true); else FUSE_COPIES(false);
+#undef FUSE_COPIES
 #undef FUSE_MODE
 #undef FUSE
   CTTA_LAUNCH_CHECK();
   return CTTA_OK;
+}
+
+extern "C" ctta_status ctta_window_fuse_renoise(const float* cond, const float* uncond, const float* w_post,
+                                                const int32_t* starts, const float* weights, const float* noise,
+                                                const float* sigma, float* x0_long, float* out, int copies, int batch,
+                                                int n_windows, int channels, int window_h, int latent_h, int width,
+                                                void* stream) {
+  return window_fuse_launch("window_fuse_renoise", cond, uncond, w_post, starts, weights, nullptr, nullptr, noise, sigma,
+                            x0_long, out, copies, batch, n_windows, channels, window_h, latent_h, width, stream);
+}
+
+extern "C" ctta_status ctta_window_fuse_edit_renoise(const float* cond, const float* uncond, const float* w_post,
+                                                     const int32_t* starts, const float* weights, const float* src_long,
+                                                     const float* keep, const float* noise, const float* sigma,
+                                                     float* x0_long, float* out, int copies, int batch, int n_windows,
+                                                     int channels, int window_h, int latent_h, int width, void* stream) {
+  CTTA_REQUIRE(src_long && keep, "window_fuse_edit_renoise: src_long and keep are both required");
+  return window_fuse_launch("window_fuse_edit_renoise", cond, uncond, w_post, starts, weights, src_long, keep, noise, sigma,
+                            x0_long, out, copies, batch, n_windows, channels, window_h, latent_h, width, stream);
 }
 
 extern "C" ctta_status ctta_snr_mse_loss(const float* pred, const float* target, const float* sigma,

@@ -482,6 +482,52 @@ def _window_fuse(zh, B, w_post, w_dev, plan, draw, sig, latent_h, z_in=None, x0_
                                              2 if use_cf else 1, B, n, C, wh, latent_h, W, N.stream_ptr()))
 
 
+def _window_fuse_keep(zh, B, w_post, w_dev, plan, src, keep, draw, sig, latent_h, z_in=None, x0_long=None):
+    """`_window_fuse` with a long source clip: between the overlap-add and add_noise the long x0 becomes
+    keep * src + (1 - keep) * x0, still ONE launch (ctta_window_fuse_edit_renoise).  `src`: (B, C, latent_h, W); `keep`:
+    (B, latent_h * W).  `zh` None: the sampler's start, keep * src noised and cut into windows."""
+    starts, weights = plan
+    n, wh = weights.shape
+    use_cf = w_post > 1.
+    if zh is None:
+        cond, unc = None, None
+    elif use_cf and _post_cfg_fusable(w_post):
+        cond, unc = zh[B * n:], zh[:B * n]
+    elif use_cf:
+        cond, unc = (1 - w_post) * zh[:B * n] + w_post * zh[B * n:], None
+    else:
+        cond, unc = zh, None
+    C, W = src.shape[1], src.shape[3]
+    N.check(N.lib().ctta_window_fuse_edit_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
+                                                  starts, N.ptr(weights), N.ptr(src), N.ptr(keep), N.ptr(draw), N.ptr(sig),
+                                                  N.ptr(x0_long), N.ptr(z_in), 2 if use_cf else 1, B, n, C, wh, latent_h, W,
+                                                  N.stream_ptr()))
+
+
+LATENT_ROW_SAMPLES = 640       # one latent row: 4 mel frames of 160 samples at 16 kHz, 40 ms
+
+
+def _extend_rows(samples, latent_h, source_at, junction_rows):
+    """The row arithmetic of `ConsistencyTTA.extend`: a source of `samples` samples placed `source_at` seconds into a clip
+    of `latent_h` rows -> (rows, r0, k0, k1): it covers rows = samples // 640 full rows from r0 = round(source_at * 25), of
+    which [k0, k1) are kept -- `junction_rows` fewer on every side that borders generated audio."""
+    rows = int(samples) // LATENT_ROW_SAMPLES
+    r0 = int(round(float(source_at) * 25))
+    junction_rows = int(junction_rows)
+    if junction_rows < 0:
+        raise ValueError("junction_rows %d: expected 0 or more" % junction_rows)
+    if rows < 8:
+        raise ValueError("a source of %d samples covers %d latent rows: at least 8 (0.32 s)" % (samples, rows))
+    if r0 < 0:
+        raise ValueError("source_at %r: row %d lies before the clip" % (source_at, r0))
+    if r0 + rows > latent_h:
+        raise ValueError("source_at %r: rows [%d, %d) of the source do not fit the clip's %d rows"
+                         % (source_at, r0, r0 + rows, latent_h))
+    k0 = r0 + (junction_rows if r0 > 0 else 0)
+    k1 = r0 + rows - (junction_rows if r0 + rows < latent_h else 0)
+    return rows, r0, k0, max(k0, k1)
+
+
 class AudioDistilledModel(nn.Module):
     """models/audio_distilled_model.py: text encoding, CFG teacher query, EMA bookkeeping."""
 
@@ -2663,6 +2709,276 @@ class ConsistencyTTA(nn.Module):
             return out[2][:, :samples]
 
         replay.graph, replay.outputs, replay.latent_h = graph, out, Ht
+        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
+        return replay
+
+    # ---- editing long clips: the windowed sampler with a long source blended into the fused x0 between two queries
+    # (the masked sampler of audioldm/ldm.py:718-805, ddim.py:210-216 at the `duration` of pipeline.py:49-50,94-95)
+    @torch.no_grad()
+    def edit_long_latent(self, encoder_states, encoder_mask, noise, src_latent, keep_mask=None, strength=1.0,
+                         cfg_scale_input=3., cfg_scale_post=1., num_steps=4, overlap=64, window_h=256, uncond_states=None,
+                         uncond_mask=None, step_noise=None):
+        """`edit_latent` for a latent of another height, `generate_long_latent` with a source: `noise` and `src_latent`
+        are (B, C, Ht, W), `keep_mask` is (B, 1, Ht, W), (1, 1, Ht, W) or None (keeps nothing).  The student is queried on
+        the windows of `long_plan(Ht, window_h, overlap)`; after every query the windows' x0 estimates are fused and the
+        long x0 becomes keep * src + (1 - keep) * x0, re-noised with ONE long draw and cut into the next windows -- one
+        launch of ctta_window_fuse_edit_renoise, which is also the start and the end.  The last
+        r = max(1, int(strength * num_steps)) of `generate_latent`'s query times run, as in `edit_latent`: at strength 1
+        the first input is keep * src noised at the head of the 18-step table, below it the whole source noised at the
+        first remaining time.  Text rows (B, or B * n for a text per window) as in `generate_long_latent`.  `step_noise`:
+        (r - 1, B, C, Ht, W), None draws it.  Ht == window_h equals `edit_latent` bit for bit."""
+        if not torch.is_tensor(noise) or noise.ndim != 4:
+            raise ValueError("noise %s: expected (B, C, Ht, W)" % (tuple(noise.shape) if torch.is_tensor(noise) else noise,))
+        r = _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps)
+        _check_step_noise(step_noise, r - 1, noise)
+
+        def draw(k):
+            if k == 0:
+                return noise
+            return torch.randn_like(noise) if step_noise is None else step_noise[k - 1]
+        return self._long_edit_loop(encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input,
+                                    cfg_scale_post, num_steps, overlap, window_h, uncond_states, uncond_mask)
+
+    def _long_edit_loop(self, encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
+                        num_steps, overlap, window_h, uncond_states, uncond_mask):
+        """The body of `edit_long_latent` and of the captured long edit: `_long_loop` with `_edit_loop`'s source, mask and
+        query times.  Nothing but launches once `draw(k)`, the k-th long noise, is a tensor at hand."""
+        sch = self.scheduler
+        num_steps = int(num_steps)
+        B, C, Ht, W = src_latent.shape
+        starts, weights = self.long_plan(Ht, window_h, overlap)
+        n, wh = weights.shape
+        use_cf = cfg_scale_post > 1.
+        enc, mask = _window_rows(encoder_states, B, n, "encoder_states"), _window_rows(encoder_mask, B, n, "encoder_mask")
+        if use_cf:
+            enc = torch.cat([_window_rows(uncond_states, B, n, "uncond_states"), enc])
+            mask = torch.cat([_window_rows(uncond_mask, B, n, "uncond_mask"), mask])
+        if not src_latent.is_cuda:
+            raise N.CttaError("src_latent is on %s: the HIP sampler has no CPU path" % src_latent.device)
+        dev = src_latent.device
+        src = src_latent.detach().to(torch.float32).contiguous()
+        # the weights and the all-ones plane are uploaded once per layout and device: a capture's warm-up run leaves them
+        # here, so the recorded sequence holds no host -> device copy
+        cache = self.__dict__.setdefault("_long_weights", {})
+        key = (Ht, wh, n, int(overlap), str(dev))
+        if key not in cache:
+            cache[key] = weights.to(dev)
+        plan = ((N.c_int32 * n)(*starts), cache[key])
+        if keep_mask is None:
+            keep = torch.zeros(B, Ht * W, dtype=torch.float32, device=dev)
+        else:
+            keep = keep_mask.detach().to(dev, torch.float32).expand(B, 1, Ht, W).reshape(B, Ht * W).contiguous()
+        w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev) if use_cf else None
+        sch.set_timesteps(18, device=dev)
+        t_head = float(sch._timesteps_host[0])
+        sig = sch._sigma_dev(sch.index_for_timestep(t_head), B, dev)
+        sch.set_timesteps(num_steps, device=dev)
+        times = ([t_head] + [float(v) for v in sch._timesteps_host[1::2]])[num_steps - r:]
+        copies = 2 if use_cf else 1
+        z_in = torch.empty((copies * B * n, C, wh, W), dtype=torch.float32, device=dev)
+        first = sch._check(draw(0))
+        if r == num_steps:          # inpainting: keep * src, noised at the head of the 18-step table
+            start_keep = keep
+        else:                       # variation: the whole source, noised at the first remaining time
+            sig = sch._sigma_dev(sch.index_for_timestep(times[0]), B, dev)
+            ones = self.__dict__.setdefault("_long_ones", {})
+            okey = (B, Ht * W, str(dev))
+            if okey not in ones:
+                ones[okey] = torch.ones(B, Ht * W, dtype=torch.float32, device=dev)
+            start_keep = ones[okey]
+        _window_fuse_keep(None, B, cfg_scale_post, w_post, plan, src, start_keep, first, sig, Ht, z_in=z_in)
+        for k, t in enumerate(times):
+            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=enc, encoder_attention_mask=mask,
+                           reuse_text=k > 0).sample
+            if k == r - 1:
+                break
+            sig = sch._sigma_dev(sch.index_for_timestep(times[k + 1]), B, dev)
+            z_in = torch.empty_like(zh)
+            _window_fuse_keep(zh, B, cfg_scale_post, w_post, plan, src, keep, sch._check(draw(k + 1)), sig, Ht, z_in=z_in)
+        out = torch.empty((B, C, Ht, W), dtype=torch.float32, device=dev)
+        _window_fuse_keep(zh, B, cfg_scale_post, w_post, plan, src, keep, None, None, Ht, x0_long=out)
+        return out
+
+    def _source_latent_chunked(self, source_wav, latent_hw, sample_posterior=False, chunk_rows=LONG_DECODE_ROWS):
+        """`_source_latent` with the batch cut into chunks of at most chunk_rows // H clips per encoder call, as
+        `_decode_long` cuts it for the decoder."""
+        per = max(1, int(chunk_rows) // int(latent_hw[0]))
+        parts = [self._source_latent(source_wav[i:i + per], latent_hw, sample_posterior)
+                 for i in range(0, source_wav.shape[0], per)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    @torch.no_grad()
+    def edit_long_from_embeds(self, encoder_states, encoder_mask, noise, source_wav, duration, keep_mask=None, strength=1.0,
+                              cfg_scale_input=3., cfg_scale_post=1., num_steps=4, sr=16000, step_noise=None, overlap=64,
+                              window_h=256, sample_posterior=False, _chunk_rows=LONG_DECODE_ROWS, **kw):
+        """`edit_from_embeds` for a clip of `duration` seconds in [2.5, 40]: `noise` is (B, C, Ht, W) with
+        Ht = 8 * ceil(duration * 25.6 / 8); the source waveform ((B, T) in [-1, 1] at 16 kHz, padded or cut to the clip) is
+        encoded at (Ht, W) -- chunked over the batch --, then `edit_long_latent`, the decoder and HiFi-GAN at that extent
+        and the cut to int(sr * duration) samples.  int16 waveforms (numpy).  The kept region has passed through the VAE
+        and the vocoder; it is not spliced from the source."""
+        self.check_eval_mode()
+        Ht = _long_latent_h(duration)
+        if not torch.is_tensor(noise) or noise.ndim != 4 or noise.shape[2] != Ht:
+            raise ValueError("noise %s: a clip of %r s takes (B, C, %d, W)"
+                             % (tuple(noise.shape) if torch.is_tensor(noise) else noise, duration, Ht))
+        r = _check_edit_inputs(noise, noise, keep_mask, strength, num_steps)
+        _check_step_noise(step_noise, r - 1, noise)
+        self.long_plan(Ht, window_h, overlap)
+        source_wav = torch.as_tensor(source_wav)
+        if source_wav.ndim != 2 or source_wav.shape[0] != noise.shape[0]:
+            raise ValueError("source_wav %s: expected (%d, samples)" % (tuple(source_wav.shape), noise.shape[0]))
+        src = self._source_latent_chunked(source_wav, (Ht, noise.shape[3]), sample_posterior, _chunk_rows)
+        lat = self.edit_long_latent(encoder_states, encoder_mask, noise, src, keep_mask, strength, cfg_scale_input,
+                                    cfg_scale_post, num_steps, overlap, window_h, step_noise=step_noise, **kw)
+        _, pcm = self._decode_long(lat, chunk_rows=_chunk_rows)
+        return pcm.cpu().numpy()[:, :int(sr * float(duration))]
+
+    def _long_edit_draws(self, rows, B, Ht, strength, num_steps, device):
+        """(noise, kw) of `edit_long` / `extend`: one long draw from torch's generator, or the r seeded draws 0 .. r - 1."""
+        C = self.unet.config.in_channels
+        if rows is None:
+            return randn_tensor((B, C, Ht, 16), device=device, dtype=torch.float32), {}
+        shape = torch.empty(B, 0, Ht, 16)             # the strength / num_steps rules alone: r queries take r draws
+        r = _check_edit_inputs(shape, shape, None, strength, num_steps)
+        draws = self.seeded_noise(rows[0], r, (C, Ht, 16), rows[1])
+        return draws[0], dict(step_noise=draws[1:])
+
+    def _long_edit_prompts(self, prompt, source_wav, num_samples, seeds):
+        """Text states, seed rows and the (B, T) source of `edit_long` / `extend`, one source clip per prompt."""
+        rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
+        embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
+        B = embeds.shape[0]
+        source_wav = torch.as_tensor(source_wav)
+        if source_wav.ndim != 2 or source_wav.shape[0] * num_samples != B:
+            raise ValueError("source_wav %s: expected (%d, samples), one clip per prompt"
+                             % (tuple(source_wav.shape), B // num_samples))
+        return rows, embeds_cf, mask_cf, embeds, mask, source_wav.repeat_interleave(num_samples, 0)
+
+    @torch.no_grad()
+    def edit_long(self, prompt, source_wav, duration, time_mask_ratio_start_and_end=(1., 1.),
+                  freq_mask_ratio_start_and_end=(1., 1.), strength=1.0, cfg_scale_input=3., cfg_scale_post=1., num_steps=4,
+                  num_samples=1, sr=16000, overlap=64, window_h=256, sample_posterior=False, seeds=None):
+        """`edit` for a clip of `duration` seconds: prompts and source waveforms -> int16 waveforms (numpy) of
+        int(sr * duration) samples with the masked time span / frequency band regenerated or, with `strength` < 1, varied.
+        The ratios are fractions of the clip's Ht rows / 16 columns (`latent_keep_mask`).  `seeds`: as in `generate_long`,
+        the r queries take the draws 0 .. r - 1 of the long latent."""
+        self.check_eval_mode()
+        Ht = _long_latent_h(duration)
+        rows, embeds_cf, mask_cf, embeds, mask, source_wav = self._long_edit_prompts(prompt, source_wav, num_samples, seeds)
+        B = embeds.shape[0]
+        noise, kw = self._long_edit_draws(rows, B, Ht, strength, num_steps, embeds.device)
+        keep = self.latent_keep_mask(B, (Ht, 16), time_mask_ratio_start_and_end=time_mask_ratio_start_and_end,
+                                     freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end)
+        if float(strength) < 1. and bool((keep == 1).all()):
+            keep = None       # as in `edit`: a variation without a masked span changes the whole clip
+        if cfg_scale_post > 1.:
+            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        return self.edit_long_from_embeds(embeds, mask, noise, source_wav, duration, keep, strength, cfg_scale_input,
+                                          cfg_scale_post, num_steps, sr, overlap=overlap, window_h=window_h,
+                                          sample_posterior=sample_posterior, **kw)
+
+    def _extend_inputs(self, source_wav, Ht, source_at, junction_rows, sample_posterior=False, chunk_rows=LONG_DECODE_ROWS):
+        """Source latent and keep mask of `extend`: the source's full rows encoded at their OWN extent, not padded to the
+        clip, written into a zero (B, C, Ht, W) latent at r0; the mask is 1 on the kept rows.  The encoder's mid-block
+        attention takes tokens in multiples of 64, which is rows in multiples of 4: a source of another length is filled up
+        with at most 3 rows of zero samples, on a side that borders generated audio (the right one when there is one), and
+        those rows are dropped from the encoding."""
+        source_wav = torch.as_tensor(source_wav)
+        if source_wav.ndim != 2:
+            raise ValueError("source_wav %s: expected (B, samples)" % (tuple(source_wav.shape),))
+        rows, r0, k0, k1 = _extend_rows(source_wav.shape[1], Ht, source_at, junction_rows)
+        fill = -rows % 4                                  # 0 when the source is the whole clip: Ht is a multiple of 8
+        left = fill if r0 + rows == Ht else 0
+        wav = torch.nn.functional.pad(source_wav[:, :rows * LATENT_ROW_SAMPLES].to(torch.float32),
+                                      (left * LATENT_ROW_SAMPLES, (fill - left) * LATENT_ROW_SAMPLES))
+        part = self._source_latent_chunked(wav, (rows + fill, 16), sample_posterior, chunk_rows)
+        src = torch.zeros((part.shape[0], part.shape[1], Ht, 16), dtype=torch.float32, device=part.device)
+        src[:, :, r0:r0 + rows] = part[:, :, left:left + rows]
+        keep = torch.zeros(1, 1, Ht, 16, dtype=torch.float32)
+        keep[:, :, k0:k1] = 1
+        return src, keep
+
+    @torch.no_grad()
+    def extend(self, prompt, source_wav, duration, source_at=0.0, junction_rows=2, cfg_scale_input=3., cfg_scale_post=1.,
+               num_steps=4, num_samples=1, sr=16000, overlap=64, window_h=256, sample_posterior=False, seeds=None):
+        """Continuation: prompts and source waveforms ((B, T) in [-1, 1] at 16 kHz, shorter than the clip) -> int16
+        waveforms (numpy) of int(sr * duration) samples that hold the source `source_at` seconds in and generated audio
+        around it.  A latent row is 640 samples: the source covers T // 640 full rows from row round(source_at * 25), is
+        encoded at that extent (filled up to a multiple of 4 rows, `_extend_inputs`) and kept there, less `junction_rows`
+        rows on every side that borders generated audio (those rows were encoded next to the encoder's padding).
+        source_at = 0 continues the clip;
+        source_at = duration - T / sr generates a lead-in.  A source of fewer than 8 rows, or one that does not lie inside
+        the clip, raises ValueError.  The kept region is the codec's rendering of the source, not a splice."""
+        self.check_eval_mode()
+        Ht = _long_latent_h(duration)
+        source_wav = torch.as_tensor(source_wav)
+        if source_wav.ndim != 2:
+            raise ValueError("source_wav %s: expected (B, samples)" % (tuple(source_wav.shape),))
+        _extend_rows(source_wav.shape[1], Ht, source_at, junction_rows)              # ValueError before the text encoder
+        rows, embeds_cf, mask_cf, embeds, mask, source_wav = self._long_edit_prompts(prompt, source_wav, num_samples, seeds)
+        B = embeds.shape[0]
+        noise, kw = self._long_edit_draws(rows, B, Ht, 1.0, num_steps, embeds.device)
+        if cfg_scale_post > 1.:
+            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        src, keep = self._extend_inputs(source_wav, Ht, source_at, junction_rows, sample_posterior)
+        lat = self.edit_long_latent(embeds, mask, noise, src, keep, 1.0, cfg_scale_input, cfg_scale_post, num_steps, overlap,
+                                    window_h, **kw)
+        _, pcm = self._decode_long(lat)
+        return pcm.cpu().numpy()[:, :int(sr * float(duration))]
+
+    @torch.no_grad()
+    def capture_long_edit_graph(self, batch, text_len, duration, num_steps=4, strength=1.0, cfg_scale_input=3.,
+                                cfg_scale_post=1., overlap=64, window_h=256, cross_attention_dim=1024, latent_cw=(8, 16),
+                                sr=16000, uncond_states=None, uncond_mask=None, _chunk_rows=LONG_DECODE_ROWS, seeded=False):
+        """`capture_long_graph` for edits: the r = max(1, int(strength * num_steps)) windowed queries of `edit_long_latent`,
+        the VAE decoder, HiFi-GAN and the int16 conversion as ONE hipGraph.  Returns `f(encoder_states, encoder_mask, noise,
+        src_latent, keep_mask) -> pcm` (int16 on the device, int(sr * duration) samples); `noise` is (r, B, C, Ht, W) (or
+        (B, C, Ht, W) when r == 1); the source latent and the mask ((B, 1, Ht, W) or (1, 1, Ht, W), None keeps nothing) are
+        static inputs owned by the capture, as in `capture_edit_graph`: every argument is copied in.  The waveform ->
+        latent half runs eagerly before a replay.  Bit-identical to `edit_long_latent(..., step_noise=noise[1:])` followed
+        by the eager decoder and vocoder.  `capture_long_graph`'s caveat holds: the VAE keeps ONE decoder and ONE vocoder
+        handle per extent, so captures of different durations need a module each.  `seeded=True`: as in `capture_graph`,
+        `f(encoder_states, encoder_mask, seeds, src_latent, keep_mask, samples=None)`, the graph begins with the fill of
+        the r long draws 0 .. r - 1."""
+        self.check_eval_mode()
+        dev = self.unet.device
+        Ht = _long_latent_h(duration)
+        self.long_plan(Ht, window_h, overlap)
+        C, W = latent_cw
+        src0 = torch.zeros((batch, C, Ht, W), device=dev)
+        r = _check_edit_inputs(src0, src0, None, strength, num_steps)
+        st, load = self._serving_inputs(batch, text_len, cross_attention_dim, (C, Ht, W), r, cfg_scale_post, uncond_states,
+                                        uncond_mask, False, seeded)
+        st["src"] = src0
+        st["keep"] = torch.zeros(batch, 1, Ht, W, device=dev)
+        # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
+        st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
+        samples = int(sr * float(duration))
+
+        def run():
+            self._fill_noise(st)
+            lat = self._long_edit_loop(st["enc"], st["mask"], lambda k: st["noise"][k], st["src"], st["keep"], r,
+                                       cfg_scale_input, cfg_scale_post, num_steps, overlap, window_h, st.get("unc"),
+                                       st.get("unc_mask"))
+            mel, pcm = self._decode_long(lat, st["scratch"], _chunk_rows)
+            return lat, mel, pcm
+
+        _warm_up(run, dev)
+        graph, out = _capture(run)
+
+        def replay(encoder_states, encoder_mask, noise, src_latent, keep_mask=None, **kw):
+            _check_edit_inputs(st["noise"], src_latent, keep_mask, strength, num_steps)
+            load(encoder_states, encoder_mask, noise, **kw)
+            st["src"].copy_(src_latent)
+            if keep_mask is None:
+                st["keep"].zero_()
+            else:
+                st["keep"].copy_(keep_mask)        # (1, 1, Ht, W) broadcasts over the batch
+            graph.replay()
+            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
+            return out[2][:, :samples]
+
+        replay.graph, replay.outputs, replay.latent_h, replay.queries = graph, out, Ht, r
         replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
         return replay
 

@@ -421,6 +421,23 @@ ctta_status ctta_window_fuse_renoise(const float* cond, const float* uncond, con
                                      const float* weights, const float* noise, const float* sigma, float* x0_long,
                                      float* out, int copies, int batch, int n_windows, int channels, int window_h,
                                      int latent_h, int width, void* stream);
+/* ctta_window_fuse_renoise with a long source clip: the masked sampler's blend (audioldm/ldm.py:718-805, ddim.py:210-216)
+ * on the fused x0 of a clip of another `duration` (pipeline.py:49-50,94-95).  Every layout and rule of
+ * ctta_window_fuse_renoise carries over; src_long is (batch, C, latent_h, W) f32 and keep is (batch, latent_h * W) f32, one
+ * plane per clip shared by its channels, 1 = keep the source, fractions allowed; both are required.  Per long element
+ * (b, c, h, x), every multiply and every add rounded on its own:
+ *   acc = the weighted overlap-add of ctta_window_fuse_renoise      (cond == NULL: every x_k = 0)
+ *   x0  = keep[b][h * W + x] * src_long + (1 - keep[b][h * W + x]) * acc            (torch's mul, rsub, mul, add)
+ *   z   = x0 + noise * sigma[b];   o = z / sqrt(sigma[b]^2 + 1)
+ * o goes to out at every covering window and every copy, x0 to x0_long when that is given.  cond == NULL is the sampler's
+ * start, keep * src plus noise cut into windows; noise == NULL and out == NULL together is its end, only x0_long (then
+ * required) is written.  One window of latent_h == window_h rows is ctta_consistency_edit_renoise / ctta_cfg_combine_keep
+ * bit for bit; keep == 0 with a finite source is ctta_window_fuse_renoise up to the sign of a zero. */
+ctta_status ctta_window_fuse_edit_renoise(const float* cond, const float* uncond, const float* w_post,
+                                          const int32_t* starts, const float* weights, const float* src_long,
+                                          const float* keep, const float* noise, const float* sigma, float* x0_long,
+                                          float* out, int copies, int batch, int n_windows, int channels, int window_h,
+                                          int latent_h, int width, void* stream);
 /* Seeded sampler noise: what torch.randn at easy_inference/consistencytta.py's noise draw becomes when a request carries
  * a seed.  Philox4x32-10 as published (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), one
  * block per four consecutive w of a (C, H, W) latent:

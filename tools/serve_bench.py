@@ -31,6 +31,12 @@ it replaces (see `long_leg`):
 
   python tools/serve_bench.py --long --out profiles/long_serving.json
 
+`--long-edit [--duration 30.72 --source-seconds 10.24]` runs the long-edit leg alone: the captured long edit (a source kept
+at the start of every clip, the rest generated) beside the captured plain long path at the same clips and windows, and the
+one-pass edit step beside the launches it replaces (see `long_edit_leg`):
+
+  python tools/serve_bench.py --long-edit --out profiles/long_edit_serving.json
+
 `--seeded` runs the seeded leg alone: the seeded captures (seeds in, the Philox fill at the head of the graph) beside the
 plain captures fed a device `torch.randn` per call, at the plain mode's shape and at the long leg's, and the fill launch
 beside the draws and uploads it replaces (see `seeded_leg`):
@@ -392,6 +398,198 @@ def long_leg(args):
             f.write(json.dumps(result, indent=1) + "\n")
 
 
+def long_edit_leg(args):
+    """`--long-edit`: the captured long edit (capture_long_edit_graph: `--long-clips` clips of `--duration` seconds, the
+    first `--source-seconds` of each kept from a source latent, the rest generated -- a continuation) beside the captured
+    plain long path (capture_long_graph) at the same clips, windows and `--edit-steps` queries, states in, in alternating
+    windows; the eager forms of both; and the one-pass step kernel (ctta_window_fuse_edit_renoise) beside the launches it
+    replaces (torch combine, slices, torch weighted sum, torch blend, ctta_heun_add_noise, ctta_heun_scale_model_input, the
+    cut into windows, torch.cat) and beside ctta_window_fuse_renoise on one long batch.  Both paths run on ONE module: they
+    decode the same extent, so they share its decoder and vocoder handles.  The source latent is synthetic: the waveform ->
+    latent half runs eagerly before a replay and is not part of either form."""
+    import torch
+    from consistencytta_amd import _native as N
+    from consistencytta_amd import modules, spec
+    from consistencytta_amd.models import ConsistencyTTA, _long_latent_h
+    dev = "cuda:0"
+    Bl, L, steps = args.long_clips, args.text_len, args.edit_steps
+    if args.tiny:
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        import cases
+        ucfg, (C, wh, W), overlap = dict(cases.TINY_UNET), (8, 32, 16), 8
+        duration = args.duration if args.duration is not None else 3.0
+        source_s = args.source_seconds if args.source_seconds is not None else 1.0
+        vae = modules.AutoencoderKL(ddconfig=cases.TINY_VAE_DD, embed_dim=8, scale_factor=0.9, hifigan_config=cases.TINY_HIFIGAN)
+    else:
+        ucfg, (C, wh, W), overlap = spec.LIGHT_UNET_CONFIG, (8, 256, 16), 64
+        duration = args.duration if args.duration is not None else 30.72
+        source_s = args.source_seconds if args.source_seconds is not None else 10.24
+        vae = modules.AutoencoderKL(ddconfig=spec.VAE_DDCONFIG, embed_dim=8, scale_factor=0.9227914214134216)
+    Ht = _long_latent_h(duration)
+    starts, weights = ConsistencyTTA.long_plan(Ht, wh, overlap)
+    n = len(starts)
+    if Ht <= wh:
+        raise SystemExit("--duration %.2f s is one window of %d rows: nothing to fuse" % (duration, Ht))
+    kept_rows = int(source_s * 25) - 2                     # `extend`'s plane for a source at 0 with junction_rows = 2
+    if not 0 < kept_rows < Ht:
+        raise SystemExit("--source-seconds %.2f does not lie inside the clip" % source_s)
+    D = ucfg["cross_attention_dim"]
+    pipe = ConsistencyTTA(unet_config=ucfg, vae=vae)
+    pipe.to(dev)
+    pipe.unet.init_random_(seed=0)
+    vae.init_random_(seed=1)
+    pipe.eval().requires_grad_(False)
+    W_IN = 4.0
+    g = torch.Generator(device="cpu").manual_seed(3)
+    keep = torch.zeros(1, 1, Ht, W)
+    keep[:, :, :kept_rows] = 1
+    keep = keep.to(dev)
+    batches = []
+    for _ in range(2):
+        lens = torch.randint(min(6, L), L + 1, (Bl,), generator=g)
+        src = torch.randn((Bl, C, Ht, W), generator=g) * 0.8
+        src[:, :, kept_rows + 2:] = 0                      # as `extend` builds it: zeros where there is no source
+        batches.append({"enc": (torch.randn(Bl, L, D, generator=g) * 0.25).to(dev),
+                        "mask": (torch.arange(L)[None, :] < lens[:, None]).to(dev),
+                        "noise": torch.randn((steps, Bl, C, Ht, W), generator=g).to(dev), "src": src.to(dev)})
+    scratch = torch.empty(4, dtype=torch.float32, device=dev)
+    samples = int(16000 * duration)
+
+    def eager_long(b):
+        lat = pipe.generate_long_latent(b["enc"], b["mask"], b["noise"][0], W_IN, 1.0, steps, overlap=overlap, window_h=wh,
+                                        step_noise=b["noise"][1:])
+        return pipe._decode_long(lat, scratch)[1][:, :samples]
+
+    def eager_edit(b):
+        lat = pipe.edit_long_latent(b["enc"], b["mask"], b["noise"][0], b["src"], keep, 1.0, W_IN, 1.0, steps,
+                                    overlap=overlap, window_h=wh, step_noise=b["noise"][1:])
+        return pipe._decode_long(lat, scratch)[1][:, :samples]
+
+    ref_long, ref_edit = eager_long(batches[0]).clone(), eager_edit(batches[0]).clone()
+    torch.cuda.synchronize()
+    kw0 = dict(cfg_scale_input=W_IN, num_steps=steps, overlap=overlap, window_h=wh, cross_attention_dim=D, latent_cw=(C, W))
+    gen_long = pipe.capture_long_graph(Bl, L, duration, **kw0)
+    gen_edit = pipe.capture_long_edit_graph(Bl, L, duration, **kw0)
+    b0 = batches[0]
+    parity = {"long_graph": bool(torch.equal(gen_long(b0["enc"], b0["mask"], b0["noise"]), ref_long)),
+              "long_edit_graph": bool(torch.equal(gen_edit(b0["enc"], b0["mask"], b0["noise"], b0["src"], keep), ref_edit))}
+    if not all(parity.values()):
+        raise SystemExit("a captured form differs from its eager counterpart: %s" % parity)
+
+    turn = [0]
+
+    def nxt():
+        turn[0] ^= 1
+        return batches[turn[0]]
+
+    def long_call():
+        b = nxt()
+        return gen_long(b["enc"], b["mask"], b["noise"])
+
+    def edit_call():
+        b = nxt()
+        return gen_edit(b["enc"], b["mask"], b["noise"], b["src"], keep)
+    forms = {"long_graph": long_call, "long_edit_graph": edit_call, "long_eager": lambda: eager_long(nxt()),
+             "long_edit_eager": lambda: eager_edit(nxt())}
+    for fn in forms.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    windows = {k: [] for k in forms}
+    for _ in range(args.rounds):
+        for k, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            windows[k].append((time.perf_counter() - t0) / args.steps * 1e3)
+    med = {k: statistics.median(v) for k, v in windows.items()}
+
+    # ---- the step between two queries alone: one launch against the chain it replaces, device time by events
+    c, u = (torch.randn(Bl * n, C, wh, W, generator=g).to(dev) for _ in range(2))
+    nz = torch.randn(Bl, C, Ht, W, generator=g).to(dev)
+    src = batches[0]["src"]
+    sig = torch.full((Bl,), 0.7, device=dev)
+    w = torch.full((Bl,), 2.0, device=dev)
+    wdev = weights.to(dev)
+    keep2 = keep.expand(Bl, 1, Ht, W).reshape(Bl, Ht * W).contiguous()
+    keep4 = keep2.view(Bl, 1, Ht, W)
+    host_starts = (N.c_int32 * n)(*starts)
+    n_long = C * Ht * W
+    L_ = N.lib()
+
+    def chain(cfg):
+        xw = (((1 - 2.0) * u + 2.0 * c) if cfg else c).view(Bl, n, C, wh, W)
+        x0 = torch.zeros(Bl, C, Ht, W, device=dev)
+        for k, s in enumerate(starts):
+            x0[:, :, s:s + wh] += wdev[k].view(1, 1, wh, 1) * xw[:, k]
+        x0 = keep4 * src + (1 - keep4) * x0
+        z, out = torch.empty_like(x0), torch.empty_like(x0)
+        N.check(L_.ctta_heun_add_noise(N.ptr(x0), N.ptr(nz), N.ptr(sig), N.ptr(z), Bl, n_long, N.stream_ptr()))
+        N.check(L_.ctta_heun_scale_model_input(N.ptr(z), N.ptr(sig), N.ptr(out), Bl, n_long, N.stream_ptr()))
+        cut = torch.stack([out[:, :, s:s + wh] for s in starts], dim=1).reshape(Bl * n, C, wh, W)
+        return torch.cat([cut] * 2) if cfg else cut
+
+    def fused(cfg):
+        out = torch.empty(((2 if cfg else 1) * Bl * n, C, wh, W), device=dev)
+        N.check(L_.ctta_window_fuse_edit_renoise(N.ptr(c), N.ptr(u) if cfg else N.c_void_p(0),
+                                                 N.ptr(w) if cfg else N.c_void_p(0), host_starts, N.ptr(wdev), N.ptr(src),
+                                                 N.ptr(keep2), N.ptr(nz), N.ptr(sig), N.c_void_p(0), N.ptr(out),
+                                                 2 if cfg else 1, Bl, n, C, wh, Ht, W, N.stream_ptr()))
+        return out
+
+    def fused_plain(cfg):
+        out = torch.empty(((2 if cfg else 1) * Bl * n, C, wh, W), device=dev)
+        N.check(L_.ctta_window_fuse_renoise(N.ptr(c), N.ptr(u) if cfg else N.c_void_p(0), N.ptr(w) if cfg else N.c_void_p(0),
+                                            host_starts, N.ptr(wdev), N.ptr(nz), N.ptr(sig), N.c_void_p(0), N.ptr(out),
+                                            2 if cfg else 1, Bl, n, C, wh, Ht, W, N.stream_ptr()))
+        return out
+    step_parity = {("cfg" if cfg else "cond"): bool(torch.equal(chain(cfg), fused(cfg))) for cfg in (False, True)}
+    step_forms = {"chain_cond": lambda: chain(False), "fused_cond": lambda: fused(False),
+                  "plain_fused_cond": lambda: fused_plain(False), "chain_cfg": lambda: chain(True),
+                  "fused_cfg": lambda: fused(True), "plain_fused_cfg": lambda: fused_plain(True)}
+    step_us = {k: [] for k in step_forms}
+    reps = 200
+    for _ in range(args.rounds + 1):           # the first round warms up and is dropped
+        for k, fn in step_forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            step_us[k].append(e0.elapsed_time(e1) / reps * 1e3)
+    step_med = {k: statistics.median(v[1:]) for k, v in step_us.items()}
+    result = {
+        "tool": "tools/serve_bench.py --long-edit", "device": torch.cuda.get_device_name(0), "tiny": bool(args.tiny),
+        "long": {"clips": Bl, "duration_s": duration, "latent_h": Ht, "window_h": wh, "overlap": overlap, "windows": n,
+                 "starts": starts, "unet_rows": Bl * n, "decoder_rows_x_latent_h": Bl * Ht, "seconds_of_audio": Bl * duration},
+        "source": {"seconds": source_s, "kept_rows": [0, kept_rows], "junction_rows": 2},
+        "text_len": L, "num_steps": steps, "steps_per_window": args.steps, "rounds": args.rounds, "warmup_calls": args.warmup,
+        "unit": "ms per call of one batch; step kernels: us per step, stream time by events over %d back-to-back steps "
+                "(launch cost included)" % reps,
+        "timing": "host clock around a window of calls ending in a device synchronise; forms alternate within a round",
+        "parity_bit_identical_to_eager": parity, "step_parity_equal": step_parity,
+        "ms_per_call_median": {k: round(v, 3) for k, v in med.items()},
+        "ms_per_call_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()},
+        "ratios_of_medians": {"long_edit_graph_over_long_graph": round(med["long_edit_graph"] / med["long_graph"], 4),
+                              "long_edit_eager_over_long_eager": round(med["long_edit_eager"] / med["long_eager"], 4),
+                              "long_edit_graph_over_long_edit_eager": round(med["long_edit_graph"] / med["long_edit_eager"], 4)},
+        "step_us_median": {k: round(v, 2) for k, v in step_med.items()},
+        "step_us_windows": {k: [round(x, 2) for x in v[1:]] for k, v in step_us.items()},
+        "step_fused_over_chain": {"cond": round(step_med["fused_cond"] / step_med["chain_cond"], 4),
+                                  "cfg": round(step_med["fused_cfg"] / step_med["chain_cfg"], 4)},
+        "step_edit_over_plain_fused": {"cond": round(step_med["fused_cond"] / step_med["plain_fused_cond"], 4),
+                                       "cfg": round(step_med["fused_cfg"] / step_med["plain_fused_cfg"], 4)},
+    }
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
 def seeded_leg(args):
     """`--seeded`: the seeded captures (capture_graph / capture_long_graph with seeded=True: B seeds in, one
     ctta_philox_normal launch at the head of the graph) beside the plain captures fed a device `torch.randn` per call (the
@@ -673,6 +871,10 @@ def main():
                     "fed a device torch.randn per call, and the fill launch beside the draws and uploads it replaces")
     ap.add_argument("--long", action="store_true", help="only the long-clip leg: the captured long path beside the captured "
                     "plain few-step path at the same number of U-Net rows, and the one-pass step kernel beside its chain")
+    ap.add_argument("--long-edit", action="store_true", help="only the long-edit leg: the captured long edit beside the "
+                    "captured plain long path, and the one-pass edit step kernel beside the chain it replaces")
+    ap.add_argument("--source-seconds", type=float, default=None, help="seconds of source kept at the start of every clip of "
+                    "the long-edit leg (default 10.24; --tiny: 1.0)")
     ap.add_argument("--duration", type=float, default=None, help="seconds per clip of the long leg (default 30.72; --tiny: 3.0)")
     ap.add_argument("--long-clips", type=int, default=8, help="clips per call of the long leg")
     ap.add_argument("--edit", action="store_true", help="only the editing leg: the captured edit path beside the captured "
@@ -699,6 +901,8 @@ def main():
         return edit_leg(args)
     if args.long:
         return long_leg(args)
+    if args.long_edit:
+        return long_edit_leg(args)
     if args.seeded:
         return seeded_leg(args)
     dev = "cuda:0"
