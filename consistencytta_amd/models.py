@@ -28,25 +28,15 @@ import torch
 from torch import nn
 
 from . import _native as N
-from . import dist_util, spec
+from . import dist_util, sampler, spec
 from .modules import AutoencoderKL, UNet2DConditionGuidedModel, UNet2DConditionModel
+from .sampler import _check_edit_inputs, _check_step_noise, _edit_queries, _post_cfg_fusable  # noqa: F401  (names tests import)
 from .scheduler import DDIMScheduler, DDPMScheduler, HeunDiscreteScheduler
 
 
 def randn_tensor(shape, generator=None, device=None, dtype=None):
     """diffusers.utils.randn_tensor: noise on `device` from the global (or given) RNG."""
     return torch.randn(shape, generator=generator, device=device, dtype=dtype)
-
-
-def _check_step_noise(step_noise, count, noise):
-    """`step_noise=` of the few-step samplers: (count, *noise.shape), one re-noising draw per sampler step after the first
-    query.  Raises before anything is launched."""
-    if step_noise is None:
-        return
-    want = (int(count),) + tuple(noise.shape)
-    if not torch.is_tensor(step_noise) or tuple(step_noise.shape) != want:
-        got = tuple(step_noise.shape) if torch.is_tensor(step_noise) else type(step_noise).__name__
-        raise ValueError("step_noise %s: expected %s (one draw per re-noising step)" % (got, want))
 
 
 def _seed_tensor(seeds, count=None, what="seeds"):
@@ -129,14 +119,6 @@ def _philox_fill(seeds, samples, draw0, out):
     with torch.cuda.device(out.device):
         N.check(N.lib().ctta_philox_normal(N.ptr(seeds), N.ptr(samples), B, int(draw0), draws, C, H, W, 1.0, N.ptr(out),
                                            N.stream_ptr()))
-
-
-def _post_cfg_fusable(w):
-    """Whether the kernels' post-CFG combine (ctta_consistency_renoise, ctta_cfg_combine: a = 1 - w subtracted in fp32) gives
-    torch's `(1 - w) * u + w * c` bit for bit: torch rounds the Python double 1 - w to fp32, so the two coefficients are the
-    same number whenever 1 - w is exact in fp32 (every dyadic scale: 1.5, 2, 2.5, 3 ...).  Any other scale keeps torch's own
-    combine inside the captured sequence."""
-    return bool(np.float32(1.0 - float(w)) == np.float32(1.0) - np.float32(w))
 
 
 def _env_on(name):
@@ -346,93 +328,12 @@ def _student_query(unet, sch, z_n, t, w_in, w_post, enc, mask, **unet_kw):
     return zh
 
 
-def _student_next_input(zh, B, w_post, w_dev, draw, sig, z_in):
-    """A captured Heun query's output -> the next query's input: post-CFG combine, add_noise, scale_model_input and the
-    2B-row stacking in ONE launch (ctta_consistency_renoise).  `zh`: B rows, or uncond + cond rows with post-CFG; a scale
-    the kernel cannot reproduce bit for bit (`_post_cfg_fusable`) is combined by torch first."""
-    use_cf = w_post > 1.
-    if use_cf and _post_cfg_fusable(w_post):
-        cond, unc = zh[B:], zh[:B]
-    elif use_cf:
-        cond, unc = (1 - w_post) * zh[:B] + w_post * zh[B:], None
-    else:
-        cond, unc = zh, None
-    N.check(N.lib().ctta_consistency_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
-                                             N.ptr(draw), N.ptr(sig), N.ptr(z_in), 2 if use_cf else 1, B, zh[0].numel(),
-                                             N.stream_ptr()))
-
-
-def _post_cfg_combine(zh, B, w_post, w_dev):
-    """The last query's post-CFG combine on the uncond + cond rows of `zh`: ctta_cfg_combine, or torch's own for a scale
-    the kernel cannot reproduce bit for bit."""
-    if not _post_cfg_fusable(w_post):
-        return (1 - w_post) * zh[:B] + w_post * zh[B:]
-    out = torch.empty_like(zh[:B])
-    N.check(N.lib().ctta_cfg_combine(N.ptr(zh[:B]), N.ptr(zh[B:]), N.ptr(w_dev), N.ptr(out), B, zh[0].numel(), N.stream_ptr()))
-    return out
-
-
-def _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps):
-    """The host-side rules of `ConsistencyTTA.edit_latent`, raised before anything is launched (they hold on host tensors):
-    `noise` is (B, C, H, W), or (r, B, C, H, W) in the captured form, the source has the sample's shape, the mask is
-    (B, 1, H, W) or (1, 1, H, W), `strength` lies in (0, 1].  Returns r = max(1, int(strength * num_steps)), the number of
-    queries that run (audioldm/pipeline.py:216, t_enc = int(transfer_strength * ddim_steps))."""
-    num_steps = int(num_steps)
-    if num_steps < 1:
-        raise ValueError("num_steps must be at least 1, got %d" % num_steps)
-    if not 0. < float(strength) <= 1.:
-        raise ValueError("strength %r: expected a number in (0, 1]" % (strength,))
-    sample = tuple(noise.shape[-4:])
-    if not torch.is_tensor(src_latent) or len(sample) != 4 or tuple(src_latent.shape) != sample:
-        got = tuple(src_latent.shape) if torch.is_tensor(src_latent) else type(src_latent).__name__
-        raise ValueError("src_latent %s: expected the noise's shape %s" % (got, sample))
-    B, _, H, W = sample
-    if keep_mask is not None and (not torch.is_tensor(keep_mask) or tuple(keep_mask.shape) not in ((B, 1, H, W), (1, 1, H, W))):
-        got = tuple(keep_mask.shape) if torch.is_tensor(keep_mask) else type(keep_mask).__name__
-        raise ValueError("keep_mask %s: expected (%d, 1, %d, %d) or (1, 1, %d, %d)" % (got, B, H, W, H, W))
-    return max(1, int(float(strength) * num_steps))
-
-
 def _ratio_span(extent, ratios, what):
     """[int(extent * r0), int(extent * r1)) of audioldm/ldm.py:766-767, after the checks the reference leaves out."""
     r0, r1 = (float(v) for v in ratios)
     if not (0. <= r0 <= r1 <= 1.):
         raise ValueError("%s %r: expected 0 <= start <= end <= 1" % (what, tuple(ratios)))
     return int(extent * r0), int(extent * r1)
-
-
-def _edit_next_input(zh, B, w_post, w_dev, src, keep, draw, sig, z_in):
-    """`_student_next_input` with a source clip: post-CFG combine, the blend keep * src + (1 - keep) * x0, add_noise,
-    scale_model_input and the 2B-row stacking in ONE launch (ctta_consistency_edit_renoise).  `zh` None: the sampler's
-    start, x0 = 0 before the blend.  `keep`: (B, H * W)."""
-    use_cf = w_post > 1.
-    if zh is None:
-        cond, unc = None, None
-    elif use_cf and _post_cfg_fusable(w_post):
-        cond, unc = zh[B:], zh[:B]
-    elif use_cf:
-        cond, unc = (1 - w_post) * zh[:B] + w_post * zh[B:], None
-    else:
-        cond, unc = zh, None
-    N.check(N.lib().ctta_consistency_edit_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
-                                                  N.ptr(src), N.ptr(keep), N.ptr(draw), N.ptr(sig), N.ptr(z_in),
-                                                  2 if use_cf else 1, B, src[0].numel(), keep.shape[1], N.stream_ptr()))
-
-
-def _post_cfg_combine_keep(zh, B, w_post, w_dev, src, keep):
-    """The last query of the edit sampler: `_post_cfg_combine` and the blend in one launch (ctta_cfg_combine_keep)."""
-    use_cf = w_post > 1.
-    if use_cf and _post_cfg_fusable(w_post):
-        cond, unc = zh[B:], zh[:B]
-    elif use_cf:
-        cond, unc = (1 - w_post) * zh[:B] + w_post * zh[B:], None
-    else:
-        cond, unc = zh, None
-    out = torch.empty_like(src)
-    N.check(N.lib().ctta_cfg_combine_keep(N.ptr(unc), N.ptr(cond), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
-                                          N.ptr(src), N.ptr(keep), N.ptr(out), B, src[0].numel(), keep.shape[1],
-                                          N.stream_ptr()))
-    return out
 
 
 LONG_MAX_WINDOWS = 16          # ctta_window_fuse_renoise carries the window starts in its launch arguments
@@ -448,60 +349,6 @@ def _long_latent_h(duration):
     if not 2.5 <= d <= 40.0:
         raise ValueError("duration %r: expected seconds in [2.5, 40.0]" % (duration,))
     return 8 * int(math.ceil(round(d * 25.6 / 8, 9)))      # rounded first: 7.5 s is 192 rows whatever 7.5 * 25.6 gives in binary
-
-
-def _window_rows(states, B, n, what):
-    """Text states / masks of the long-clip sampler as B * n rows, row b * n + k: B rows are repeated per window, B * n rows
-    give every window its own."""
-    if states is None or states.shape[0] not in (B, B * n):
-        got = None if states is None else tuple(states.shape)
-        raise ValueError("%s %s: expected %d rows (repeated per window) or %d (one per window)" % (what, got, B, B * n))
-    return states.repeat_interleave(n, 0) if states.shape[0] == B and n > 1 else states
-
-
-def _window_fuse(zh, B, w_post, w_dev, plan, draw, sig, latent_h, z_in=None, x0_long=None):
-    """`_student_next_input` for a clip of `latent_h` rows queried as n overlapping windows (rows b * n + k of `zh`): the
-    post-CFG combine per window, the weighted overlap-add into one long x0, add_noise with ONE long draw,
-    scale_model_input, the cut into the next windows and the 2 x stacking in ONE launch (ctta_window_fuse_renoise).  `zh`
-    None: the sampler's start, x0 = 0.  `draw` and `z_in` None: the sampler's end, the fused x0 goes to `x0_long`.
-    `plan`: (host int32 array of starts, (n, window_h) device weights)."""
-    starts, weights = plan
-    n, wh = weights.shape
-    use_cf = w_post > 1.
-    if zh is None:
-        cond, unc = None, None
-    elif use_cf and _post_cfg_fusable(w_post):
-        cond, unc = zh[B * n:], zh[:B * n]
-    elif use_cf:
-        cond, unc = (1 - w_post) * zh[:B * n] + w_post * zh[B * n:], None
-    else:
-        cond, unc = zh, None
-    C, W = (x0_long if z_in is None else z_in).shape[1], (x0_long if z_in is None else z_in).shape[3]
-    N.check(N.lib().ctta_window_fuse_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
-                                             starts, N.ptr(weights), N.ptr(draw), N.ptr(sig), N.ptr(x0_long), N.ptr(z_in),
-                                             2 if use_cf else 1, B, n, C, wh, latent_h, W, N.stream_ptr()))
-
-
-def _window_fuse_keep(zh, B, w_post, w_dev, plan, src, keep, draw, sig, latent_h, z_in=None, x0_long=None):
-    """`_window_fuse` with a long source clip: between the overlap-add and add_noise the long x0 becomes
-    keep * src + (1 - keep) * x0, still ONE launch (ctta_window_fuse_edit_renoise).  `src`: (B, C, latent_h, W); `keep`:
-    (B, latent_h * W).  `zh` None: the sampler's start, keep * src noised and cut into windows."""
-    starts, weights = plan
-    n, wh = weights.shape
-    use_cf = w_post > 1.
-    if zh is None:
-        cond, unc = None, None
-    elif use_cf and _post_cfg_fusable(w_post):
-        cond, unc = zh[B * n:], zh[:B * n]
-    elif use_cf:
-        cond, unc = (1 - w_post) * zh[:B * n] + w_post * zh[B * n:], None
-    else:
-        cond, unc = zh, None
-    C, W = src.shape[1], src.shape[3]
-    N.check(N.lib().ctta_window_fuse_edit_renoise(N.ptr(cond), N.ptr(unc), N.ptr(w_dev) if unc is not None else N.c_void_p(0),
-                                                  starts, N.ptr(weights), N.ptr(src), N.ptr(keep), N.ptr(draw), N.ptr(sig),
-                                                  N.ptr(x0_long), N.ptr(z_in), 2 if use_cf else 1, B, n, C, wh, latent_h, W,
-                                                  N.stream_ptr()))
 
 
 LATENT_ROW_SAMPLES = 640       # one latent row: 4 mel frames of 160 samples at 16 kHz, 40 ms
@@ -1438,7 +1285,7 @@ def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, 
     else:           # DDIMScheduler.add_noise's coefficient pair; the dummy row is (1, 0)
         cols = [sch.noise_coeffs(t, 1) for t in later] + [torch.tensor([[1.0], [0.0]])]
         tab = torch.cat(cols, dim=1).to(dev)                                                    # (2, K + 1)
-    w_dev = torch.full((B,), float(w_post), dtype=torch.float32, device=dev)
+    form = sampler.Plain(B, w_post, dev)
     zin = z_first.clone().contiguous()
     zh = torch.empty_like(zin)
     idx = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -1454,7 +1301,7 @@ def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, 
         first[0] = False
         zh.copy_(out)
         if heun:
-            _student_next_input(out, B, w_post, w_dev, draw, c[0], zin)
+            form.step(out, draw, c[0], zin)
         else:
             cond = (1 - w_post) * out[:B] + w_post * out[B:] if use_cf else out
             N.check(N.lib().ctta_lincomb2_rows(N.ptr(cond.contiguous()), N.ptr(draw), N.ptr(c[0]), N.ptr(c[1]), N.ptr(zin), B,
@@ -1470,7 +1317,7 @@ def _student_loop_graphed(self, sch, unet, z_first, t_first, later, step_noise, 
     unet._text_key = None       # the handle's text cache was last filled outside the module's own bookkeeping
     if not use_cf:
         return zh.clone()
-    return _post_cfg_combine(zh, B, w_post, w_dev) if heun else (1 - w_post) * zh[:B] + w_post * zh[B:]
+    return form.end(zh) if heun else (1 - w_post) * zh[:B] + w_post * zh[B:]
 
 
 AudioLCM._student_loop_graphed = _student_loop_graphed
@@ -2233,39 +2080,15 @@ class ConsistencyTTA(nn.Module):
 
     def _generate_latent_static(self, encoder_states, encoder_mask, noise, cfg_scale_input, cfg_scale_post, num_steps,
                                 uncond_states=None, uncond_mask=None, **unet_kw):
-        """`generate_latent` in the form the captured paths record: `noise` is (num_steps, B, C, H, W) -- row 0 the initial
-        draw, rows 1.. the step noise, nothing random happens here --, every query after the first takes the text K / V
-        from the handle's cache on the caller's word (`reuse_text=True`: the text states are the same tensors for the
-        whole call, the teacher loop's rule), the post-CFG combine, add_noise, scale_model_input and the 2B-row stacking
-        between two queries are ONE launch (ctta_consistency_renoise) and the final combine is ctta_cfg_combine.  Same
-        fp32 operations per element as the eager sequence, so the latent is bit-identical to `generate_latent` with
-        `step_noise=noise[1:]`."""
-        sch = self.scheduler
-        use_cf = cfg_scale_post > 1.
-        B = noise.shape[1]
-        dev = noise.device
-        w_post = None
-        if use_cf:
-            encoder_states = torch.cat([uncond_states, encoder_states])
-            encoder_mask = torch.cat([uncond_mask, encoder_mask])
-            w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev)
-        sch.set_timesteps(18, device=dev)
-        z_N = noise[0] * sch.init_noise_sigma
-        z_in = sch.scale_model_input(torch.cat([z_N] * 2) if use_cf else z_N, float(sch._timesteps_host[0]))
-        t = float(sch._timesteps_host[0])
-        sch.set_timesteps(num_steps, device=dev)
-        later = [float(v) for v in sch._timesteps_host[1::2]]
-        assert len(later) == noise.shape[0] - 1, (len(later), tuple(noise.shape))
-        for k in range(len(later) + 1):
-            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=encoder_states,
-                           encoder_attention_mask=encoder_mask, reuse_text=k > 0, **unet_kw).sample
-            if k == len(later):
-                break
-            t = later[k]
-            sig = sch._sigma_dev(sch.index_for_timestep(t), B, dev)
-            z_in = torch.empty_like(zh)
-            _student_next_input(zh, B, cfg_scale_post, w_post, noise[k + 1], sig, z_in)
-        return _post_cfg_combine(zh, B, cfg_scale_post, w_post) if use_cf else zh
+        """`generate_latent` in the form the captured paths record (`sampler.Plain`): `noise` is (num_steps, B, C, H, W) --
+        row 0 the initial draw, rows 1.. the step noise, nothing random happens here.  Same fp32 operations per element as
+        the eager sequence, so the latent is bit-identical to `generate_latent` with `step_noise=noise[1:]`.  `unet_kw`: the
+        static adapter rows of a capture with `adapters=True`."""
+        assert noise.shape[0] == int(num_steps), (num_steps, tuple(noise.shape))
+        enc, mask = sampler.stack_text(encoder_states, encoder_mask, uncond_states, uncond_mask, cfg_scale_post)
+        form = sampler.Plain(noise.shape[1], cfg_scale_post, noise.device)
+        return sampler.sample(form, self.unet, self.scheduler, enc, mask, lambda k: noise[k], num_steps, cfg_scale_input,
+                              **unet_kw)
 
     # ---- editing: the few-step sampler with a source clip (audioldm/pipeline.py:145-300, ldm.py:718-805, ddim.py:210-216)
     @staticmethod
@@ -2304,70 +2127,16 @@ class ConsistencyTTA(nn.Module):
         (B, 1, H, W) or (1, 1, H, W), None keeps nothing.  `step_noise`: (r - 1, B, C, H, W)."""
         r = _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps)
         _check_step_noise(step_noise, r - 1, noise)
+        return self._edit_sample(encoder_states, encoder_mask, sampler.draws(noise, step_noise), src_latent, keep_mask, r,
+                                 cfg_scale_input, cfg_scale_post, num_steps, uncond_states, uncond_mask, reuse_text=False)
 
-        def draw(k):
-            if k == 0:
-                return noise
-            return torch.randn_like(noise) if step_noise is None else step_noise[k - 1]
-        return self._edit_loop(encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
-                               num_steps, uncond_states, uncond_mask, static=False)
-
-    def _edit_latent_static(self, encoder_states, encoder_mask, noise, src_latent, keep_mask, cfg_scale_input, cfg_scale_post,
-                            num_steps, strength=1.0, uncond_states=None, uncond_mask=None):
-        """`edit_latent` in the form the captured path records, with `_generate_latent_static`'s rules: `noise` is
-        (r, B, C, H, W) -- row 0 the first draw, rows 1.. the step noise --, queries after the first take the text K / V
-        from the handle's cache, each step is one launch of ctta_consistency_edit_renoise and the end is
-        ctta_cfg_combine_keep."""
-        r = _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps)
-        if noise.ndim != 5 or noise.shape[0] != r:
-            raise ValueError("noise %s: expected %s (row 0 the first draw, rows 1.. the step noise)"
-                             % (tuple(noise.shape), (r,) + tuple(src_latent.shape)))
-        return self._edit_loop(encoder_states, encoder_mask, lambda k: noise[k], src_latent, keep_mask, r, cfg_scale_input,
-                               cfg_scale_post, num_steps, uncond_states, uncond_mask, static=True)
-
-    def _edit_loop(self, encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
-                   num_steps, uncond_states, uncond_mask, static):
-        """The body of `edit_latent` and `_edit_latent_static`: r queries, one launch between two of them.  `draw(k)`: the
-        k-th noise.  `static`: nothing but launches happens (text K / V reuse on the caller's word, as in a capture)."""
-        sch = self.scheduler
-        use_cf = cfg_scale_post > 1.
-        if not src_latent.is_cuda:
-            raise N.CttaError("src_latent is on %s: the HIP sampler has no CPU path" % src_latent.device)
-        dev = src_latent.device
-        B, _, H, W = src_latent.shape
-        src = src_latent.detach().to(torch.float32).contiguous()
-        if keep_mask is None:
-            keep = torch.zeros(B, H * W, dtype=torch.float32, device=dev)
-        else:
-            keep = keep_mask.detach().to(dev, torch.float32).expand(B, 1, H, W).reshape(B, H * W).contiguous()
-        w_post = None
-        if use_cf:
-            encoder_states = torch.cat([uncond_states, encoder_states])
-            encoder_mask = torch.cat([uncond_mask, encoder_mask])
-            w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev)
-        sch.set_timesteps(18, device=dev)
-        t_head = float(sch._timesteps_host[0])
-        sig = sch._sigma_dev(sch.index_for_timestep(t_head), B, dev)
-        sch.set_timesteps(num_steps, device=dev)
-        times = ([t_head] + [float(v) for v in sch._timesteps_host[1::2]])[int(num_steps) - r:]
-        copies = 2 if use_cf else 1
-        z_in = torch.empty((copies * B,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
-        first = sch._check(draw(0))
-        if r == int(num_steps):     # inpainting: keep * src, noised at the head of the 18-step table
-            _edit_next_input(None, B, cfg_scale_post, w_post, src, keep, first, sig, z_in)
-        else:                       # variation: the whole source, noised at the first remaining time
-            sig = sch._sigma_dev(sch.index_for_timestep(times[0]), B, dev)
-            N.check(N.lib().ctta_consistency_renoise(N.ptr(src), N.c_void_p(0), N.c_void_p(0), N.ptr(first), N.ptr(sig),
-                                                     N.ptr(z_in), copies, B, src[0].numel(), N.stream_ptr()))
-        for k, t in enumerate(times):
-            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=encoder_states,
-                           encoder_attention_mask=encoder_mask, reuse_text=(k > 0) if static else None).sample
-            if k == r - 1:
-                break
-            sig = sch._sigma_dev(sch.index_for_timestep(times[k + 1]), B, dev)
-            z_in = torch.empty_like(zh)
-            _edit_next_input(zh, B, cfg_scale_post, w_post, src, keep, sch._check(draw(k + 1)), sig, z_in)
-        return _post_cfg_combine_keep(zh, B, cfg_scale_post, w_post, src, keep)
+    def _edit_sample(self, encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
+                     num_steps, uncond_states, uncond_mask, reuse_text=True):
+        """The body of `edit_latent` and of the captured edit (`sampler.Keep`): the last r of the query times, `draw(k)` the
+        k-th noise.  `reuse_text`: as in `sampler.sample`; the captured form reuses the text K / V."""
+        form = sampler.Keep(src_latent, keep_mask, cfg_scale_post)
+        enc, mask = sampler.stack_text(encoder_states, encoder_mask, uncond_states, uncond_mask, cfg_scale_post)
+        return sampler.sample(form, self.unet, self.scheduler, enc, mask, draw, num_steps, cfg_scale_input, r, reuse_text)
 
     def _source_latent(self, source_wav, latent_hw, sample_posterior=False):
         """(B, T) waveforms in [-1, 1] at 16 kHz -> the scaled source latent (B, C, H, W): `wav_to_fbank` with
@@ -2420,20 +2189,11 @@ class ConsistencyTTA(nn.Module):
             raise ValueError("source_wav %s: expected (%d, samples), one clip per prompt"
                              % (tuple(source_wav.shape), B // num_samples))
         source_wav = source_wav.repeat_interleave(num_samples, 0)
-        kw = {}
-        if rows is None:
-            noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
-        else:
-            shape = torch.empty(B, 0, 256, 16)        # the strength / num_steps rules alone: r queries take r draws
-            r = _check_edit_inputs(shape, shape, None, strength, num_steps)
-            draws = self.seeded_noise(rows[0], r, (self.unet.config.in_channels, 256, 16), rows[1])
-            noise, kw["step_noise"] = draws[0], draws[1:]
+        noise, kw = self._prompt_draws(rows, B, 256, _edit_queries(strength, num_steps), cfg_scale_post, embeds_cf, mask_cf)
         keep = self.latent_keep_mask(B, (256, 16), time_mask_ratio_start_and_end=time_mask_ratio_start_and_end,
                                      freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end)
         if float(strength) < 1. and bool((keep == 1).all()):
             keep = None       # style_transfer has no mask: a variation without a masked span changes the whole clip
-        if cfg_scale_post > 1.:
-            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
         return self.edit_from_embeds(embeds, mask, noise, source_wav, keep, strength, cfg_scale_input, cfg_scale_post,
                                      num_steps, sr, sample_posterior=sample_posterior, **kw)
 
@@ -2450,44 +2210,14 @@ class ConsistencyTTA(nn.Module):
         `capture_graph` -- `replay(encoder_states, encoder_mask, seeds, src_latent, keep_mask, samples=None)`, the graph
         begins with the fill of the r draws 0 .. r - 1."""
         self.check_eval_mode()
-        dev = self.unet.device
-        src0 = torch.zeros((batch,) + tuple(latent), device=dev)
-        r = _check_edit_inputs(src0, src0, None, strength, num_steps)
+        r = _edit_queries(strength, num_steps)
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, r, cfg_scale_post, uncond_states,
                                         uncond_mask, False, seeded)
-        st["src"] = src0
-        st["keep"] = torch.zeros(batch, 1, latent[1], latent[2], device=dev)
-        # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
-        st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
-
-        def run():
-            self._fill_noise(st)
-            lat = self._edit_latent_static(st["enc"], st["mask"], st["noise"], st["src"], st["keep"], cfg_scale_input,
-                                           cfg_scale_post, num_steps, strength, st.get("unc"), st.get("unc_mask"))
-            mel = self.vae.decode_first_stage(lat)
-            wav = self.vae.vocode(mel)
-            pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
-            N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(st["scratch"]), None, N.ptr(pcm),
-                                              N.stream_ptr()))
-            return lat, mel, pcm
-
-        _warm_up(run, dev)
-        graph, out = _capture(run)
-
-        def replay(encoder_states, encoder_mask, noise, src_latent, keep_mask=None, **kw):
-            _check_edit_inputs(st["noise"], src_latent, keep_mask, strength, num_steps)
-            load(encoder_states, encoder_mask, noise, **kw)
-            st["src"].copy_(src_latent)
-            if keep_mask is None:
-                st["keep"].zero_()
-            else:
-                st["keep"].copy_(keep_mask)        # (1, 1, H, W) broadcasts over the batch
-            graph.replay()
-            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
-            return out[2]
-
-        replay.graph, replay.outputs, replay.queries = graph, out, r
-        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
+        replay = self._capture_sampler(
+            st, load, lambda: self._edit_sample(st["enc"], st["mask"], lambda k: st["noise"][k], st["src"], st["keep"], r,
+                                                cfg_scale_input, cfg_scale_post, num_steps, st.get("unc"), st.get("unc_mask")),
+            chunk_rows=None, edit=(strength, num_steps))
+        replay.queries = r
         return replay
 
     # ---- long and short clips: overlapping windows of one long latent, fused between two queries of the few-step sampler
@@ -2543,80 +2273,43 @@ class ConsistencyTTA(nn.Module):
         if not torch.is_tensor(noise) or noise.ndim != 4:
             raise ValueError("noise %s: expected (B, C, Ht, W)" % (tuple(noise.shape) if torch.is_tensor(noise) else noise,))
         _check_step_noise(step_noise, int(num_steps) - 1, noise)
+        return self._long_sample(encoder_states, encoder_mask, sampler.draws(noise, step_noise), tuple(noise.shape),
+                                 cfg_scale_input, cfg_scale_post, num_steps, overlap, window_h, uncond_states, uncond_mask)
 
-        def draw(k):
-            if k == 0:
-                return noise
-            return torch.randn_like(noise) if step_noise is None else step_noise[k - 1]
-        return self._long_loop(encoder_states, encoder_mask, draw, tuple(noise.shape), cfg_scale_input, cfg_scale_post,
-                               num_steps, overlap, window_h, uncond_states, uncond_mask)
-
-    def _long_loop(self, encoder_states, encoder_mask, draw, shape, cfg_scale_input, cfg_scale_post, num_steps, overlap,
-                   window_h, uncond_states, uncond_mask):
-        """The body of `generate_long_latent` and of the captured long path: nothing but launches once `draw(k)`, the k-th
-        long noise, is a tensor at hand.  Queries after the first take the text K / V from the handle's cache (the text
-        states are the same tensors for the whole call)."""
-        sch = self.scheduler
-        num_steps = int(num_steps)
-        if num_steps < 1:
-            raise ValueError("num_steps must be at least 1, got %d" % num_steps)
-        B, C, Ht, W = shape
-        starts, weights = self.long_plan(Ht, window_h, overlap)
-        n, wh = weights.shape
-        use_cf = cfg_scale_post > 1.
-        enc, mask = _window_rows(encoder_states, B, n, "encoder_states"), _window_rows(encoder_mask, B, n, "encoder_mask")
-        if use_cf:
-            enc = torch.cat([_window_rows(uncond_states, B, n, "uncond_states"), enc])
-            mask = torch.cat([_window_rows(uncond_mask, B, n, "uncond_mask"), mask])
-        first = sch._check(draw(0))
-        dev = first.device
-        # the weights are uploaded once per layout and device: a capture's warm-up run leaves them here, so the recorded
-        # sequence holds no host -> device copy
-        cache = self.__dict__.setdefault("_long_weights", {})
-        key = (Ht, wh, n, int(overlap), str(dev))
-        if key not in cache:
-            cache[key] = weights.to(dev)
-        plan = ((N.c_int32 * n)(*starts), cache[key])
-        w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev) if use_cf else None
-        sch.set_timesteps(18, device=dev)
-        t_head = float(sch._timesteps_host[0])
-        sig = sch._sigma_dev(sch.index_for_timestep(t_head), B, dev)
-        sch.set_timesteps(num_steps, device=dev)
-        times = [t_head] + [float(v) for v in sch._timesteps_host[1::2]]
-        copies = 2 if use_cf else 1
-        z_in = torch.empty((copies * B * n, C, wh, W), dtype=torch.float32, device=dev)
-        _window_fuse(None, B, cfg_scale_post, w_post, plan, first, sig, Ht, z_in=z_in)
-        for k, t in enumerate(times):
-            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=enc, encoder_attention_mask=mask,
-                           reuse_text=k > 0).sample
-            if k == num_steps - 1:
-                break
-            sig = sch._sigma_dev(sch.index_for_timestep(times[k + 1]), B, dev)
-            z_in = torch.empty_like(zh)
-            _window_fuse(zh, B, cfg_scale_post, w_post, plan, sch._check(draw(k + 1)), sig, Ht, z_in=z_in)
-        out = torch.empty((B, C, Ht, W), dtype=torch.float32, device=dev)
-        _window_fuse(zh, B, cfg_scale_post, w_post, plan, None, None, Ht, x0_long=out)
-        return out
+    def _long_sample(self, encoder_states, encoder_mask, draw, shape, cfg_scale_input, cfg_scale_post, num_steps, overlap,
+                     window_h, uncond_states, uncond_mask, src_latent=None, keep_mask=None, r=None):
+        """The body of `generate_long_latent`, of `edit_long_latent` (`src_latent`, `keep_mask`, the last `r` query times)
+        and of their captures (`sampler.Windows`): nothing but launches once `draw(k)`, the k-th long noise, is a tensor at
+        hand.  `shape`: (B, C, Ht, W) of the clip."""
+        if int(num_steps) < 1:
+            raise ValueError("num_steps must be at least 1, got %d" % int(num_steps))
+        plan = self.long_plan(shape[2], window_h, overlap)
+        enc, mask = sampler.stack_text(encoder_states, encoder_mask, uncond_states, uncond_mask, cfg_scale_post,
+                                       windows=(shape[0], plan[1].shape[0]))
+        dev = (draw(0) if src_latent is None else src_latent).device
+        form = sampler.Windows(plan, shape, overlap, cfg_scale_post, dev, self.__dict__.setdefault("_long_cache", {}),
+                               src_latent, keep_mask)
+        return sampler.sample(form, self.unet, self.scheduler, enc, mask, draw, num_steps, cfg_scale_input, r)
 
     def _decode_long(self, lat, scratch=None, chunk_rows=LONG_DECODE_ROWS):
         """Long latent -> (mel, int16 waveform on the device): `decode_first_stage`, `vocode` and vocoder_infer's
-        batch-global centring.  The batch is cut into chunks of at most chunk_rows // Ht clips per decoder / vocoder call;
+        batch-global centring.  The batch is cut into chunks of at most chunk_rows // Ht clips per decoder / vocoder call
+        (`chunk_rows` None: no chunking, the whole batch in one call, whatever its size);
         the centring stays over the WHOLE batch: per-chunk extrema (ctta_wav_extrema), their maximum / minimum, then
         ctta_wav_center per chunk with that pair -- the arithmetic of ctta_wav_finalize on the whole batch.  `scratch`:
         the kernels' work buffer (4 floats), the caller's in a capture."""
         B, Ht = lat.shape[0], lat.shape[2]
-        per = max(1, int(chunk_rows) // Ht)
+        per = B if chunk_rows is None else max(1, int(chunk_rows) // Ht)
         dev = lat.device
         if scratch is None:
             scratch = torch.empty(4, dtype=torch.float32, device=dev)
         L_ = N.lib()
         mels = [self.vae.decode_first_stage(lat[i:i + per]) for i in range(0, B, per)]
+        if len(mels) == 1:
+            return mels[0], self._vocode_pcm(mels[0], scratch)
         wavs = [self.vae.vocode(m) for m in mels]
         pcm = torch.empty((B, wavs[0].shape[1]), dtype=torch.int16, device=dev)
         with torch.cuda.device(dev):
-            if len(wavs) == 1:
-                N.check(L_.ctta_wav_finalize(N.ptr(wavs[0]), wavs[0].numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
-                return mels[0], pcm
             mm = torch.empty(len(wavs), 2, dtype=torch.float32, device=dev)
             for i, w in enumerate(wavs):
                 N.check(L_.ctta_wav_extrema(N.ptr(w), w.numel(), N.ptr(scratch), N.ptr(mm[i]), N.stream_ptr()))
@@ -2625,6 +2318,15 @@ class ConsistencyTTA(nn.Module):
                 N.check(L_.ctta_wav_center(N.ptr(w), w.numel(), N.ptr(both), N.ptr(scratch), None, N.ptr(pcm[i * per:]),
                                            N.stream_ptr()))
         return torch.cat(mels), pcm
+
+    def _vocode_pcm(self, mel, scratch):
+        """Mel -> int16 waveform on the device: `vocode` and vocoder_infer's batch-global centring (ctta_wav_finalize).
+        `scratch`: the kernel's work buffer (4 floats)."""
+        wav = self.vae.vocode(mel)
+        pcm = torch.empty(wav.shape, dtype=torch.int16, device=wav.device)
+        with torch.cuda.device(wav.device):
+            N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
+        return pcm
 
     @torch.no_grad()
     def generate_long_from_embeds(self, encoder_states, encoder_mask, noise, duration, cfg_scale_input=3., cfg_scale_post=1.,
@@ -2654,15 +2356,7 @@ class ConsistencyTTA(nn.Module):
         Ht = _long_latent_h(duration)
         rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
         embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
-        B = embeds.shape[0]
-        kw = {}
-        if rows is None:
-            noise = randn_tensor((B, self.unet.config.in_channels, Ht, 16), device=embeds.device, dtype=torch.float32)
-        else:
-            draws = self.seeded_noise(rows[0], num_steps, (self.unet.config.in_channels, Ht, 16), rows[1])
-            noise, kw["step_noise"] = draws[0], draws[1:]
-        if cfg_scale_post > 1.:
-            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        noise, kw = self._prompt_draws(rows, embeds.shape[0], Ht, num_steps, cfg_scale_post, embeds_cf, mask_cf)
         return self.generate_long_from_embeds(embeds, mask, noise, duration, cfg_scale_input, cfg_scale_post, num_steps, sr,
                                               overlap=overlap, **kw)
 
@@ -2682,34 +2376,17 @@ class ConsistencyTTA(nn.Module):
         `capture_graph`, `f(encoder_states, encoder_mask, seeds, samples=None)`; the fill draws the long (C, Ht, W) latent,
         whose first rows are the draw of every shorter clip under the same seed."""
         self.check_eval_mode()
-        dev = self.unet.device
         Ht = _long_latent_h(duration)
         self.long_plan(Ht, window_h, overlap)
         C, W = latent_cw
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, (C, Ht, W), num_steps, cfg_scale_post,
                                         uncond_states, uncond_mask, False, seeded)
-        # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
-        st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
-        samples = int(sr * float(duration))
-
-        def run():
-            self._fill_noise(st)
-            lat = self._long_loop(st["enc"], st["mask"], lambda k: st["noise"][k], (batch, C, Ht, W), cfg_scale_input,
-                                  cfg_scale_post, num_steps, overlap, window_h, st.get("unc"), st.get("unc_mask"))
-            mel, pcm = self._decode_long(lat, st["scratch"], _chunk_rows)
-            return lat, mel, pcm
-
-        _warm_up(run, dev)
-        graph, out = _capture(run)
-
-        def replay(*args, **kw):
-            load(*args, **kw)
-            graph.replay()
-            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
-            return out[2][:, :samples]
-
-        replay.graph, replay.outputs, replay.latent_h = graph, out, Ht
-        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
+        replay = self._capture_sampler(
+            st, load, lambda: self._long_sample(st["enc"], st["mask"], lambda k: st["noise"][k], (batch, C, Ht, W),
+                                                cfg_scale_input, cfg_scale_post, num_steps, overlap, window_h, st.get("unc"),
+                                                st.get("unc_mask")),
+            chunk_rows=_chunk_rows, samples=int(sr * float(duration)))
+        replay.latent_h = Ht
         return replay
 
     # ---- editing long clips: the windowed sampler with a long source blended into the fused x0 between two queries
@@ -2731,73 +2408,9 @@ class ConsistencyTTA(nn.Module):
             raise ValueError("noise %s: expected (B, C, Ht, W)" % (tuple(noise.shape) if torch.is_tensor(noise) else noise,))
         r = _check_edit_inputs(noise, src_latent, keep_mask, strength, num_steps)
         _check_step_noise(step_noise, r - 1, noise)
-
-        def draw(k):
-            if k == 0:
-                return noise
-            return torch.randn_like(noise) if step_noise is None else step_noise[k - 1]
-        return self._long_edit_loop(encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input,
-                                    cfg_scale_post, num_steps, overlap, window_h, uncond_states, uncond_mask)
-
-    def _long_edit_loop(self, encoder_states, encoder_mask, draw, src_latent, keep_mask, r, cfg_scale_input, cfg_scale_post,
-                        num_steps, overlap, window_h, uncond_states, uncond_mask):
-        """The body of `edit_long_latent` and of the captured long edit: `_long_loop` with `_edit_loop`'s source, mask and
-        query times.  Nothing but launches once `draw(k)`, the k-th long noise, is a tensor at hand."""
-        sch = self.scheduler
-        num_steps = int(num_steps)
-        B, C, Ht, W = src_latent.shape
-        starts, weights = self.long_plan(Ht, window_h, overlap)
-        n, wh = weights.shape
-        use_cf = cfg_scale_post > 1.
-        enc, mask = _window_rows(encoder_states, B, n, "encoder_states"), _window_rows(encoder_mask, B, n, "encoder_mask")
-        if use_cf:
-            enc = torch.cat([_window_rows(uncond_states, B, n, "uncond_states"), enc])
-            mask = torch.cat([_window_rows(uncond_mask, B, n, "uncond_mask"), mask])
-        if not src_latent.is_cuda:
-            raise N.CttaError("src_latent is on %s: the HIP sampler has no CPU path" % src_latent.device)
-        dev = src_latent.device
-        src = src_latent.detach().to(torch.float32).contiguous()
-        # the weights and the all-ones plane are uploaded once per layout and device: a capture's warm-up run leaves them
-        # here, so the recorded sequence holds no host -> device copy
-        cache = self.__dict__.setdefault("_long_weights", {})
-        key = (Ht, wh, n, int(overlap), str(dev))
-        if key not in cache:
-            cache[key] = weights.to(dev)
-        plan = ((N.c_int32 * n)(*starts), cache[key])
-        if keep_mask is None:
-            keep = torch.zeros(B, Ht * W, dtype=torch.float32, device=dev)
-        else:
-            keep = keep_mask.detach().to(dev, torch.float32).expand(B, 1, Ht, W).reshape(B, Ht * W).contiguous()
-        w_post = torch.full((B,), float(cfg_scale_post), dtype=torch.float32, device=dev) if use_cf else None
-        sch.set_timesteps(18, device=dev)
-        t_head = float(sch._timesteps_host[0])
-        sig = sch._sigma_dev(sch.index_for_timestep(t_head), B, dev)
-        sch.set_timesteps(num_steps, device=dev)
-        times = ([t_head] + [float(v) for v in sch._timesteps_host[1::2]])[num_steps - r:]
-        copies = 2 if use_cf else 1
-        z_in = torch.empty((copies * B * n, C, wh, W), dtype=torch.float32, device=dev)
-        first = sch._check(draw(0))
-        if r == num_steps:          # inpainting: keep * src, noised at the head of the 18-step table
-            start_keep = keep
-        else:                       # variation: the whole source, noised at the first remaining time
-            sig = sch._sigma_dev(sch.index_for_timestep(times[0]), B, dev)
-            ones = self.__dict__.setdefault("_long_ones", {})
-            okey = (B, Ht * W, str(dev))
-            if okey not in ones:
-                ones[okey] = torch.ones(B, Ht * W, dtype=torch.float32, device=dev)
-            start_keep = ones[okey]
-        _window_fuse_keep(None, B, cfg_scale_post, w_post, plan, src, start_keep, first, sig, Ht, z_in=z_in)
-        for k, t in enumerate(times):
-            zh = self.unet(z_in, t, guidance=cfg_scale_input, encoder_hidden_states=enc, encoder_attention_mask=mask,
-                           reuse_text=k > 0).sample
-            if k == r - 1:
-                break
-            sig = sch._sigma_dev(sch.index_for_timestep(times[k + 1]), B, dev)
-            z_in = torch.empty_like(zh)
-            _window_fuse_keep(zh, B, cfg_scale_post, w_post, plan, src, keep, sch._check(draw(k + 1)), sig, Ht, z_in=z_in)
-        out = torch.empty((B, C, Ht, W), dtype=torch.float32, device=dev)
-        _window_fuse_keep(zh, B, cfg_scale_post, w_post, plan, src, keep, None, None, Ht, x0_long=out)
-        return out
+        return self._long_sample(encoder_states, encoder_mask, sampler.draws(noise, step_noise), tuple(noise.shape),
+                                 cfg_scale_input, cfg_scale_post, num_steps, overlap, window_h, uncond_states, uncond_mask,
+                                 src_latent, keep_mask, r)
 
     def _source_latent_chunked(self, source_wav, latent_hw, sample_posterior=False, chunk_rows=LONG_DECODE_ROWS):
         """`_source_latent` with the batch cut into chunks of at most chunk_rows // H clips per encoder call, as
@@ -2833,16 +2446,6 @@ class ConsistencyTTA(nn.Module):
         _, pcm = self._decode_long(lat, chunk_rows=_chunk_rows)
         return pcm.cpu().numpy()[:, :int(sr * float(duration))]
 
-    def _long_edit_draws(self, rows, B, Ht, strength, num_steps, device):
-        """(noise, kw) of `edit_long` / `extend`: one long draw from torch's generator, or the r seeded draws 0 .. r - 1."""
-        C = self.unet.config.in_channels
-        if rows is None:
-            return randn_tensor((B, C, Ht, 16), device=device, dtype=torch.float32), {}
-        shape = torch.empty(B, 0, Ht, 16)             # the strength / num_steps rules alone: r queries take r draws
-        r = _check_edit_inputs(shape, shape, None, strength, num_steps)
-        draws = self.seeded_noise(rows[0], r, (C, Ht, 16), rows[1])
-        return draws[0], dict(step_noise=draws[1:])
-
     def _long_edit_prompts(self, prompt, source_wav, num_samples, seeds):
         """Text states, seed rows and the (B, T) source of `edit_long` / `extend`, one source clip per prompt."""
         rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
@@ -2866,13 +2469,11 @@ class ConsistencyTTA(nn.Module):
         Ht = _long_latent_h(duration)
         rows, embeds_cf, mask_cf, embeds, mask, source_wav = self._long_edit_prompts(prompt, source_wav, num_samples, seeds)
         B = embeds.shape[0]
-        noise, kw = self._long_edit_draws(rows, B, Ht, strength, num_steps, embeds.device)
+        noise, kw = self._prompt_draws(rows, B, Ht, _edit_queries(strength, num_steps), cfg_scale_post, embeds_cf, mask_cf)
         keep = self.latent_keep_mask(B, (Ht, 16), time_mask_ratio_start_and_end=time_mask_ratio_start_and_end,
                                      freq_mask_ratio_start_and_end=freq_mask_ratio_start_and_end)
         if float(strength) < 1. and bool((keep == 1).all()):
             keep = None       # as in `edit`: a variation without a masked span changes the whole clip
-        if cfg_scale_post > 1.:
-            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
         return self.edit_long_from_embeds(embeds, mask, noise, source_wav, duration, keep, strength, cfg_scale_input,
                                           cfg_scale_post, num_steps, sr, overlap=overlap, window_h=window_h,
                                           sample_posterior=sample_posterior, **kw)
@@ -2917,9 +2518,7 @@ class ConsistencyTTA(nn.Module):
         _extend_rows(source_wav.shape[1], Ht, source_at, junction_rows)              # ValueError before the text encoder
         rows, embeds_cf, mask_cf, embeds, mask, source_wav = self._long_edit_prompts(prompt, source_wav, num_samples, seeds)
         B = embeds.shape[0]
-        noise, kw = self._long_edit_draws(rows, B, Ht, 1.0, num_steps, embeds.device)
-        if cfg_scale_post > 1.:
-            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        noise, kw = self._prompt_draws(rows, B, Ht, _edit_queries(1.0, num_steps), cfg_scale_post, embeds_cf, mask_cf)
         src, keep = self._extend_inputs(source_wav, Ht, source_at, junction_rows, sample_posterior)
         lat = self.edit_long_latent(embeds, mask, noise, src, keep, 1.0, cfg_scale_input, cfg_scale_post, num_steps, overlap,
                                     window_h, **kw)
@@ -2941,44 +2540,61 @@ class ConsistencyTTA(nn.Module):
         `f(encoder_states, encoder_mask, seeds, src_latent, keep_mask, samples=None)`, the graph begins with the fill of
         the r long draws 0 .. r - 1."""
         self.check_eval_mode()
-        dev = self.unet.device
         Ht = _long_latent_h(duration)
         self.long_plan(Ht, window_h, overlap)
         C, W = latent_cw
-        src0 = torch.zeros((batch, C, Ht, W), device=dev)
-        r = _check_edit_inputs(src0, src0, None, strength, num_steps)
+        r = _edit_queries(strength, num_steps)
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, (C, Ht, W), r, cfg_scale_post, uncond_states,
                                         uncond_mask, False, seeded)
-        st["src"] = src0
-        st["keep"] = torch.zeros(batch, 1, Ht, W, device=dev)
+        replay = self._capture_sampler(
+            st, load, lambda: self._long_sample(st["enc"], st["mask"], lambda k: st["noise"][k], (batch, C, Ht, W),
+                                                cfg_scale_input, cfg_scale_post, num_steps, overlap, window_h, st.get("unc"),
+                                                st.get("unc_mask"), st["src"], st["keep"], r),
+            chunk_rows=_chunk_rows, samples=int(sr * float(duration)), edit=(strength, num_steps))
+        replay.latent_h, replay.queries = Ht, r
+        return replay
+
+    def _capture_sampler(self, st, load, sample, chunk_rows, samples=None, edit=None):
+        """What the single-graph captures share: the seeded fill (`_fill_noise`), `sample()` -> latent and the decoder
+        (`_decode_long` with `chunk_rows`; None: the whole batch in one call) recorded as ONE hipGraph after an eager
+        warm-up run, and the callable that refills the static inputs `st` through `load`, replays and returns the pcm (cut
+        to `samples` per clip).  `edit`: the (strength, num_steps) of an editing capture -- the source latent and the keep
+        mask are the static inputs `st["src"]` / `st["keep"]` made here, and the callable takes `(encoder_states,
+        encoder_mask, noise, src_latent, keep_mask=None)`, checks them on the host and copies them in.  The callable
+        carries `.graph`, `.outputs` = (latent, mel, pcm), `.uncond_states` and `.uncond_mask`."""
+        dev = self.unet.device
         # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
         st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
-        samples = int(sr * float(duration))
+        if edit is not None:
+            _, B, C, H, W = st["noise"].shape
+            st["src"] = torch.zeros((B, C, H, W), device=dev)
+            st["keep"] = torch.zeros(B, 1, H, W, device=dev)
+            load_states = load
+
+            def load(encoder_states, encoder_mask, noise, src_latent, keep_mask=None, **kw):
+                _check_edit_inputs(st["noise"], src_latent, keep_mask, *edit)
+                load_states(encoder_states, encoder_mask, noise, **kw)
+                st["src"].copy_(src_latent)
+                if keep_mask is None:
+                    st["keep"].zero_()
+                else:
+                    st["keep"].copy_(keep_mask)        # (1, 1, H, W) broadcasts over the batch
 
         def run():
             self._fill_noise(st)
-            lat = self._long_edit_loop(st["enc"], st["mask"], lambda k: st["noise"][k], st["src"], st["keep"], r,
-                                       cfg_scale_input, cfg_scale_post, num_steps, overlap, window_h, st.get("unc"),
-                                       st.get("unc_mask"))
-            mel, pcm = self._decode_long(lat, st["scratch"], _chunk_rows)
-            return lat, mel, pcm
+            lat = sample()
+            return (lat,) + self._decode_long(lat, st["scratch"], chunk_rows)
 
         _warm_up(run, dev)
         graph, out = _capture(run)
 
-        def replay(encoder_states, encoder_mask, noise, src_latent, keep_mask=None, **kw):
-            _check_edit_inputs(st["noise"], src_latent, keep_mask, strength, num_steps)
-            load(encoder_states, encoder_mask, noise, **kw)
-            st["src"].copy_(src_latent)
-            if keep_mask is None:
-                st["keep"].zero_()
-            else:
-                st["keep"].copy_(keep_mask)        # (1, 1, Ht, W) broadcasts over the batch
+        def replay(*args, **kw):
+            load(*args, **kw)
             graph.replay()
             self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
-            return out[2][:, :samples]
+            return out[2] if samples is None else out[2][:, :samples]
 
-        replay.graph, replay.outputs, replay.latent_h, replay.queries = graph, out, Ht, r
+        replay.graph, replay.outputs = graph, out
         replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
         return replay
 
@@ -3131,41 +2747,25 @@ class ConsistencyTTA(nn.Module):
         graph runs, as the seeded capture reads its seeds: one graph serves every mapping.  Composes with `seeded` and
         `from_tokens`; identical to `forward_from_embeds(..., adapters=, adapter_scales=)`."""
         self.check_eval_mode()
-        dev = self.unet.device
-        st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
-                                        uncond_states, uncond_mask, from_tokens, seeded, adapters)
-        scratch = torch.empty(4, dtype=torch.float32, device=dev)
+        st, load_inputs = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
+                                               uncond_states, uncond_mask, from_tokens, seeded, adapters)
         akw = dict(adapter_rows=st["slots"], adapter_scales=st["ascale"]) if adapters else {}
 
-        def run():
-            self._fill_noise(st)
+        def sample():
             enc, mask = self._encode_static(st) if from_tokens else (st["enc"], st["mask"])
-            lat = self._generate_latent_static(enc, mask, st["noise"], cfg_scale_input, cfg_scale_post, num_steps,
-                                               st.get("unc"), st.get("unc_mask"), **akw)
-            mel = self.vae.decode_first_stage(lat)
-            wav = self.vae.vocode(mel)
-            pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
-            N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
-            return lat, mel, pcm
+            return self._generate_latent_static(enc, mask, st["noise"], cfg_scale_input, cfg_scale_post, num_steps,
+                                                st.get("unc"), st.get("unc_mask"), **akw)
 
-        _warm_up(run, dev)
-        graph, out = _capture(run)
-
-        def replay(*args, **kw):
+        def load(*args, **kw):
             if adapters:
                 names, strengths = kw.pop("adapters", None), kw.pop("adapter_scales", None)
             elif "adapters" in kw or "adapter_scales" in kw:
                 raise ValueError("this graph was captured without adapters=True")
-            load(*args, **kw)
+            load_inputs(*args, **kw)
             if adapters:
                 st["load_adapters"](names, strengths)
-            graph.replay()
-            self.unet._text_key = None      # the handle's text cache now holds the replay's K / V, not an eager call's
-            return out[2]
 
-        replay.graph, replay.outputs = graph, out
-        replay.uncond_states, replay.uncond_mask = st.get("unc"), st.get("unc_mask")
-        return replay
+        return self._capture_sampler(st, load, sample, chunk_rows=None)
 
     def capture_pipeline(self, batch, text_len, cfg_scale_input=3., cross_attention_dim=1024, latent=(8, 256, 16),
                          candidates=8, num_steps=1, cfg_scale_post=1.0, uncond_states=None, uncond_mask=None,
@@ -3189,7 +2789,8 @@ class ConsistencyTTA(nn.Module):
         dev = self.unet.device
         st, load = self._serving_inputs(batch, text_len, cross_attention_dim, latent, num_steps, cfg_scale_post,
                                         uncond_states, uncond_mask, from_tokens, seeded)
-        scratch = torch.empty(4, dtype=torch.float32, device=dev)
+        # ctta_wav_finalize's work buffer: every replay writes it, so it lives as long as the callable (`st` does)
+        st["scratch"] = torch.empty(4, dtype=torch.float32, device=dev)
         held = ("seeds", "samples") if seeded else ("noise",)      # what waits one call beside the text states
 
         def graphed(fn):      # every stage on the stream that warmed it up
@@ -3211,12 +2812,7 @@ class ConsistencyTTA(nn.Module):
         g_v, mel = graphed(lambda: self.vae.decode_first_stage(lat_in))
         mel_in = mel.clone()
 
-        def voc():
-            wav = self.vae.vocode(mel_in)
-            pcm = torch.empty(wav.shape, dtype=torch.int16, device=dev)
-            N.check(N.lib().ctta_wav_finalize(N.ptr(wav), wav.numel(), N.ptr(scratch), None, N.ptr(pcm), N.stream_ptr()))
-            return pcm
-        g_h, pcm = graphed(voc)
+        g_h, pcm = graphed(lambda: self._vocode_pcm(mel_in, st["scratch"]))
         side_graphs = [("v", g_v), ("u", g_u)] + ([("t", g_t)] if from_tokens else [])
         streams = {k: torch.cuda.Stream(device=dev) for k, _ in side_graphs}
 
@@ -3269,6 +2865,20 @@ class ConsistencyTTA(nn.Module):
     encode_text = AudioDistilledModel.encode_text
     encode_text_classifier_free = AudioDistilledModel.encode_text_classifier_free
 
+    def _prompt_draws(self, rows, B, latent_h, count, cfg_scale_post, embeds_cf, mask_cf):
+        """(noise, kw) of the prompt-level entries: the (B, C, latent_h, 16) noise from torch's generator, or, with the
+        seed rows of `_prompt_seeds`, the seeded draws 0 .. count - 1 as noise + `step_noise`; with post-CFG the uncond
+        half of `encode_text_classifier_free` as `uncond_states` / `uncond_mask`."""
+        C, kw = self.unet.config.in_channels, {}
+        if rows is None:
+            noise = randn_tensor((B, C, latent_h, 16), device=embeds_cf.device, dtype=torch.float32)
+        else:
+            seeded = self.seeded_noise(rows[0], count, (C, latent_h, 16), rows[1])
+            noise, kw["step_noise"] = seeded[0], seeded[1:]
+        if cfg_scale_post > 1.:
+            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        return noise, kw
+
     @torch.no_grad()
     def forward(self, prompt, cfg_scale_input=3., cfg_scale_post=1., num_steps=1, num_samples=1, sr=16000, seeds=None,
                 adapters=None, adapter_scales=None):
@@ -3282,15 +2892,7 @@ class ConsistencyTTA(nn.Module):
         a_rows, a_scales = expand_adapter_rows(adapters, adapter_scales, n_prompts, num_samples)   # ValueError before any work
         rows = None if seeds is None else _prompt_seeds(seeds, prompt, num_samples)
         embeds_cf, mask_cf, embeds, mask = self.encode_text_classifier_free(prompt, num_samples)
-        B = embeds.shape[0]
-        kw = {}
-        if rows is None:
-            noise = randn_tensor((B, self.unet.config.in_channels, 256, 16), device=embeds.device, dtype=torch.float32)
-        else:
-            draws = self.seeded_noise(rows[0], num_steps, (self.unet.config.in_channels, 256, 16), rows[1])
-            noise, kw["step_noise"] = draws[0], draws[1:]
-        if cfg_scale_post > 1.:
-            kw.update(uncond_states=embeds_cf[:B], uncond_mask=mask_cf[:B])
+        noise, kw = self._prompt_draws(rows, embeds.shape[0], 256, num_steps, cfg_scale_post, embeds_cf, mask_cf)
         if a_rows is not None:
             kw.update(adapters=a_rows, adapter_scales=a_scales)
         return self.forward_from_embeds(embeds, mask, noise, cfg_scale_input, cfg_scale_post, num_steps, sr, **kw)

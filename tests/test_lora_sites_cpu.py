@@ -140,7 +140,7 @@ def test_defaults_and_cross_attention_kwargs():
 
 
 def test_merge_folds_the_modules_scale():
-    m = _lora_unet()
+    m = _lora_unet().init_deterministic(3)      # the base weights are torch.empty until set: heap leftovers may hold NaN
     m.load_state_dict(LC.lora_weights(LC.LORA_TINY_LIGHT), strict=False)
     sd = {k: v.clone() for k, v in m.state_dict().items()}
     m.lora_scale = 0.5
